@@ -9,13 +9,18 @@ sharded in contiguous blocks (align3d_amd.distributed.shard_range), every rank a
 RCCL all-gather collects the 4x4 poses in global pair order (gather_poses) — weak scaling.
 
     python bench.py --gpus 1 --steps 600 --warmup 20
+    python bench.py --gpus 1 --steps 600 --warmup 20 --dump-outputs bench_outputs
+    python bench.py --gpus 1 --full
     python bench.py --gpus N ...            (no WORLD_SIZE in the env: starts N fresh rank processes itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (WORLD_SIZE must equal N)
 
-Prints ONE JSON line on rank 0 (contract in the round instructions) with `roofline` for the dominant
-kernel (the per-pixel kernel) and `cpu_baseline` (the CPU oracle timed on a bounded sample); `extra` holds the
-secondary workloads (kd-tree, Icp, frame preparation, odometry, streaming), each with its own roofline and CPU
-baseline, and the min / median / max of repeated timings."""
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps, writes the last step's poses
+with --dump-outputs and prints the line: `value` and `ms_per_step` come from the timed steps, and so does its
+`roofline` (the step's algorithmic bytes over the timed step); `cpu_baseline` is null.  With --full the line
+also carries `roofline` for the dominant kernel (the per-pixel kernel) from per-launch event timing and
+`cpu_baseline` (the CPU oracle timed on a bounded sample); `extra` holds the secondary workloads (kd-tree, Icp,
+frame preparation, odometry, streaming), each with its own roofline and CPU baseline, and the min / median / max of
+repeated timings."""
 import argparse
 import ctypes as C
 import glob
@@ -1224,6 +1229,21 @@ def launch_ranks(n, argv):
     return rc
 
 
+def dump_outputs(directory, poses, status, gathered=None):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 .npy files — per pair the
+    pose's translation (x, y, z) and unit quaternion (i, j, k, w) and the status (0 = A3D_OK), and with N > 1 the
+    gathered row-major 4x4 pose matrices of every rank in global pair order."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"pose_translation": np.array([p.t for p in poses], np.float32),
+              "pose_quaternion": np.array([p.q for p in poses], np.float32),
+              "pair_status": np.asarray(status, np.float32)}
+    if gathered is not None:
+        arrays["gathered_pose_matrices"] = np.asarray(gathered, np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"wrote {', '.join(f'{k}{list(v.shape)}' for k, v in arrays.items())} to {directory}")
+
+
 def run_leg(errors, name, fn, *a, **kw):
     """One secondary measurement.  A failure costs that leg only: it is logged, recorded under extra.errors and the line is
     still printed (an exception in any leg after the timed region used to lose the whole line)."""
@@ -1515,10 +1535,20 @@ def main():
     ap.add_argument("--rehearse-collective", action="store_true",
                     help="run the N > 1 code path (process group, all-gather on the context stream) even with one "
                          "rank: checks the RCCL path on a one-GPU box (launch under torchrun --nproc-per-node 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (float32): its pairs' poses "
+                         "and per-pair status, and with N > 1 the gathered pose matrices of every rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: repeated timings, the per-launch "
+                         "roofline, the copy ceiling, the secondary workloads (unless --no-extras), the CPU baselines and "
+                         "parity legs (unless --cpu-pairs 0), the accuracy against the synthetic ground truth, the "
+                         "gathered poses against the local ones, and the detail file")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:  # nobody launched ranks for us: do it here, before anything touches the GPU
             sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1628,11 +1658,17 @@ def main():
 
     out = None
     if rank == 0:
+        # what the last timed step computed, read before anything else runs on the batch
+        poses, status = batch.results()
+        gathered_host = gathered.cpu().numpy() if multi else None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, poses, status, gathered_host)
         errors = {}
         # ---- repeated short timings of the same step (>= 20 repetitions, min / median / max) ----
         rep_steps = max(1, min(30, args.steps))
-        reps = [] if multi else (run_leg(errors, "repeated_timings", repeated_step_timings, ctx, batch, rep_steps) or [])
-        r = run_leg(errors, "roofline", headline_roofline, ctx, batch, params, P, W, H, distinct, ms_per_step)
+        reps = [] if multi or not args.full else (
+            run_leg(errors, "repeated_timings", repeated_step_timings, ctx, batch, rep_steps) or [])
+        r = run_leg(errors, "roofline", headline_roofline, ctx, batch, params, P, W, H, distinct, ms_per_step) if args.full else None
         iters = [int(p.max_iterations) for p in params]
         if r:
             roof, step_alg_bytes, iters = r
@@ -1640,10 +1676,11 @@ def main():
             step_alg_bytes = P * sum(iters[l] * level_bytes(W >> l, H >> l) for l in range(len(params)))
             ach = step_alg_bytes / (ms_per_step * 1e-3) / 1e9
             roof = {"bound": "hbm", "kernel": "image_icp_head_kernel", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": ach / HBM_PEAK_GBS, "traffic": None, "note": "from the timed step: the per-launch passes failed"}
-        if not args.no_extras:  # the chip's own ceiling beside the nominal 8 TB/s (N > 1 too: VERDICT r5 item 2)
+                    "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                    "note": ("from the timed step: the per-launch passes failed" if args.full
+                             else "from the timed step (the per-launch passes run with --full)")}
+        if args.full and not args.no_extras:  # the chip's own ceiling beside the nominal 8 TB/s (N > 1 too: VERDICT r5 item 2)
             run_leg(errors, "copy_ceiling", add_copy_ceiling, roof, device)
-        poses, status = batch.align()
         failed_pairs = int(np.count_nonzero(status))
         roof["failed_pairs"] = failed_pairs  # a failed pair freezes and its blocks stop working: must be 0
 
@@ -1653,30 +1690,33 @@ def main():
             for l, fr in enumerate(live_pixel_fractions(ctx, params, targets[0], sources[0], poses[0])):
                 roof[f"level{l}_live_pixel_frac_pair0"] = fr
 
-        run_leg(errors, "live_pixel_fractions", live_fractions)
+        if args.full:
+            run_leg(errors, "live_pixel_fractions", live_fractions)
         extra = {"failed_pairs": failed_pairs,
                  "timing": {"timed_region_s": elapsed, "ms_per_step_repeated": stats(reps) if reps else None,
-                            "steps_per_repeat": rep_steps, "repeats_x_steps": f"{len(reps)} x {rep_steps}"}}
+                            "steps_per_repeat": rep_steps, "repeats_x_steps": f"{len(reps)} x {rep_steps}"}
+                 if args.full else {"timed_region_s": elapsed}}
         if multi:  # the gathered buffer holds every rank's block in global pair order; this rank's starts at lo
-            own = gathered[lo:hi].cpu().numpy().reshape(P, 4, 4)
-            extra["gather_matches_local_poses"] = bool(
-                all(np.allclose(own[p], poses[p].matrix(), atol=1e-6) for p in range(P)))
+            if args.full:
+                own = gathered_host[lo:hi].reshape(P, 4, 4)
+                extra["gather_matches_local_poses"] = bool(
+                    all(np.allclose(own[p], poses[p].matrix(), atol=1e-6) for p in range(P)))
             extra["gathered_pairs"] = int(gathered.shape[0])
             if args.dump_gathered:
-                np.save(args.dump_gathered, gathered.cpu().numpy())
-        # accuracy against the synthetic ground truth (reported, not a parity claim)
-        errs = []
-        for p, (fa, fb) in enumerate(pair_frames):
-            gt = synth.relative_pose(poses_gt[fa], poses_gt[fb])
-            d = np.linalg.inv(gt) @ poses[p].matrix().astype(np.float64)
-            errs.append((np.arccos(np.clip((np.trace(d[:3, :3]) - 1) / 2, -1, 1)), np.linalg.norm(d[:3, 3])))
-        extra["mean_error_vs_synthetic_gt"] = {"angle_rad": float(np.mean([e[0] for e in errs])),
-                                               "translation_m": float(np.mean([e[1] for e in errs]))}
+                np.save(args.dump_gathered, gathered_host)
+        if args.full:  # accuracy against the synthetic ground truth (reported, not a parity claim)
+            errs = []
+            for p, (fa, fb) in enumerate(pair_frames):
+                gt = synth.relative_pose(poses_gt[fa], poses_gt[fb])
+                d = np.linalg.inv(gt) @ poses[p].matrix().astype(np.float64)
+                errs.append((np.arccos(np.clip((np.trace(d[:3, :3]) - 1) / 2, -1, 1)), np.linalg.norm(d[:3, 3])))
+            extra["mean_error_vs_synthetic_gt"] = {"angle_rad": float(np.mean([e[0] for e in errs])),
+                                                   "translation_m": float(np.mean([e[1] for e in errs]))}
         keep = {"level0_host": None, "depth0": None, "clouds": None, "bench_icp_clouds": None, "poses_pinned": None}
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             keep = secondary_legs(ctx, errors, extra, params, targets, sources, P, W, H, build_ms, ms_per_step, step_alg_bytes)
         cpu = None
-        if args.cpu_pairs > 0:
+        if args.full and args.cpu_pairs > 0:
             cpu = cpu_legs(ctx, errors, extra, args, world, host_pyramids, pair_frames, params, P, poses, targets, sources, keep)
         if errors:
             extra["errors"] = errors
@@ -1707,7 +1747,10 @@ def main():
     batch.free()
     if multi:
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and not args.full:  # a plain run writes no detail file: the line holds all it measured
+        sys.stdout.flush()
+        os.write(json_fd, (compact_line(out) + "\n").encode())
+    elif rank == 0:
         detail = None
         try:  # the full result (lists, per-level / per-pair tables, statistics): a file, not stdout
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)

@@ -11,7 +11,7 @@ for cfg in "$@"; do
   extra=""
   case "$cfg" in *--*) extra="${cfg#*--}";; esac
   echo "== $cfg"
-  env $envs timeout -k 10 300 python3 bench.py --steps $STEPS --warmup $WARMUP --no-extras --cpu-pairs 0 $extra 2>/dev/null | python3 -c "
+  env $envs timeout -k 10 300 python3 bench.py --steps $STEPS --warmup $WARMUP --full --no-extras --cpu-pairs 0 $extra 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -35,7 +35,7 @@ def test_two_fresh_ranks_align_their_own_blocks_and_gather(ctx, tmp_path, shared
     P = 8
     dump = str(tmp_path / "gathered.npy")
     args = ["--gpus", "2", "--backend", "gloo", "--device", "0", "--pairs-per-gpu", str(P), "--steps", "3", "--warmup", "1",
-            "--no-extras", "--cpu-pairs", "0", "--dump-gathered", dump] + (["--shared-frames"] if shared else [])
+            "--full", "--no-extras", "--cpu-pairs", "0", "--dump-gathered", dump] + (["--shared-frames"] if shared else [])
     r = run_bench(args)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -130,7 +130,7 @@ def test_four_fresh_ranks_keep_global_pair_order(ctx, tmp_path):
     P, N = 2, 4
     dump = str(tmp_path / "gathered.npy")
     r = run_bench(["--gpus", str(N), "--backend", "gloo", "--device", "0", "--pairs-per-gpu", str(P), "--steps", "2",
-                   "--warmup", "1", "--no-extras", "--cpu-pairs", "2", "--cpu-orders", "3", "--dump-gathered", dump])
+                   "--warmup", "1", "--full", "--no-extras", "--cpu-pairs", "2", "--cpu-orders", "3", "--dump-gathered", dump])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -179,7 +179,7 @@ def test_two_rank_line_carries_the_copy_ceiling():
     """The default N > 1 run (no --no-extras) also measures the chip's own copy ceiling on rank 0's device (a child
     process, while the other ranks wait at the barrier): `hbm_copy_ceiling_GBs` and `frac_of_copy_ceiling` in the line."""
     r = run_bench(["--gpus", "2", "--backend", "gloo", "--device", "0", "--pairs-per-gpu", "2", "--steps", "2", "--warmup", "1",
-                   "--cpu-pairs", "1", "--cpu-orders", "2"])
+                   "--full", "--cpu-pairs", "1", "--cpu-orders", "2"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -207,7 +207,7 @@ def test_the_drivers_launch_form_with_one_rank_goes_through_rccl():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rehearse-collective", "--pairs-per-gpu", "4",
-           "--steps", "2", "--warmup", "1", "--no-extras", "--cpu-pairs", "1", "--cpu-orders", "2"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--cpu-pairs", "1", "--cpu-orders", "2"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -216,3 +216,39 @@ def test_the_drivers_launch_form_with_one_rank_goes_through_rccl():
     assert out["n_gpus"] == 1 and out["config"]["ranks_in_collective"] == 1 and out["config"]["gathered_pairs"] == 4
     assert out["config"]["gather_matches_local_poses"] is True and "RCCL" in out["config"]["collective"]
     assert out["roofline"]["failed_pairs"] == 0 and out["cpu_baseline"] is not None
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_its_last_timed_step_computed(ctx, tmp_path):
+    """A plain one-GPU run (no --full): the line carries the headline's contract keys from the timed steps alone, and
+    --dump-outputs writes the last timed step's poses and status, which equal bit for bit a single-process batch of the
+    same pairs (stream 1000)."""
+    P = 4
+    dump = tmp_path / "outputs"
+    r = run_bench(["--gpus", "1", "--pairs-per-gpu", str(P), "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "frame-pairs/s" and out["dtype"] == "f32"
+    assert abs(out["value"] - P / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert out["cpu_baseline"] is None and out["detail_file"] is None and out["roofline"]["failed_pairs"] == 0
+    t, q, st = (np.load(dump / f"{n}.npy") for n in ("pose_translation", "pose_quaternion", "pair_status"))
+    assert t.shape == (P, 3) and q.shape == (P, 4) and st.shape == (P,)
+    assert t.dtype == q.dtype == st.dtype == np.float32 and not st.any()
+
+    import bench
+    from align3d_amd import IcpParams, MsIcpParams, MultiscaleAlignBatch
+
+    pyr, _, _ = bench.build_stream_pyramids(ctx, seed=1000, n_frames=2 * P, width=640, height=480)
+    batch = MultiscaleAlignBatch(ctx, MsIcpParams.repeat(3, IcpParams.default()), [pyr[2 * p] for p in range(P)],
+                                 [pyr[2 * p + 1] for p in range(P)])
+    poses, status = batch.align()
+    batch.free()
+    for lv in (lv for pp in pyr for lv in pp):
+        lv.free()
+    assert not status.any()
+    assert np.array_equal(t.view(np.uint32), np.array([p.t for p in poses], np.float32).view(np.uint32))
+    assert np.array_equal(q.view(np.uint32), np.array([p.q for p in poses], np.float32).view(np.uint32))
