@@ -313,6 +313,13 @@ struct a3d_device_image {
   a3d::DeviceArena* arena = nullptr;     // when set, the arrays above are carved out of it and not freed one by one
   bool built = false;        // made by the device frame builder (its arena layout is fixed when it is planned)
   bool mask_is_z = false;    // built with a depth scale for which mask == (z != 0) on every pixel (frame.hip)
+  // Level 0 of a device-built pyramid: the filtered u16 depth plane [h][w] each point was back-projected from (0 =
+  // invalid) and the f32 constants of that back-projection.  points_from_depth: every point equals
+  // backproject_px(depth16, row, col, bp_*, depth_scale) (devmath.hpp) bit for bit and mask == (depth16 != 0); set by the
+  // frame builder only, on level 0, only together with mask_is_z.  Uploaded images never carry it.
+  uint16_t* depth16 = nullptr;
+  float depth_scale = 0, bp_fx = 0, bp_fy = 0, bp_cx = 0, bp_cy = 0;
+  bool points_from_depth = false;
   bool own_normals = false;  // `normals` is its own hipMalloc although the image lives in an arena (uploaded without
                              // normals, a3d_range_image_compute_normals called later)
 };

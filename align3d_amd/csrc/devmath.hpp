@@ -221,6 +221,29 @@ __device__ __forceinline__ float div_by(float a, const DivBy d) {
 __device__ __forceinline__ bool div_den_ok(float z) { return (fabsf(z) > 1e-9f) & (fabsf(z) < 1e9f); }
 __device__ __forceinline__ bool div_num_ok(float a) { return (a == 0.0f) | ((fabsf(a) > 1e-20f) & (fabsf(a) < 1e9f)); }
 
+// CameraIntrinsics::backproject (camera.rs:101-107) of a (filtered) u16 depth: z = d scale, x = (u - cx) z / fx,
+// y = (v - cy) z / fy; (0,0,0) for an invalid pixel (mask = depth > 0, structure.rs:56-95).  ONE definition for the frame
+// builder (which stores the point) and the level-0 alignment kernel (which rebuilds it from the stored depth plane,
+// image_icp.hip DEPTH16): both inline this function under the same flags, so the two points are the same bits.
+// dfx / dfy = div_prepare(fx / fy), focal_ok = div_den_ok(fx) & div_den_ok(fy).
+__device__ __forceinline__ V3 backproject_px(uint32_t d, int row, int col, float fx, float fy, float cx, float cy, float scale,
+                                             const DivBy dfx, const DivBy dfy, bool focal_ok) {
+  V3 p{0.f, 0.f, 0.f};
+  if (d > 0) {
+    p.z = (float)d * scale;
+    const float ax = ((float)col - cx) * p.z, ay = ((float)row - cy) * p.z;
+    // the two IEEE quotients by the (uniform) focal lengths through their refined reciprocals (div_by: bit-identical to `/`
+    // inside its operand range); plain division for the wave when anything is outside it
+    const bool fast = focal_ok & div_num_ok(ax) & div_num_ok(ay);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fast) != 0ull, 0)) {
+      p.x = ax / fx, p.y = ay / fy;
+    } else {
+      p.x = ax == 0.0f ? ax : div_by(ax, dfx), p.y = ay == 0.0f ? ay : div_by(ay, dfy);
+    }
+  }
+  return p;
+}
+
 
 // The per-pixel body of RangeImage::compute_normals (src/range_image/structure.rs:207-257) as the kernels evaluate it:
 // the same decisions and the same bits as normal_from_neighbours below (the reference's operations in the reference's

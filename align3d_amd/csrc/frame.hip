@@ -66,6 +66,21 @@ __device__ __forceinline__ void st_u8u_stream(void* base, uint32_t idx, uint8_t 
   __builtin_nontemporal_store(v, (uint8_t __attribute__((address_space(1)))*)((a3d_gptr)base + idx));
 #endif
 }
+__device__ __forceinline__ void st_u16u_stream(void* base, uint32_t idx, uint16_t v) {
+#ifdef A3D_BUILDER_NO_NT
+  *(uint16_t __attribute__((address_space(1)))*)((a3d_gptr)base + idx * 2u) = v;
+#else
+  __builtin_nontemporal_store(v, (uint16_t __attribute__((address_space(1)))*)((a3d_gptr)base + idx * 2u));
+#endif
+}
+// two horizontally adjacent u16 (idx even: 4-byte aligned)
+__device__ __forceinline__ void st_u16x2u_stream(void* base, uint32_t idx, uint32_t lo, uint32_t hi) {
+#ifdef A3D_BUILDER_NO_NT
+  *(uint32_t __attribute__((address_space(1)))*)((a3d_gptr)base + idx * 2u) = lo | (hi << 16);
+#else
+  __builtin_nontemporal_store(lo | (hi << 16), (uint32_t __attribute__((address_space(1)))*)((a3d_gptr)base + idx * 2u));
+#endif
+}
 __device__ __forceinline__ V3 ld_v3g(const float* base, size_t idx) {
   const f32x3 v = *(const f32x3_u*)(base + 3 * idx);
   return V3{v.x, v.y, v.z};
@@ -75,6 +90,7 @@ __device__ __forceinline__ V3 ld_v3g(const float* base, size_t idx) {
 struct LevelLayout {
   uint32_t w, h;
   size_t points, mask, normals, colors, intensities, imap;
+  size_t depth16;  // level 0 only (else 0): the filtered depth each point was back-projected from, u16 [h][w], 0 = invalid
 };
 constexpr uint32_t MAX_LEVELS = 16;
 struct PyramidLayout {
@@ -136,7 +152,7 @@ __global__ void __launch_bounds__(L0_THREADS)
     level0_kernel(const uint16_t* __restrict__ depth, uint32_t w, uint32_t h, double inv_ss, double inv_sc,
                   const double* __restrict__ grids, unsigned long long capacity, uint32_t* __restrict__ scal, float fx,
                   float fy, float cx, float cy, float scale, FrameBases bases, size_t off_points, size_t off_mask,
-                  size_t off_normals, bool with_normals, LevelLayout L1, bool emit_l1) {
+                  size_t off_normals, size_t off_depth16, bool with_normals, LevelLayout L1, bool emit_l1) {
   __shared__ float sp[3][ST_H][ST_W + 1];
   __shared__ float sn[3][OWN_H][OWN_W + 1];  // the owned pixels' normals, for the fused level-1 pick
   __shared__ uint8_t sm[ST_H][ST_W];         // their masks (1: depth > 0)
@@ -176,18 +192,8 @@ __global__ void __launch_bounds__(L0_THREADS)
           d[k] = v;
         }
       }
-      if (d[k] > 0) {  // CameraIntrinsics::backproject (camera.rs:101-107): x = (u - cx) z / fx, y = (v - cy) z / fy
-        pz[k] = (float)d[k] * scale;
-        const float ax = ((float)col - cx) * pz[k], ay = ((float)row[k] - cy) * pz[k];
-        // the two IEEE quotients by the (uniform) focal lengths through their refined reciprocals (div_by: bit-identical
-        // to `/` inside its operand range, devmath.hpp); plain division for the wave when anything is outside it
-        const bool fast = focal_ok & div_num_ok(ax) & div_num_ok(ay);
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fast) != 0ull, 0)) {
-          px[k] = ax / fx, py[k] = ay / fy;
-        } else {
-          px[k] = ax == 0.0f ? ax : div_by(ax, dfx), py[k] = ay == 0.0f ? ay : div_by(ay, dfy);
-        }
-      }
+      const V3 p = backproject_px(d[k], row[k], col, fx, fy, cx, cy, scale, dfx, dfy, focal_ok);  // (devmath.hpp)
+      px[k] = p.x, py[k] = p.y, pz[k] = p.z;
     }
     sp[0][ly[k]][lx] = px[k], sp[1][ly[k]][lx] = py[k], sp[2][ly[k]][lx] = pz[k];
     sm[ly[k]][lx] = d[k] > 0 ? 1 : 0;
@@ -216,6 +222,7 @@ __global__ void __launch_bounds__(L0_THREADS)
       const uint32_t idx = __umul24((uint32_t)row[k], w) + (uint32_t)col;
       st_v3u_stream(base + off_points, idx, V3{px[k], py[k], pz[k]});
       st_u8u_stream(base + off_mask, idx, d[k] > 0 ? 1 : 0);
+      st_u16u_stream(base + off_depth16, idx, (uint16_t)d[k]);  // (the depth the point was back-projected from)
       if (with_normals) st_v3u_stream(base + off_normals, idx, nrm[k]);
     }
   if (!emit_l1 || A3D_L0_PROBE == 3 || A3D_L0_PROBE == 4) return;
@@ -273,32 +280,16 @@ __global__ void __launch_bounds__(L0_THREADS)
 // shared-reciprocal quotients, normal_from_neighbours_dev, pick_nearest_to_mean): same bits.
 constexpr int QS = 32, QT = QS / 2;
 
-// CameraIntrinsics::backproject (camera.rs:101-107) of a filtered depth: x = (u - cx) z / fx, y = (v - cy) z / fy; (0,0,0)
-// for an invalid pixel (mask = depth > 0, structure.rs:56-95).
-__device__ __forceinline__ V3 backproject_px(uint32_t d, int row, int col, float fx, float fy, float cx, float cy, float scale,
-                                             const DivBy dfx, const DivBy dfy, bool focal_ok) {
-  V3 p{0.f, 0.f, 0.f};
-  if (d > 0) {
-    p.z = (float)d * scale;
-    const float ax = ((float)col - cx) * p.z, ay = ((float)row - cy) * p.z;
-    // the two IEEE quotients by the (uniform) focal lengths through their refined reciprocals (div_by: bit-identical to `/`
-    // inside its operand range, devmath.hpp); plain division for the wave when anything is outside it
-    const bool fast = focal_ok & div_num_ok(ax) & div_num_ok(ay);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fast) != 0ull, 0)) {
-      p.x = ax / fx, p.y = ay / fy;
-    } else {
-      p.x = ax == 0.0f ? ax : div_by(ax, dfx), p.y = ay == 0.0f ? ay : div_by(ay, dfy);
-    }
-  }
-  return p;
-}
+// (backproject_px, the back-projection of one filtered depth, is in devmath.hpp: the alignment kernel rebuilds level-0
+// points from the stored depth plane with the same function)
 
 template <bool FILTER>
 __global__ void __launch_bounds__(256)
     level0_quad_kernel(const uint16_t* __restrict__ depth, uint32_t w, uint32_t h, double inv_ss, double inv_sc,
                        const double* __restrict__ grids, unsigned long long capacity, uint32_t* __restrict__ scal, float fx,
                        float fy, float cx, float cy, float scale, FrameBases bases, size_t off_points, size_t off_mask,
-                       size_t off_normals, bool with_normals, LevelLayout L1, bool emit_l1, LevelLayout L2, bool emit_l2,
+                       size_t off_normals, size_t off_depth16, bool with_normals, LevelLayout L1, bool emit_l1, LevelLayout L2,
+                       bool emit_l2,
                        bool l2_is_last, Unsplat unsplat, uint32_t patches_x, uint32_t patches_y) {
   __shared__ float sp[3][QS + 2][QS + 3];  // the patch's points at (y + 1, x + 1), halo included
   __shared__ float s1[2][3][QT][QT + 1];   // level-1 picks (0: points, 1: normals) for the level-2 picks
@@ -496,6 +487,22 @@ __global__ void __launch_bounds__(256)
                                                                                (__umul24((uint32_t)(r0 + my), w) + (uint32_t)(c0 + mx))));
   }
   store_rows(off_points, !mask_words);
+  // the depth plane: the filtered depth each stored point was back-projected from (0 = invalid), straight from the quad's
+  // registers — a patch row of it is 64 bytes, so a row-ordered store would cover no more whole lines than this: one dword
+  // per quad row (pixels 2 tx, 2 tx + 1) when the width is even (every quad row then starts 4-byte aligned), else per pixel
+  if (A3D_LQ_PROBE != 1) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      if (!rin[a]) continue;
+      const uint32_t i0 = __umul24((uint32_t)row[a], w) + (uint32_t)col[0];
+      if ((w & 1u) == 0) {  // (block-uniform; col[1] < w whenever col[0] < w)
+        if (cin[0]) st_u16x2u_stream(base + off_depth16, i0, d[a][0], d[a][1]);
+      } else {
+        if (cin[0]) st_u16u_stream(base + off_depth16, i0, (uint16_t)d[a][0]);
+        if (cin[1]) st_u16u_stream(base + off_depth16, i0 + 1u, (uint16_t)d[a][1]);
+      }
+    }
+  }
   if (with_normals) {  // (block-uniform)
     __syncthreads();
 #pragma unroll
@@ -929,6 +936,7 @@ ArenaPlan plan_arena(uint32_t w, uint32_t h, const a3d_builder_params* prm) {
     L.colors = take(n * 3);
     L.points = take(n * 12);
     L.mask = take(n);
+    L.depth16 = l == 0 ? take(n * 2) : 0;
     L.normals = prm->with_normals ? take(n * 12) : 0;
     L.intensities = prm->with_intensity ? take(n) : 0;
     L.imap = prm->with_intensity ? take((size_t)(L.w + 2) * (L.h + 2) * 4) : 0;
@@ -991,8 +999,8 @@ a3d_status enqueue_chunk(a3d_context* ctx, const a3d_builder_params* prm, uint32
     if (quad) {
       hipLaunchKernelGGL(level0_quad_kernel<true>, dim3(gridq.x * gridq.y * gridq.z), dim3(256), 0, s, d_depth, w, h, 1.0 / prm->sigma_space,
                          1.0 / prm->sigma_color, (const double*)gb.blurred, gb.capacity, gb.scal, fx, fy, cx, cy, depth_scale,
-                         bases, L0.points, L0.mask, L0.normals, prm->with_normals != 0, P.lv[1], fuse_l1, L2, fuse_l2, l2_is_last,
-                         gb.unsplat, gridq.x, gridq.y);
+                         bases, L0.points, L0.mask, L0.normals, L0.depth16, prm->with_normals != 0, P.lv[1], fuse_l1, L2, fuse_l2,
+                         l2_is_last, gb.unsplat, gridq.x, gridq.y);
       if (defer) {
         A3D_HIP_TRY(hipGetLastError());
         ctx->grid_clean = gb.clean;  // (the zeros are back once this kernel has run)
@@ -1002,20 +1010,21 @@ a3d_status enqueue_chunk(a3d_context* ctx, const a3d_builder_params* prm, uint32
     else
       hipLaunchKernelGGL(level0_kernel<true>, dim3((w + OWN_W - 1) / OWN_W, (h + OWN_H - 1) / OWN_H, F), dim3(L0_THREADS), 0, s,
                          d_depth, w, h, 1.0 / prm->sigma_space, 1.0 / prm->sigma_color, (const double*)gb.blurred, gb.capacity,
-                         gb.scal, fx, fy, cx, cy, depth_scale, bases, L0.points, L0.mask, L0.normals, prm->with_normals != 0,
-                         P.lv[1], fuse_l1);
+                         gb.scal, fx, fy, cx, cy, depth_scale, bases, L0.points, L0.mask, L0.normals, L0.depth16,
+                         prm->with_normals != 0, P.lv[1], fuse_l1);
 #endif
     A3D_HIP_TRY(hipMemcpyAsync(result, gb.scal, (size_t)F * SC_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   } else {
     if (quad)
       hipLaunchKernelGGL(level0_quad_kernel<false>, dim3(gridq.x * gridq.y * gridq.z), dim3(256), 0, s, d_depth, w, h, 0.0, 0.0,
                          (const double*)nullptr, 0ull, (uint32_t*)nullptr, fx, fy, cx, cy, depth_scale, bases, L0.points, L0.mask,
-                         L0.normals, prm->with_normals != 0, P.lv[1], fuse_l1, L2, fuse_l2, l2_is_last, Unsplat{}, gridq.x, gridq.y);
+                         L0.normals, L0.depth16, prm->with_normals != 0, P.lv[1], fuse_l1, L2, fuse_l2, l2_is_last, Unsplat{},
+                         gridq.x, gridq.y);
 #ifdef A3D_DIAGNOSTICS
     else
       hipLaunchKernelGGL(level0_kernel<false>, dim3((w + OWN_W - 1) / OWN_W, (h + OWN_H - 1) / OWN_H, F), dim3(L0_THREADS), 0, s,
                          d_depth, w, h, 0.0, 0.0, (const double*)nullptr, 0ull, (uint32_t*)nullptr, fx, fy, cx, cy, depth_scale,
-                         bases, L0.points, L0.mask, L0.normals, prm->with_normals != 0, P.lv[1], fuse_l1);
+                         bases, L0.points, L0.mask, L0.normals, L0.depth16, prm->with_normals != 0, P.lv[1], fuse_l1);
 #endif
   }
   // RangeImage::pyramid (structure.rs:342-351): normals exist at level 0 only (builder.rs:79-82), coarser levels
@@ -1068,7 +1077,7 @@ struct Chunk {
 // earlier chunk reads), followed by an event the compute stream waits for.
 a3d_status chunk_prepare(a3d_context* ctx, const a3d_builder_params* prm, const ArenaPlan& plan, Chunk& c,
                          const uint16_t* const* depth, const uint8_t* const* rgb, uint32_t w, uint32_t h, double fx,
-                         double fy, double cx, double cy, hipEvent_t uploaded, bool mask_is_z) {
+                         double fy, double cx, double cy, float depth_scale, hipEvent_t uploaded, bool mask_is_z) {
   const size_t n = (size_t)w * h;
   const uint64_t L = prm->pyramid_levels;
   for (uint32_t f = 0; f < c.F; ++f) {
@@ -1092,6 +1101,14 @@ a3d_status chunk_prepare(a3d_context* ctx, const a3d_builder_params* prm, const 
       im->fx64 = fx * k, im->fy64 = fy * k, im->cx64 = cx * k, im->cy64 = cy * k;
       im->fx = (float)im->fx64, im->fy = (float)im->fy64, im->cx = (float)im->cx64, im->cy = (float)im->cy64;
       char* b = (char*)arena->base;
+      if (l == 0) {
+        // the level-0 kernel back-projected every point from this plane with (float)fx .. (float)cy and this scale —
+        // exactly the image's own fx .. cy at level 0 — so a point is backproject_px of its depth (devmath.hpp)
+        im->depth16 = (uint16_t*)(b + Y.depth16);
+        im->depth_scale = depth_scale;
+        im->bp_fx = (float)fx, im->bp_fy = (float)fy, im->bp_cx = (float)cx, im->bp_cy = (float)cy;
+        im->points_from_depth = mask_is_z;
+      }
       im->colors = (uint8_t*)(b + Y.colors), im->points = (float*)(b + Y.points), im->mask = (uint8_t*)(b + Y.mask);
       if (prm->with_normals) im->normals = (float*)(b + Y.normals), im->has_normals = true;
       if (prm->with_intensity) {
@@ -1178,8 +1195,8 @@ a3d_status build_frames(a3d_context* ctx, const a3d_builder_params* prm, uint64_
     c.result = ctx->pinned_words + k * (MAX_BATCH * SC_STRIDE);
     const float fscale = (float)depth_scale;
     const bool mask_is_z = fscale >= 1.1754944e-38f && std::isfinite(fscale);  // 1.0f * scale != 0, and so is d * scale
-    const a3d_status st = chunk_prepare(ctx, prm, plan, c, depth + f0, rgb + f0, w, h, fx, fy, cx, cy, ctx->copy_events[k],
-                                        mask_is_z);
+    const a3d_status st = chunk_prepare(ctx, prm, plan, c, depth + f0, rgb + f0, w, h, fx, fy, cx, cy, fscale,
+                                        ctx->copy_events[k], mask_is_z);
     if (st != A3D_OK) return fail(st);
   }
   std::vector<size_t> todo(n_chunks);
@@ -1379,5 +1396,21 @@ a3d_status a3d_range_image_download(a3d_device_image* im, float* points, uint8_t
   A3D_HIP_TRY(hipStreamSynchronize(s));
   return A3D_OK;
 }
+
+#ifdef A3D_DIAGNOSTICS
+a3d_status a3d_range_image_download_depth16(a3d_device_image* im, uint16_t* out_depth, float out_backproject[5],
+                                            int32_t* out_points_from_depth) {
+  A3D_REQUIRE(im && out_depth && out_backproject && out_points_from_depth, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE(im->depth16, A3D_MISSING_FIELD, "image has no depth plane");
+  hipSetDevice(im->ctx->device);
+  const size_t n = (size_t)im->width * im->height;
+  A3D_HIP_TRY(hipMemcpyAsync(out_depth, im->depth16, n * 2, hipMemcpyDeviceToHost, im->ctx->stream));
+  A3D_HIP_TRY(hipStreamSynchronize(im->ctx->stream));
+  out_backproject[0] = im->bp_fx, out_backproject[1] = im->bp_fy, out_backproject[2] = im->bp_cx;
+  out_backproject[3] = im->bp_cy, out_backproject[4] = im->depth_scale;
+  *out_points_from_depth = im->points_from_depth ? 1 : 0;
+  return A3D_OK;
+}
+#endif
 
 }  // extern "C"

@@ -26,11 +26,18 @@ struct LevelDesc {
   uint32_t src_n;
   uint32_t tw, th;
   float fx, fy, cx, cy;
-  uint32_t flags;  // bit 0: both images carry mask_is_z
+  uint32_t flags;  // bit 0: both images carry mask_is_z; bit 1: both carry points_from_depth (common.hpp)
   uint32_t ppt;    // source pixels per thread at this level: the pair's tiles are ceil(src_n / (256 ppt)) blocks
+  uint32_t src_w;  // source width (DEPTH16: the source pixel's row and column)
+  // DEPTH16 (level 0 of device-built pyramids): the depth planes the points were back-projected from, and each side's
+  // back-projection constants: fx, fy, cx, cy, depth scale
+  const uint16_t* src_depth;  // [src_n]
+  const uint16_t* tgt_depth;  // [th*tw]
+  float src_bp[5], tgt_bp[5];
+  float src_inv_w;            // 1.0f / src_w (correctly rounded, host)
   uint32_t pad;
 };
-static_assert(sizeof(LevelDesc) == 96, "LevelDesc layout");
+static_assert(sizeof(LevelDesc) == 160, "LevelDesc layout");
 
 struct Gates {
   float max_distance_sqr;
@@ -106,14 +113,55 @@ struct SrcPx {  // stage A: one source record
   uint8_t intensity;   // the raw byte; converted to f32 where it is used (stage D), two steps after its load,
                        // so that the conversion does not wait for the load inside the step that issued it
   bool live;
+  uint32_t depth, row, col;  // D16 & D16_SRC: the raw u16 depth (back-projected in stage B, where it is consumed) and its pixel
 };
+// The back-projection constants of one side (DEPTH16), wave-uniform: fx, fy, cx, cy, scale, the two shared reciprocals.
+struct BackProj {
+  float fx, fy, cx, cy, scale;
+  DivBy dfx, dfy;
+  bool focal_ok;
+};
+struct BackProj2 {
+  BackProj src, tgt;
+};
+__device__ __forceinline__ float uniform_f(float x) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
+}
+__device__ __forceinline__ BackProj make_backproj(const float (&k)[5]) {
+  BackProj b;
+  b.fx = k[0], b.fy = k[1], b.cx = k[2], b.cy = k[3], b.scale = k[4];
+  // (computed once per kernel in the VALU; readfirstlane parks the results in SGPRs, not in eight VGPRs)
+  const DivBy dx = div_prepare(b.fx), dy = div_prepare(b.fy);
+  b.dfx = DivBy{uniform_f(dx.negz), uniform_f(dx.y)}, b.dfy = DivBy{uniform_f(dy.negz), uniform_f(dy.y)};
+  b.focal_ok = div_den_ok(b.fx) & div_den_ok(b.fy);
+  return b;
+}
+// DEPTH16 sides (the D16 template argument of the stages): D16_TGT the target point is rebuilt from the gathered u16 depth,
+// D16_SRC the source point from the streamed one.  A3D_ICP_DEPTH16_SRC=0 (compile time): target only, source points read.
+constexpr int D16_TGT = 1, D16_SRC = 2;
+#ifndef A3D_ICP_DEPTH16_SRC
+#define A3D_ICP_DEPTH16_SRC 1
+#endif
+constexpr int D16_SIDES = D16_TGT | (A3D_ICP_DEPTH16_SRC ? D16_SRC : 0);
 // ZMASK: both images of the pair were made by the device frame builder with a depth scale that maps every depth
 // unit to a non-zero z, so a pixel's mask is 1 exactly when its point's z is not 0 (invalid pixels are stored as
 // (0, 0, 0), frame.hip) — the two mask bytes per pixel need not be read.  Decided per launch on the host.
-template <bool ZMASK = false>
+// D16 & D16_SRC (level 0 of device-built pyramids, decided per launch on the host): the record is the pixel's 2-byte depth
+// instead of its 12-byte point; mask == (depth != 0) on these images.
+template <bool ZMASK = false, int D16 = 0>
 __device__ __forceinline__ SrcPx stage_a(const LevelDesc& d, uint32_t i, bool in_range) {
   const uint32_t ii = in_range ? i : 0u;
   SrcPx s;
+  if (D16 & D16_SRC) {
+    // row = floor((ii + 0.5) / w) in f32: exact below 2^22 pixels (the host checks) — (ii + 0.5) is representable, the two
+    // roundings move the quotient by less than 2^-23 of itself, less than its distance 0.5 / w from an integer
+    const uint32_t r = f32_as_usize(((float)ii + 0.5f) * d.src_inv_w);
+    s.row = r, s.col = ii - __umul24(r, d.src_w);
+    s.depth = ld<uint16_t>(d.src_depth, ii * 2u);
+    s.intensity = ld<uint8_t>(d.src_intensities, ii);
+    s.live = in_range;  // & (depth != 0): in stage B, where the depth is consumed
+    return s;
+  }
   s.sp = ld_v3(d.src_points, ii);
   s.intensity = ld<uint8_t>(d.src_intensities, ii);
   if (ZMASK) {
@@ -133,11 +181,20 @@ struct ProjPx {  // stage B: transformed point, projection, the gathered target 
   V3 tp, tn;
   uint8_t tmask;  // consumed in stage C, so that stage B only ISSUES the gathers
   bool live;
+  uint32_t tdepth, trow, tcol;  // D16 & D16_TGT: the gathered u16 depth and its pixel (tp is rebuilt in stage C)
 };
-template <bool ZMASK = false>
-__device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, const SrcPx& s, float twf, float thf) {
+template <bool ZMASK = false, int D16 = 0>
+__device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, const SrcPx& s, float twf, float thf,
+                                          const BackProj2& bp = BackProj2{}) {
   ProjPx o;
-  o.p = transform_vector(T, s.sp);
+  V3 sp = s.sp;
+  bool slive = s.live;
+  if (D16 & D16_SRC) {  // the source point from its depth: the builder's own function (devmath.hpp), the same bits
+    sp = backproject_px(s.depth, (int)s.row, (int)s.col, bp.src.fx, bp.src.fy, bp.src.cx, bp.src.cy, bp.src.scale, bp.src.dfx,
+                        bp.src.dfy, bp.src.focal_ok);
+    slive = slive & (s.depth != 0u);
+  }
+  o.p = transform_vector(T, sp);
   // CameraIntrinsics::project (src/camera.rs:64-70): x * fx / z + cx
   const float z = o.p.z, au = o.p.x * d.fx, av = o.p.y * d.fy;
   const DivBy dz = div_prepare(z);
@@ -150,9 +207,15 @@ __device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, con
   o.v = qv + d.cy;
   // (u + 0.5) as i32 -> as usize -> get_point bounds test: in range iff -1 < x < dim (NaN casts to 0)
   const float ur = o.u + 0.5f, vr = o.v + 0.5f;
-  o.live = s.live & !((ur <= -1.0f) | (ur >= twf) | (vr <= -1.0f) | (vr >= thf));
+  o.live = slive & !((ur <= -1.0f) | (ur >= twf) | (vr <= -1.0f) | (vr >= thf));
   const uint32_t col = (uint32_t)f32_as_i32(ur), row = (uint32_t)f32_as_i32(vr);  // (NaN casts to 0)
   const uint32_t tidx = o.live ? __umul24(row, d.tw) + col : 0u;
+  if (D16 & D16_TGT) {  // 2 bytes instead of the 12-byte point (and the mask byte: mask == (depth != 0))
+    o.tdepth = ld<uint16_t>(d.tgt_depth, tidx * 2u);
+    o.trow = row, o.tcol = col;
+    o.tn = ld_v3(d.tgt_normals, tidx);
+    return o;
+  }
   o.tp = ld_v3(d.tgt_points, tidx);
   o.tn = ld_v3(d.tgt_normals, tidx);
   o.tmask = ZMASK ? (uint8_t)0 : ld<uint8_t>(d.tgt_mask, tidx);
@@ -163,13 +226,23 @@ struct MapPx {  // stage C: gates passed, the intensity-map cell
   float t00, t10, t01, t11;
   uint32_t ui, vi;
 };
-template <bool ZMASK = false>
-__device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, ProjPx& px, uint32_t mw) {
+template <bool ZMASK = false, int D16 = 0>
+__device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, ProjPx& px, uint32_t mw,
+                                         const BackProj2& bp = BackProj2{}) {
+  bool tvalid;
+  if (D16 & D16_TGT) {  // the gathered depth lands here: the target point of the builder's own function, the same bits
+    const uint32_t td = px.live ? px.tdepth : 0u;  // (a rejected lane's row / column are not a pixel's: no point)
+    px.tp = backproject_px(td, (int)px.trow, (int)px.tcol, bp.tgt.fx, bp.tgt.fy, bp.tgt.cx, bp.tgt.cy, bp.tgt.scale,
+                           bp.tgt.dfx, bp.tgt.dfy, bp.tgt.focal_ok);
+    tvalid = td != 0u;
+  } else {
+    tvalid = ZMASK ? px.tp.z != 0.0f : px.tmask == 1;  // RangeImage::get_point: mask == 1 (structure.rs:176)
+  }
   const V3 diff = px.tp - px.p;
   // angle_between_normals(&p, &n) >= max_normal_angle on the POINT p; NaN (|p.n| > 1) passes (image_icp.rs:118-123)
   const float pn = dot(px.p, px.tn);
   // (bitwise on purpose: the short-circuit form compiles to three nested exec-mask branches per pixel)
-  px.live = px.live & (ZMASK ? px.tp.z != 0.0f : px.tmask == 1)    // RangeImage::get_point: mask == 1 (structure.rs:176)
+  px.live = px.live & tvalid
             & !(norm_squared(diff) > gt.max_distance_sqr)        // image_icp.rs:114
             & !((pn >= -1.0f) & (pn <= gt.dot_reject_max));
   MapPx m;
@@ -429,25 +502,28 @@ __global__ void __launch_bounds__(256)
 // cost a full drain of the pipeline per pixel before they were found.
 // The first two source records do not depend on the pose: the callers issue them (pixel_source_at) BEFORE they wait
 // for the pose of the iteration, so those loads are in flight during the head.
-template <bool ZMASK>
+template <bool ZMASK, int D16 = 0>
 __device__ __forceinline__ SrcPx pixel_source_at(const LevelDesc& d, uint32_t base, int ppt, int k0) {
   const uint32_t i = base + (uint32_t)k0 * 256u;
-  return stage_a<ZMASK>(d, i, (k0 < ppt) && (i < d.src_n));
+  return stage_a<ZMASK, D16>(d, i, (k0 < ppt) && (i < d.src_n));
 }
-template <bool ZMASK>
+template <bool ZMASK, int D16 = 0>
 __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, const Pose& T, uint32_t base, int ppt,
                                            const SrcPx& s0, SrcPx sa, float (&acc)[GN_PARTIAL]) {
   const uint32_t mw = d.tw + 2;
   const float twf = (float)d.tw, thf = (float)d.th;
+  BackProj2 bp{};
+  if (D16 & D16_SRC) bp.src = make_backproj(d.src_bp);
+  if (D16 & D16_TGT) bp.tgt = make_backproj(d.tgt_bp);
   SrcPx sb;
-  ProjPx pa = stage_b<ZMASK>(d, T, s0, twf, thf), pb;
+  ProjPx pa = stage_b<ZMASK, D16>(d, T, s0, twf, thf, bp), pb;
   uint8_t ia = s0.intensity, ib;
   // one step: `cur` holds the projected pixel k, `s_next` the source record of pixel k+1 (consumed here); leaves the
   // projected pixel k+1 in `nxt` and the source record of pixel k+2 in `s_new`
   auto step = [&](ProjPx& cur, uint8_t cur_i, ProjPx& nxt, uint8_t& nxt_i, const SrcPx& s_next, SrcPx& s_new, int k0) {
-    s_new = pixel_source_at<ZMASK>(d, base, ppt, k0 + 2);  // issue source record k+2
-    const MapPx mp = stage_c<ZMASK>(d, gt, cur, mw);        // gathers(k) land; issue map cell(k)
-    nxt = stage_b<ZMASK>(d, T, s_next, twf, thf);           // issue gathers(k+1)
+    s_new = pixel_source_at<ZMASK, D16>(d, base, ppt, k0 + 2);  // issue source record k+2
+    const MapPx mp = stage_c<ZMASK, D16>(d, gt, cur, mw, bp);     // gathers(k) land; issue map cell(k)
+    nxt = stage_b<ZMASK, D16>(d, T, s_next, twf, thf, bp);        // issue gathers(k+1)
     nxt_i = s_next.intensity;
     if (cur.live) {
       const Terms t = stage_d(d, gt, cur, mp, cur_i, mw);
@@ -467,7 +543,9 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
 // launch and runs the solve (head_advance), then takes the pixel pass with the resulting pose and stores its own
 // partial with plain stores.  State and partials alternate between two buffers (in / out).  A pair whose own tile
 // count is below the grid's (a smaller image in a mixed batch) leaves the surplus blocks to store zero partials.
-template <bool ZMASK>
+// DEPTH16: level 0 of a batch whose every image carries points_from_depth — the points are rebuilt from the u16 depth
+// planes (D16_SIDES: the target's, and the source's unless A3D_ICP_DEPTH16_SRC=0) instead of read.
+template <bool ZMASK, bool DEPTH16>
 __global__ void __launch_bounds__(256, 1)
     image_icp_head_kernel(const LevelDesc* __restrict__ descs, const JobState* __restrict__ states_in,
                           JobState* __restrict__ states_out, Gates gt, const float* __restrict__ partials_in,
@@ -491,7 +569,8 @@ __global__ void __launch_bounds__(256, 1)
   const LevelDesc d = descs[pair];
   const int ppt = (int)d.ppt;
   const uint32_t base = tile * (256u * (uint32_t)ppt) + threadIdx.x;
-  const SrcPx s0 = pixel_source_at<ZMASK>(d, base, ppt, 0), s1 = pixel_source_at<ZMASK>(d, base, ppt, 1);
+  constexpr int D16 = DEPTH16 ? D16_SIDES : 0;
+  const SrcPx s0 = pixel_source_at<ZMASK, D16>(d, base, ppt, 0), s1 = pixel_source_at<ZMASK, D16>(d, base, ppt, 1);
   A3D_HEAD_STAMP(1);  // descriptor loaded, first source pixels requested
   head_advance(states_in + pair, tile == 0 ? states_out + pair : nullptr, partials_in + (size_t)pair * job_stride, head,
                pair, s_state, tile == 0);
@@ -499,7 +578,7 @@ __global__ void __launch_bounds__(256, 1)
   if ((int)s_state[15] == A3D_OK) {  // a failed job stays frozen: its blocks contribute nothing
     auto uni = [&](int k) { return __uint_as_float(__builtin_amdgcn_readfirstlane(s_state[k])); };
     const Pose T{{uni(0), uni(1), uni(2)}, {uni(3), uni(4), uni(5), uni(6)}};
-    pixel_pass<ZMASK>(d, gt, T, base, ppt, s0, s1, acc);
+    pixel_pass<ZMASK, D16>(d, gt, T, base, ppt, s0, s1, acc);
   }
   A3D_HEAD_STAMP(3);  // pixel pass done
   block_reduce_store<GN_PARTIAL, false>(acc, partials_out + (size_t)pair * job_stride + (size_t)tile * GN_PARTIAL);
@@ -657,7 +736,7 @@ __global__ void __launch_bounds__(256, 4)  // four blocks per CU: what plan_tili
     for (uint32_t it = 0; it < lv.iterations; ++it) {
       const uint32_t base0 = rank * (256u * (uint32_t)ppt) + threadIdx.x;
       SrcPx s0{}, s1{};
-      if (mine) s0 = pixel_source_at<ZMASK>(d, base0, ppt, 0), s1 = pixel_source_at<ZMASK>(d, base0, ppt, 1);
+      if (mine) s0 = pixel_source_at<ZMASK, 0>(d, base0, ppt, 0), s1 = pixel_source_at<ZMASK, 0>(d, base0, ppt, 1);
       head(rank == 0);
       if (!alive) break;
       const bool ok = (int)s_state[15] == A3D_OK;  // (a failed pair stays frozen: its blocks publish zeros)
@@ -670,8 +749,8 @@ __global__ void __launch_bounds__(256, 4)  // four blocks per CU: what plan_tili
         for (int k = 0; k < GN_PARTIAL; ++k) acc[k] = 0.0f;
         if (ok && tile < own_tiles) {
           const uint32_t base = tile * (256u * (uint32_t)ppt) + threadIdx.x;
-          if (tile != rank) s0 = pixel_source_at<ZMASK>(d, base, ppt, 0), s1 = pixel_source_at<ZMASK>(d, base, ppt, 1);
-          pixel_pass<ZMASK>(d, lv.gates, T, base, ppt, s0, s1, acc);
+          if (tile != rank) s0 = pixel_source_at<ZMASK, 0>(d, base, ppt, 0), s1 = pixel_source_at<ZMASK, 0>(d, base, ppt, 1);
+          pixel_pass<ZMASK, 0>(d, lv.gates, T, base, ppt, s0, s1, acc);
         }
         block_reduce_store<GN_PARTIAL, true>(acc, job_partials + (size_t)(seq & 1u) * partials_half + (size_t)tile * GN_PARTIAL);
         __syncthreads();  // (the reduction's LDS is reused by the next tile)
@@ -1054,6 +1133,8 @@ struct a3d_multiscale_batch {
   // every image of the batch was built on the device with masks that equal (z != 0): the kernels skip the two mask
   // bytes per pixel
   bool zmask = false;
+  // and every level-0 image carries its depth plane (points_from_depth): level 0 rebuilds the points from it (DEPTH16)
+  bool depth16 = false;
   // Pair groups launched on separate streams: one group's launch ramp and head overlap the other groups' streaming
   // (pairs are independent, so the groups never synchronise until the final read-out).
   uint32_t n_streams = 1;
@@ -1112,6 +1193,15 @@ a3d_status fill_desc(const a3d_device_image* target, const a3d_device_image* sou
   d->fx = target->fx, d->fy = target->fy, d->cx = target->cx, d->cy = target->cy;
   d->flags = (target->mask_is_z && source->mask_is_z) ? 1u : 0u;
   d->ppt = 2, d->pad = 0;
+  d->src_w = source->width;
+  d->src_inv_w = 1.0f / (float)std::max(1u, source->width);
+  const bool from_depth = target->points_from_depth && source->points_from_depth && target->depth16 && source->depth16;
+  if (from_depth) d->flags |= 2u;
+  d->src_depth = from_depth ? source->depth16 : nullptr;
+  d->tgt_depth = from_depth ? target->depth16 : nullptr;
+  const float sbp[5] = {source->bp_fx, source->bp_fy, source->bp_cx, source->bp_cy, source->depth_scale};
+  const float tbp[5] = {target->bp_fx, target->bp_fy, target->bp_cx, target->bp_cy, target->depth_scale};
+  for (int k = 0; k < 5; ++k) d->src_bp[k] = sbp[k], d->tgt_bp[k] = tbp[k];
   return A3D_OK;
 }
 
@@ -1264,12 +1354,15 @@ a3d_status launch_head_kernel(a3d_multiscale_batch* b, uint32_t level, uint32_t 
   const float* part_in = b->d_partials + (size_t)((seq + 1u) & 1u) * b->partials_half + (size_t)p0 * job_stride;
   float* part_out = b->d_partials + (size_t)(seq & 1u) * b->partials_half + (size_t)p0 * job_stride;
   const LevelDesc* descs = b->d_descs + (size_t)level * P + p0;
-  if (b->zmask)
-    hipLaunchKernelGGL(image_icp_head_kernel<true>, dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in, st_out,
-                       b->gates[level], part_in, part_out, job_stride, prev);
+  if (b->depth16 && level == 0)
+    hipLaunchKernelGGL((image_icp_head_kernel<true, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
+                       st_out, b->gates[level], part_in, part_out, job_stride, prev);
+  else if (b->zmask)
+    hipLaunchKernelGGL((image_icp_head_kernel<true, false>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
+                       st_out, b->gates[level], part_in, part_out, job_stride, prev);
   else
-    hipLaunchKernelGGL(image_icp_head_kernel<false>, dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in, st_out,
-                       b->gates[level], part_in, part_out, job_stride, prev);
+    hipLaunchKernelGGL((image_icp_head_kernel<false, false>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
+                       st_out, b->gates[level], part_in, part_out, job_stride, prev);
   A3D_HIP_TRY(hipGetLastError());
   return A3D_OK;
 }
@@ -1284,6 +1377,15 @@ a3d_status batch_commit_descs(a3d_multiscale_batch* b) {
   const char* zenv = A3D_DIAG_ENV("A3D_ICP_ZMASK");
   b->zmask = !(zenv && atoi(zenv) == 0);
   for (const LevelDesc& dsc : b->h_descs) b->zmask = b->zmask && (dsc.flags & 1u);
+  // DEPTH16, level 0 only, with the rule ZMASK uses: every pair's two images carry the flag (and the source's row and
+  // column come out of an f32 quotient that is exact below 2^22 pixels); the diagnostics build's A3D_ICP_DEPTH16=0 reads
+  // the points instead
+  const char* denv = A3D_DIAG_ENV("A3D_ICP_DEPTH16");
+  b->depth16 = b->zmask && L > 0 && !(denv && atoi(denv) == 0);
+  for (uint32_t p = 0; p < P && b->depth16; ++p) {
+    const LevelDesc& dsc = b->h_descs[p];
+    b->depth16 = (dsc.flags & 2u) && dsc.src_n <= (1u << 22);
+  }
   b->partials_half = max_partials;  // floats per buffer: the launches alternate between two
   if (b->partials_capacity < 2 * max_partials) {  // grow-only: a reused engine keeps its buffer
     if (b->d_partials) A3D_HIP_TRY(hipFree(b->d_partials));
@@ -1315,7 +1417,8 @@ a3d_status batch_create(a3d_context* ctx, const a3d_icp_params* params, uint32_t
       per_cu = fallback_per_cu;
     return (uint32_t)std::max(1, ctx->num_cus) * (uint32_t)std::max(0, per_cu);
   };
-  b->resident_blocks = resident(image_icp_head_kernel<true>, 4);
+  // (the tiling of every level follows this kernel's occupancy, whichever form a level runs: same sums, same bits)
+  b->resident_blocks = resident(image_icp_head_kernel<true, false>, 4);
 #ifdef A3D_DIAGNOSTICS
   b->persist_resident_blocks = resident(image_icp_persistent_kernel<true>, 0);
   if (const char* env = getenv("A3D_ICP_ACCUM")) {

@@ -299,6 +299,12 @@ a3d_status a3d_image_icp_accumulate_exact(a3d_context* ctx, const a3d_icp_params
 a3d_status a3d_image_icp_accumulate_weighted(a3d_context* ctx, const a3d_icp_params* params,
                                              const a3d_device_image* target, const a3d_device_image* source,
                                              const a3d_pose* pose, a3d_gn_state* out_state);
+/* Level 0 of a device-built pyramid: the u16 depth plane its points were back-projected from (width * height, 0 =
+ * invalid), the f32 back-projection constants {fx, fy, cx, cy, depth scale} and whether the image carries
+ * points_from_depth (the alignment kernel then rebuilds level-0 points from the plane).  A3D_MISSING_FIELD for any other
+ * image.  Test hook. */
+a3d_status a3d_range_image_download_depth16(a3d_device_image* image, uint16_t* out_depth, float out_backproject[5],
+                                            int32_t* out_points_from_depth);
 #endif /* A3D_DIAGNOSTICS */
 
 /* ---- instrumentation that SHIPS in the product library -------------------------------------------------------
