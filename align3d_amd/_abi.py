@@ -242,6 +242,7 @@ DIAG_SIGNATURES = {
         [_P, C.POINTER(IcpParamsC), _P, _P, C.POINTER(PoseC), C.POINTER(GnStateC)],
     ),
     "a3d_range_image_download_depth16": (_ST, [_P, _P, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "a3d_backproject_proven": (_ST, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
 }
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")

@@ -10,6 +10,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include <algorithm>
+#include <cmath>
 #include <stdint.h>
 
 #define A3D_HD __host__ __device__ __forceinline__
@@ -243,6 +246,63 @@ __device__ __forceinline__ V3 backproject_px(uint32_t d, int row, int col, float
   }
   return p;
 }
+
+// backproject_px of a PROVEN image (backproject_proven below holds for its size and constants): no per-lane branch, no
+// range test, no ballot, no zero select.  The same bits as backproject_px for every d >= 1 at every pixel of the image:
+// - z = d scale, ax, ay are the same operations;
+// - the proof puts every numerator in div_num_ok range and fx, fy in div_den_ok range, so backproject_px's ballot is 0 on
+//   every wave and it takes div_by too;
+// - the proof leaves no non-zero numerator below 1e-20, so ax == 0 only when col - cx is an exact 0: +0 times z > 0 is
+//   +0 (never -0), and div_by(+0, div_prepare(f)) = +0 for f > 0, what the select returns.  The proof requires fx > 0
+//   (fy > 0) when a column (row) of the image equals cx (cy); for f < 0 div_by(+0) is -0 and the image fails the proof.
+// A lane with d = 0 yields (±0, ±0, +0) instead of (0, 0, 0); the callers leave it dead (image_icp.hip: slive, tvalid).
+__device__ __forceinline__ V3 backproject_px_proven(uint32_t d, int row, int col, float cx, float cy, float scale,
+                                                    const DivBy dfx, const DivBy dfy) {
+  V3 p;
+  p.z = (float)d * scale;
+  const float ax = ((float)col - cx) * p.z, ay = ((float)row - cy) * p.z;
+  p.x = div_by(ax, dfx), p.y = div_by(ay, dfy);
+  return p;
+}
+#endif  // __HIPCC__
+
+// Host: whether backproject_px_proven is backproject_px for every (d in [1, 65535], row in [0, h), col in [0, w)) of an
+// image back-projected with fx, fy, cx, cy and scale (the f32 operations of the kernels, in the same order):
+// z = RN(d scale) finite and > 0, focal_ok, div_num_ok(ax), div_num_ok(ay), and a zero numerator only where
+// div_by(+0) = +0.  Rounding is monotone, so the extremes decide: RN(k - c) does not decrease with k, its largest
+// magnitude is at k = 0 or n - 1, its smallest non-zero one next to c; the largest |ax| is RN(max |col - cx| RN(65535
+// scale)), the smallest non-zero one RN(min |col - cx| scale).
+inline bool backproject_proven(uint32_t w, uint32_t h, float fx, float fy, float cx, float cy, float scale) {
+  if (w == 0 || h == 0 || w > (1u << 24) || h > (1u << 24)) return false;  // (float)col exact
+  if (!(scale >= 1.17549435e-38f)) return false;                           // a positive normal f32 (NaN fails)
+  const float zmin = 1.0f * scale, zmax = 65535.0f * scale;
+  if (!(zmax <= 3.40282347e38f)) return false;
+  auto den_ok = [](float f) { return (std::fabs(f) > 1e-9f) & (std::fabs(f) < 1e9f); };  // div_den_ok
+  auto axis_ok = [&](uint32_t n, float f, float c) {
+    if (!den_ok(f) || !std::isfinite(c)) return false;
+    float amax = 0.0f, amin = INFINITY;
+    bool zero = false;
+    const double fl = std::floor(std::min(std::max((double)c, -2.0), (double)n + 1.0));
+    const double ks[6] = {0.0, (double)(n - 1), fl - 1.0, fl, fl + 1.0, fl + 2.0};
+    for (double kd : ks) {
+      const float k = (float)std::min(std::max(kd, 0.0), (double)(n - 1));
+      const float a = k - c;
+      if (a == 0.0f) {
+        if (k != c) return false;  // (a flushed difference: not the exact +0 the kernels see)
+        zero = true;
+      } else {
+        amax = std::max(amax, std::fabs(a)), amin = std::min(amin, std::fabs(a));
+      }
+    }
+    const float big = amax * zmax;
+    if (!(big < 1e9f)) return false;                            // div_num_ok: |a| < 1e9
+    if (amin != INFINITY && !(amin * zmin > 1e-20f)) return false;  // div_num_ok: |a| > 1e-20 or a == 0
+    return !zero || f > 0.0f;
+  };
+  return axis_ok(w, fx, cx) && axis_ok(h, fy, cy);
+}
+
+#if defined(__HIPCC__)
 
 
 // The per-pixel body of RangeImage::compute_normals (src/range_image/structure.rs:207-257) as the kernels evaluate it:

@@ -119,7 +119,6 @@ struct SrcPx {  // stage A: one source record
 struct BackProj {
   float fx, fy, cx, cy, scale;
   DivBy dfx, dfy;
-  bool focal_ok;
 };
 struct BackProj2 {
   BackProj src, tgt;
@@ -133,7 +132,6 @@ __device__ __forceinline__ BackProj make_backproj(const float (&k)[5]) {
   // (computed once per kernel in the VALU; readfirstlane parks the results in SGPRs, not in eight VGPRs)
   const DivBy dx = div_prepare(b.fx), dy = div_prepare(b.fy);
   b.dfx = DivBy{uniform_f(dx.negz), uniform_f(dx.y)}, b.dfy = DivBy{uniform_f(dy.negz), uniform_f(dy.y)};
-  b.focal_ok = div_den_ok(b.fx) & div_den_ok(b.fy);
   return b;
 }
 // DEPTH16 sides (the D16 template argument of the stages): D16_TGT the target point is rebuilt from the gathered u16 depth,
@@ -189,10 +187,9 @@ __device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, con
   ProjPx o;
   V3 sp = s.sp;
   bool slive = s.live;
-  if (D16 & D16_SRC) {  // the source point from its depth: the builder's own function (devmath.hpp), the same bits
-    sp = backproject_px(s.depth, (int)s.row, (int)s.col, bp.src.fx, bp.src.fy, bp.src.cx, bp.src.cy, bp.src.scale, bp.src.dfx,
-                        bp.src.dfy, bp.src.focal_ok);
-    slive = slive & (s.depth != 0u);
+  if (D16 & D16_SRC) {  // the source point from its depth: the builder's function in its proven form (devmath.hpp), the same bits
+    sp = backproject_px_proven(s.depth, (int)s.row, (int)s.col, bp.src.cx, bp.src.cy, bp.src.scale, bp.src.dfx, bp.src.dfy);
+    slive = slive & (s.depth != 0u);  // (a depth-0 pixel's (±0, ±0, +0) is never summed)
   }
   o.p = transform_vector(T, sp);
   // CameraIntrinsics::project (src/camera.rs:64-70): x * fx / z + cx
@@ -230,11 +227,10 @@ template <bool ZMASK = false, int D16 = 0>
 __device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, ProjPx& px, uint32_t mw,
                                          const BackProj2& bp = BackProj2{}) {
   bool tvalid;
-  if (D16 & D16_TGT) {  // the gathered depth lands here: the target point of the builder's own function, the same bits
+  if (D16 & D16_TGT) {  // the gathered depth lands here: the builder's function in its proven form, the same bits
     const uint32_t td = px.live ? px.tdepth : 0u;  // (a rejected lane's row / column are not a pixel's: no point)
-    px.tp = backproject_px(td, (int)px.trow, (int)px.tcol, bp.tgt.fx, bp.tgt.fy, bp.tgt.cx, bp.tgt.cy, bp.tgt.scale,
-                           bp.tgt.dfx, bp.tgt.dfy, bp.tgt.focal_ok);
-    tvalid = td != 0u;
+    px.tp = backproject_px_proven(td, (int)px.trow, (int)px.tcol, bp.tgt.cx, bp.tgt.cy, bp.tgt.scale, bp.tgt.dfx, bp.tgt.dfy);
+    tvalid = td != 0u;  // (td == 0: (±0, ±0, +0), dead below)
   } else {
     tvalid = ZMASK ? px.tp.z != 0.0f : px.tmask == 1;  // RangeImage::get_point: mask == 1 (structure.rs:176)
   }
@@ -522,6 +518,9 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
   // projected pixel k+1 in `nxt` and the source record of pixel k+2 in `s_new`
   auto step = [&](ProjPx& cur, uint8_t cur_i, ProjPx& nxt, uint8_t& nxt_i, const SrcPx& s_next, SrcPx& s_new, int k0) {
     s_new = pixel_source_at<ZMASK, D16>(d, base, ppt, k0 + 2);  // issue source record k+2
+    // (DEPTH16: otherwise the source depth load takes the register of the gathered depth of k, is issued after that
+    // depth is read, and the step starts with vmcnt(0) instead of keeping the source record in flight)
+    if (D16) __builtin_amdgcn_sched_barrier(0);
     const MapPx mp = stage_c<ZMASK, D16>(d, gt, cur, mw, bp);     // gathers(k) land; issue map cell(k)
     nxt = stage_b<ZMASK, D16>(d, T, s_next, twf, thf, bp);        // issue gathers(k+1)
     nxt_i = s_next.intensity;
@@ -543,7 +542,8 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
 // launch and runs the solve (head_advance), then takes the pixel pass with the resulting pose and stores its own
 // partial with plain stores.  State and partials alternate between two buffers (in / out).  A pair whose own tile
 // count is below the grid's (a smaller image in a mixed batch) leaves the surplus blocks to store zero partials.
-// DEPTH16: level 0 of a batch whose every image carries points_from_depth — the points are rebuilt from the u16 depth
+// DEPTH16: level 0 of a batch whose every image carries points_from_depth and passes backproject_proven (devmath.hpp) —
+// the points are rebuilt, in straight-line code (backproject_px_proven), from the u16 depth
 // planes (D16_SIDES: the target's, and the source's unless A3D_ICP_DEPTH16_SRC=0) instead of read.
 template <bool ZMASK, bool DEPTH16>
 __global__ void __launch_bounds__(256, 1)
@@ -1195,7 +1195,13 @@ a3d_status fill_desc(const a3d_device_image* target, const a3d_device_image* sou
   d->ppt = 2, d->pad = 0;
   d->src_w = source->width;
   d->src_inv_w = 1.0f / (float)std::max(1u, source->width);
-  const bool from_depth = target->points_from_depth && source->points_from_depth && target->depth16 && source->depth16;
+  // DEPTH16 rebuilds the points through backproject_px_proven: both images carry their depth planes, and the proof holds
+  // for each (devmath.hpp; an image that fails it is read as points)
+  auto proven = [](const a3d_device_image* im) {
+    return im->points_from_depth && im->depth16 &&
+           backproject_proven(im->width, im->height, im->bp_fx, im->bp_fy, im->bp_cx, im->bp_cy, im->depth_scale);
+  };
+  const bool from_depth = proven(target) && proven(source);
   if (from_depth) d->flags |= 2u;
   d->src_depth = from_depth ? source->depth16 : nullptr;
   d->tgt_depth = from_depth ? target->depth16 : nullptr;
@@ -1377,7 +1383,8 @@ a3d_status batch_commit_descs(a3d_multiscale_batch* b) {
   const char* zenv = A3D_DIAG_ENV("A3D_ICP_ZMASK");
   b->zmask = !(zenv && atoi(zenv) == 0);
   for (const LevelDesc& dsc : b->h_descs) b->zmask = b->zmask && (dsc.flags & 1u);
-  // DEPTH16, level 0 only, with the rule ZMASK uses: every pair's two images carry the flag (and the source's row and
+  // DEPTH16, level 0 only, with the rule ZMASK uses: every pair's two images carry the flag and pass the back-projection
+  // proof (fill_desc), no third kernel form and no runtime branch for the others (and the source's row and
   // column come out of an f32 quotient that is exact below 2^22 pixels); the diagnostics build's A3D_ICP_DEPTH16=0 reads
   // the points instead
   const char* denv = A3D_DIAG_ENV("A3D_ICP_DEPTH16");

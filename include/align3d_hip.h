@@ -305,6 +305,10 @@ a3d_status a3d_image_icp_accumulate_weighted(a3d_context* ctx, const a3d_icp_par
  * image.  Test hook. */
 a3d_status a3d_range_image_download_depth16(a3d_device_image* image, uint16_t* out_depth, float out_backproject[5],
                                             int32_t* out_points_from_depth);
+/* Whether the image ICP kernel may rebuild the points of a width x height depth image back-projected with {fx, fy, cx, cy,
+ * depth scale} in straight-line code: the host proof the alignment applies to every level-0 image before it takes its
+ * depth plane (1 = proven, 0 = its points are read).  No device work.  Test hook. */
+a3d_status a3d_backproject_proven(uint32_t width, uint32_t height, const float backproject[5], int32_t* out_proven);
 #endif /* A3D_DIAGNOSTICS */
 
 /* ---- instrumentation that SHIPS in the product library -------------------------------------------------------
