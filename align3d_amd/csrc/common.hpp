@@ -94,9 +94,10 @@ struct a3d_context {
   hipEvent_t kd_ev[2] = {nullptr, nullptr};  // around a kd-tree build's launches (a3d_kdtree_build_ms): made once
   int num_cus = 0;
   // Grow-only scratch regions for per-call temporaries (all work on a context is ordered on its one stream,
-  // so successive calls may reuse them): [0] frame builder temporaries, [1] bilateral grids, [2] kd-tree build.
-  void* scratch[3] = {nullptr, nullptr, nullptr};
-  size_t scratch_size[3] = {0, 0, 0};
+  // so successive calls may reuse them): [0] frame builder temporaries, [1] bilateral grids, [2] kd-tree build,
+  // [3] range image -> point cloud conversion (its per-image table and tile counts, pointcloud.hip).
+  void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t scratch_size[4] = {0, 0, 0, 0};
   // Device blocks handed back by freed kd-trees / Icp objects (ctx_block_release), kept for the next one of about the
   // same size (ctx_block_alloc): Icp::new per frame then costs no hipMalloc / hipFree (each a device-wide
   // synchronisation, ~0.1 ms).  Reuse is stream-ordered: everything on a context runs on its one stream.

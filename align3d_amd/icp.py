@@ -291,8 +291,57 @@ class DevicePointCloud:
         self.d_points = ctx.to_device(cloud.points)
         self.d_normals = None if cloud.normals is None else ctx.to_device(cloud.normals)
 
+    @staticmethod
+    def from_range_image(device_image):
+        """PointCloud::from(&RangeImage) (src/range_image/structure.rs:375-406) without leaving the device: the kept
+        pixels (mask != 0) of a resident image, row-major, bit for bit (a3d_range_image_to_point_cloud).  The cloud has
+        normals iff the image has them; it owns its buffers (`free()`)."""
+        return DevicePointCloud.from_range_images([device_image])[0]
+
+    @staticmethod
+    def from_range_images(images):
+        """from_range_image for resident images of one context in one pass (a3d_range_image_to_point_clouds)."""
+        images = list(images)
+        if not images:
+            return []
+        ctx = images[0].ctx
+        n = len(images)
+        clouds = []
+        try:
+            for im in images:
+                h, w = im.shape
+                c = DevicePointCloud.__new__(DevicePointCloud)
+                c.ctx, c.n = ctx, 0
+                c.d_points, c.d_normals = None, None
+                clouds.append(c)
+                c.d_points = ctx.malloc(w * h * 12)
+                c.d_normals = ctx.malloc(w * h * 12) if im.has_normals() else None
+            caps = (C.c_uint64 * n)(*[im.shape[0] * im.shape[1] for im in images])
+            lens = (C.c_uint64 * n)()
+            _abi.check(
+                ctx.lib.a3d_range_image_to_point_clouds(_handle_array(images), n,
+                                                        (C.c_void_p * n)(*[c.d_points for c in clouds]),
+                                                        (C.c_void_p * n)(*[c.d_normals for c in clouds]), caps, lens),
+                "a3d_range_image_to_point_clouds",
+            )
+        except BaseException:
+            for c in clouds:
+                c.free()
+            raise
+        for c, k in zip(clouds, lens):
+            c.n = int(k)
+        return clouds
+
     def len(self):
         return self.n
+
+    def download(self):
+        """(points [len,3], normals [len,3] or None) read back to the host."""
+        pts = self.ctx.to_host(self.d_points, np.empty((self.n, 3), np.float32)) if self.n else np.empty((0, 3), np.float32)
+        if self.d_normals is None:
+            return pts, None
+        nrm = self.ctx.to_host(self.d_normals, np.empty((self.n, 3), np.float32)) if self.n else np.empty((0, 3), np.float32)
+        return pts, nrm
 
     def view(self):
         v = _abi.PointCloudViewC()

@@ -97,6 +97,12 @@ class DeviceRangeImage:
         _abi.check(self.ctx.lib.a3d_range_image_compute_normals(self.handle))
         return self
 
+    def has_normals(self):
+        """Whether the resident image carries normals (RangeImage::normals is Some)."""
+        out = C.c_int32()
+        _abi.check(self.ctx.lib.a3d_range_image_has_normals(self.handle, C.byref(out)))
+        return bool(out.value)
+
     def download_normals(self):
         out = np.empty(self.shape + (3,), np.float32)
         _abi.check(self.ctx.lib.a3d_range_image_download_normals(self.handle, _abi.ptr(out)))

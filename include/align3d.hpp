@@ -361,6 +361,49 @@ class R3dTree {
   a3d_kdtree* t_ = nullptr;
 };
 
+/// PointCloud::from(&RangeImage) (src/range_image/structure.rs:375-406) kept in HBM: the pixels with mask != 0 of a
+/// resident image, row-major, points and normals bit for bit (a3d_range_image_to_point_cloud).  Owns its two buffers
+/// (width * height capacity each); view() feeds Icp::from_device / align_device and R3dTree::from_device.
+class DevicePointCloud {
+ public:
+  DevicePointCloud(const Context& ctx, const RangeImage& image) : ctx_(ctx.raw()) {
+    const uint64_t capacity = image.width() * image.height();
+    int32_t has_normals = 0;
+    check(a3d_range_image_has_normals(image.raw(), &has_normals));
+    void *p = nullptr, *q = nullptr;
+    check(a3d_malloc(ctx_, capacity * 12, &p));
+    points_ = static_cast<float*>(p);
+    if (has_normals) {
+      a3d_status s = a3d_malloc(ctx_, capacity * 12, &q);
+      if (s != A3D_OK) release(), check(s);
+      normals_ = static_cast<float*>(q);
+    }
+    a3d_status s = a3d_range_image_to_point_cloud(image.raw(), points_, normals_, capacity, &len_);
+    if (s != A3D_OK) release(), check(s);
+  }
+  DevicePointCloud(DevicePointCloud&& o) noexcept : ctx_(o.ctx_), points_(o.points_), normals_(o.normals_), len_(o.len_) {
+    o.points_ = o.normals_ = nullptr, o.len_ = 0;
+  }
+  ~DevicePointCloud() { release(); }
+  DevicePointCloud(const DevicePointCloud&) = delete;
+  DevicePointCloud& operator=(const DevicePointCloud&) = delete;
+  uint64_t len() const { return len_; }
+  const float* d_points() const { return points_; }
+  const float* d_normals() const { return normals_; }  // nullptr: the image had no normals
+  a3d_point_cloud_view view() const { return a3d_point_cloud_view{points_, normals_, len_}; }
+
+ private:
+  void release() {
+    if (points_) a3d_free(ctx_, points_);
+    if (normals_) a3d_free(ctx_, normals_);
+    points_ = normals_ = nullptr;
+  }
+  a3d_context* ctx_ = nullptr;
+  float* points_ = nullptr;
+  float* normals_ = nullptr;
+  uint64_t len_ = 0;
+};
+
 /// Icp::new(params, &target_cloud) ; align(&source_cloud)
 class Icp {
  public:

@@ -265,6 +265,23 @@ a3d_status a3d_range_image_download(a3d_device_image* image, float* points, uint
  * one launch per frame. */
 a3d_status a3d_range_image_compute_normals_batch(a3d_device_image* const* images, uint64_t n);
 
+/* PointCloud::from(&RangeImage) (src/range_image/structure.rs:375-406): mask != 0, row-major.  d_points / d_normals:
+ * DEVICE [capacity][3] f32 on the image's GPU (d_normals may be NULL; A3D_MISSING_FIELD if it is not and the image has
+ * no normals).  Points and normals are copied bit for bit.  Host-synchronous; *out_len = number of points written.
+ * capacity >= width * height is always enough; a smaller one that the cloud does not fit gives A3D_INVALID_PARAMETER,
+ * *out_len = the point count, and nothing written.  The result is an a3d_point_cloud_view of device pointers for
+ * a3d_pcl_icp_new_device / a3d_pcl_icp_align_device / a3d_kdtree_new_device. */
+a3d_status a3d_range_image_to_point_cloud(const a3d_device_image* image, float* d_points, float* d_normals,
+                                          uint64_t capacity, uint64_t* out_len);
+/* The same for n images of one context in one pass (structure.rs:375-406 for each): per-image output pointers and
+ * capacities (d_normals may be NULL, or hold NULL entries), lengths into out_lens[n].  If any image does not fit its
+ * capacity, A3D_INVALID_PARAMETER and nothing is written for any image (out_lens still holds every count).  n == 0:
+ * A3D_OK, nothing touched. */
+a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images, uint64_t n, float* const* d_points,
+                                           float* const* d_normals, const uint64_t* capacities, uint64_t* out_lens);
+/* Whether the resident image carries normals (RangeImage::normals is Some): 1 or 0.  No device work. */
+a3d_status a3d_range_image_has_normals(const a3d_device_image* image, int32_t* out_has_normals);
+
 /* RangeImage::compute_normals, host in / host out convenience form. */
 a3d_status a3d_compute_normals(a3d_context* ctx, const float* points, const uint8_t* mask,
                                uint64_t width, uint64_t height, float* out_normals);

@@ -1,0 +1,215 @@
+"""PointCloud::from(&RangeImage) (src/range_image/structure.rs:375-406) on the device: DevicePointCloud.from_range_image[s]
+(a3d_range_image_to_point_cloud[s]) against the host path PointCloud.from_range_image, bit for bit."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from align3d_amd import (A3dError, BilateralFilter, CameraIntrinsics, DevicePointCloud, Icp, IcpParams, PointCloud,
+                         R3dTree, RangeImage, RangeImageBuilder, SlamTbDataset, _abi)
+from align3d_amd.range_image import DeviceRangeImage
+from data_util import SlamTbSample
+from gpu_util import oracle_frame, to_range_image
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _assert_same(dc, pc):
+    pts, nrm = dc.download()
+    assert dc.len() == pc.len()
+    assert np.array_equal(_bits(pts), _bits(pc.points))
+    if pc.normals is None:
+        assert nrm is None and dc.d_normals is None
+    else:
+        assert nrm is not None and np.array_equal(_bits(nrm), _bits(pc.normals))
+
+
+def _upload(ctx, host):
+    """A fresh resident copy (never the builder's image a download() remembers)."""
+    return DeviceRangeImage(ctx, host)
+
+
+def _synthetic(seed, h, w, mask_values=(0, 1, 2, 255), normals=True):
+    rng = np.random.default_rng(seed)
+    # raw random bits: NaNs with payloads, infinities, -0.0 and denormals all occur among the kept points
+    pts = rng.integers(0, 2**32, size=(h, w, 3), dtype=np.uint64).astype(np.uint32).view(np.float32)
+    special = np.asarray([np.nan, -0.0, np.inf, -np.inf, 0.0, 1e-45], np.float32)
+    pts.reshape(-1)[:min(6, pts.size)] = special[:min(6, pts.size)]
+    nrm = rng.integers(0, 2**32, size=(h, w, 3), dtype=np.uint64).astype(np.uint32).view(np.float32) if normals else None
+    mask = rng.choice(np.asarray(mask_values, np.uint8), size=(h, w))
+    mask.reshape(-1)[0] = mask_values[-1]
+    return RangeImage(pts, mask, CameraIntrinsics(500.0, 500.0, w / 2, h / 2, w, h), normals=nrm)
+
+
+def _sample1_device_frame(ctx, i, levels=1, bilateral=False):
+    s = SlamTbSample("sample1")
+    b = RangeImageBuilder(ctx).pyramid_levels(levels)
+    if bilateral:
+        b = b.with_bilateral_filter(BilateralFilter.default())
+    return b.build(CameraIntrinsics(*s.intrinsics(i), 640, 480), *s.load(i), s.depth_scale(i))
+
+
+def test_reference_kat_sample1_frame0(ctx):
+    # should_convert_into_pointcloud (structure.rs:478-485): one level, no bilateral filter -> 270 213 points
+    lv = _sample1_device_frame(ctx, 0)[0]
+    dc = DevicePointCloud.from_range_image(lv)
+    assert dc.len() == 270213
+    _assert_same(dc, PointCloud.from_range_image(lv.download()))
+    dc.free()
+    lv.free()
+
+
+def test_bit_identity_with_host_path_on_uploaded_images(ctx):
+    cases = [to_range_image(oracle_frame("sample1", 0)), to_range_image(oracle_frame("sample1", 5))]
+    assert cases[0].normals is not None
+    for k, (h, w) in enumerate([(1, 1), (1, 63), (3, 65), (90, 150), (481, 641), (720, 1280)]):
+        cases.append(_synthetic(k, h, w))
+    cases.append(_synthetic(10, 37, 101, mask_values=(0,)))    # all zero
+    cases.append(_synthetic(11, 37, 101, mask_values=(1,)))    # all one
+    cases.append(_synthetic(12, 64, 64, mask_values=(2, 255)))  # every pixel kept, none through mask == 1
+    for host in cases:
+        dev = _upload(ctx, host)
+        dc = DevicePointCloud.from_range_image(dev)
+        _assert_same(dc, PointCloud.from_range_image(host))
+        dc.free()
+        dev.free()
+    # without normals: a cloud without normals; asking for them is A3D_MISSING_FIELD
+    host = _synthetic(13, 45, 77, normals=False)
+    dev = _upload(ctx, host)
+    assert not dev.has_normals()
+    dc = DevicePointCloud.from_range_image(dev)
+    assert dc.d_normals is None
+    _assert_same(dc, PointCloud.from_range_image(host))
+    n = C.c_uint64(12345)
+    st = ctx.lib.a3d_range_image_to_point_cloud(dev.handle, dc.d_points, dc.d_points, 45 * 77, C.byref(n))
+    assert st == _abi.A3D_MISSING_FIELD and n.value == 12345
+    dc.free()
+    dev.free()
+
+
+@pytest.mark.parametrize("bilateral", [False, True])
+def test_builder_pyramid_levels(ctx, bilateral):
+    for frame in (0, 5):
+        pyr = _sample1_device_frame(ctx, frame, levels=3, bilateral=bilateral)
+        for lv in pyr:  # (level 0 carries the u16 depth plane: its points are rebuilt from it)
+            host = lv.download()
+            dc = DevicePointCloud.from_range_image(lv)
+            _assert_same(dc, PointCloud.from_range_image(host))
+            dc.free()
+        host0 = pyr[0].download()
+        up = _upload(ctx, host0)  # level 0 uploaded back: the plain path, the same bits
+        a, b = DevicePointCloud.from_range_image(pyr[0]), DevicePointCloud.from_range_image(up)
+        (pa, na), (pb, nb) = a.download(), b.download()
+        assert a.len() == b.len() > 0
+        assert np.array_equal(_bits(pa), _bits(pb)) and np.array_equal(_bits(na), _bits(nb))
+        for x in (a, b, up, *pyr):
+            x.free()
+
+
+def test_batch_equals_single_calls_and_capacity_check(ctx):
+    rng = np.random.default_rng(7)
+    hosts = [_synthetic(100 + k, int(rng.integers(1, 200)), int(rng.integers(1, 300)), normals=bool(k % 3))
+             for k in range(38)]
+    hosts += [to_range_image(oracle_frame("sample1", 0)), _synthetic(200, 480, 640, mask_values=(0,))]
+    devs = [_upload(ctx, h) for h in hosts]
+    batch = DevicePointCloud.from_range_images(devs)
+    assert len(batch) == len(devs)
+    for d, h, c in zip(devs, hosts, batch):
+        single = DevicePointCloud.from_range_image(d)
+        ref = PointCloud.from_range_image(h)
+        assert c.len() == single.len() == ref.len()
+        _assert_same(c, ref)
+        _assert_same(single, ref)
+        single.free()
+    # out_lens through the raw call
+    n = len(devs)
+    caps = (C.c_uint64 * n)(*[h.len() for h in hosts])
+    lens = (C.c_uint64 * n)()
+    st = ctx.lib.a3d_range_image_to_point_clouds((C.c_void_p * n)(*[d.handle for d in devs]), n,
+                                                 (C.c_void_p * n)(*[c.d_points for c in batch]), None, caps, lens)
+    assert st == _abi.A3D_OK
+    assert list(lens) == [h.valid_points_count() for h in hosts]
+    # too small a capacity: status 1, the output buffer left as it was
+    host = to_range_image(oracle_frame("sample1", 0))
+    dev = _upload(ctx, host)
+    count = host.valid_points_count()
+    sentinel = np.full((host.len(), 3), np.float32(-7.25))
+    d_out = ctx.to_device(sentinel)
+    n1 = C.c_uint64(0)
+    st = ctx.lib.a3d_range_image_to_point_cloud(dev.handle, d_out, None, count - 1, C.byref(n1))
+    assert st == _abi.A3D_INVALID_PARAMETER and n1.value == count
+    assert np.array_equal(ctx.to_host(d_out, np.empty_like(sentinel)), sentinel)
+    # ... in a batch: nothing written for any image
+    small = _upload(ctx, _synthetic(300, 20, 30))
+    d_out2 = ctx.to_device(sentinel[:600])
+    lens2 = (C.c_uint64 * 2)()
+    st = ctx.lib.a3d_range_image_to_point_clouds((C.c_void_p * 2)(small.handle, dev.handle), 2,
+                                                 (C.c_void_p * 2)(d_out2, d_out), None, (C.c_uint64 * 2)(600, count - 1),
+                                                 lens2)
+    assert st == _abi.A3D_INVALID_PARAMETER and lens2[1] == count
+    assert np.array_equal(ctx.to_host(d_out, np.empty_like(sentinel)), sentinel)
+    assert np.array_equal(ctx.to_host(d_out2, np.empty_like(sentinel[:600])), sentinel[:600])
+    # exactly enough is enough
+    st = ctx.lib.a3d_range_image_to_point_cloud(dev.handle, d_out, None, count, C.byref(n1))
+    assert st == _abi.A3D_OK and n1.value == count
+    ctx.free(d_out), ctx.free(d_out2)
+    for x in (*batch, *devs, dev, small):
+        x.free()
+
+
+def test_end_to_end_bench_icp_shape(ctx):
+    # benches/bench_icp.rs:9-39: sample1 frames 0 (target) and 5 (source), IcpParams { max_iterations: 10, .. }
+    ds = SlamTbDataset.load(os.path.join(ROOT, "tests", "golden", "rgbd", "sample1"))
+    levels = []
+    for i in (0, 5):
+        cam, depth, rgb, depth_scale = ds.get(i)
+        levels.append(RangeImageBuilder(ctx).pyramid_levels(1).with_intensity(False).build(cam, depth, rgb, depth_scale)[0])
+    ht, hs = (PointCloud.from_range_image(lv.download(intensity=False)) for lv in levels)
+    dt, dsrc = DevicePointCloud.from_range_images(levels)
+    prm = IcpParams(max_iterations=10)
+    icp_h = Icp.new(ctx, prm, ht)
+    T_host = icp_h.align(hs)
+    icp_d = Icp.new(ctx, prm, dt)
+    T_dev = icp_d.align(dsrc)
+    a, b = T_host.to_c(), T_dev.to_c()
+    assert np.array_equal(_bits(list(a.t) + list(a.q)), _bits(list(b.t) + list(b.q)))
+    th, td = R3dTree.new(ctx, ht.points), R3dTree.new_device(ctx, dt.d_points, dt.len())
+    (sh, lh), (sd, ld) = th.download(), td.download()
+    assert np.array_equal(sh, sd) and np.array_equal(lh, ld)
+    for x in (icp_h, icp_d, th, td, dt, dsrc, *levels):
+        x.free()
+
+
+def _status(fn):
+    try:
+        fn()
+        return _abi.A3D_OK
+    except A3dError as e:
+        return e.status
+
+
+def test_empty_cloud(ctx):
+    host = _synthetic(400, 48, 64, mask_values=(0,))
+    dev = _upload(ctx, host)
+    dc = DevicePointCloud.from_range_image(dev)
+    assert dc.len() == 0
+    hc = PointCloud.from_range_image(host)
+    assert hc.len() == 0
+    src = PointCloud.from_range_image(to_range_image(oracle_frame("sample1", 5)))
+    prm = IcpParams(max_iterations=3)
+    st_host = _status(lambda: Icp.new(ctx, prm, hc).align(src))
+    st_dev = _status(lambda: Icp.new(ctx, prm, dc).align(src))
+    assert st_dev == st_host
+    st_host = _status(lambda: Icp.new(ctx, prm, src).align(hc))
+    d_src = DevicePointCloud(ctx, src)
+    st_dev = _status(lambda: Icp.new(ctx, prm, d_src).align(dc))
+    assert st_dev == st_host
+    for x in (dc, d_src, dev):
+        x.free()
