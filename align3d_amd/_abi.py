@@ -168,6 +168,9 @@ SIGNATURES = {
     "a3d_range_image_to_point_cloud": (_ST, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "a3d_range_image_to_point_clouds": (_ST, [_PP, C.c_uint64, _PP, _PP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "a3d_range_image_has_normals": (_ST, [_P, C.POINTER(C.c_int32)]),
+    "a3d_range_image_set_colors": (_ST, [_P, _P]),
+    "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
+    "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),
     "a3d_image_icp_align": (_ST, [_P, C.POINTER(IcpParamsC), _P, _P, C.POINTER(PoseC), C.POINTER(PoseC)]),
     "a3d_image_icp_accumulate": (
         _ST,

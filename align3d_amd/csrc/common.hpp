@@ -95,9 +95,10 @@ struct a3d_context {
   int num_cus = 0;
   // Grow-only scratch regions for per-call temporaries (all work on a context is ordered on its one stream,
   // so successive calls may reuse them): [0] frame builder temporaries, [1] bilateral grids, [2] kd-tree build,
-  // [3] range image -> point cloud conversion (its per-image table and tile counts, pointcloud.hip).
-  void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t scratch_size[4] = {0, 0, 0, 0};
+  // [3] range image -> point cloud conversion (its per-image table and tile counts, pointcloud.hip), [4] the per-image,
+  // per-level pointer table of a3d_range_image_pyramids / a3d_range_image_compute_intensity (pyramid.hip).
+  void* scratch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t scratch_size[5] = {0, 0, 0, 0, 0};
   // Device blocks handed back by freed kd-trees / Icp objects (ctx_block_release), kept for the next one of about the
   // same size (ctx_block_alloc): Icp::new per frame then costs no hipMalloc / hipFree (each a device-wide
   // synchronisation, ~0.1 ms).  Reuse is stream-ordered: everything on a context runs on its one stream.
@@ -296,6 +297,8 @@ namespace a3d {
 // recycled before the fence has passed.  Individually allocated images are released with hipFree, which waits for
 // the device by itself.
 void attach_fence(const a3d_device_image* im, const std::shared_ptr<UseFence>& fence);
+// Enqueue-only work of a context on images that live in arenas: one lazily recorded fence per call (image.hip).
+void fence_self_work(a3d_context* ctx, a3d_device_image* const* images, uint64_t n);
 }  // namespace a3d
 
 // One RangeImage in HBM, in the reference's own standard layout (DESIGN.md "Data layout in HBM").
@@ -323,4 +326,7 @@ struct a3d_device_image {
   bool points_from_depth = false;
   bool own_normals = false;  // `normals` is its own hipMalloc although the image lives in an arena (uploaded without
                              // normals, a3d_range_image_compute_normals called later)
+  // the same for colours (a3d_range_image_set_colors) and for intensities / their map (a3d_range_image_compute_intensity,
+  // a3d_range_image_pyramids on an image that came without them)
+  bool own_colors = false, own_intensities = false, own_imap = false;
 };

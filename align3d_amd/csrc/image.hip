@@ -110,6 +110,23 @@ a3d_status launch_compute_normals_batch(a3d_context* ctx, const NormalsBatch& ba
   return A3D_OK;
 }
 
+template <typename T>
+a3d_status upload_array(a3d_context* ctx, const T* host, size_t count, T** dev) {
+  A3D_HIP_TRY(hipMalloc((void**)dev, count * sizeof(T)));
+  A3D_HIP_TRY(hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  return A3D_OK;
+}
+
+a3d_status launch_compute_normals(a3d_context* ctx, const float* points, const uint8_t* mask, float* normals,
+                                  uint32_t w, uint32_t h) {
+  NormalsBatch b{};
+  b.points[0] = points, b.mask[0] = mask, b.normals[0] = normals;
+  return launch_compute_normals_batch(ctx, b, 1, w, h);
+}
+
+}  // namespace
+
+namespace a3d {
 // Enqueue-only work of a context on images that live in arenas: ONE (lazily recorded) fence per call, shared by the
 // arenas of all the images the call touched; it replaces the fence an earlier call left on an arena (a later event on
 // the same stream covers the earlier work), so repeated calls do not pile fences up.
@@ -131,23 +148,6 @@ void fence_self_work(a3d_context* ctx, a3d_device_image* const* images, uint64_t
   }
 }
 
-template <typename T>
-a3d_status upload_array(a3d_context* ctx, const T* host, size_t count, T** dev) {
-  A3D_HIP_TRY(hipMalloc((void**)dev, count * sizeof(T)));
-  A3D_HIP_TRY(hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  return A3D_OK;
-}
-
-a3d_status launch_compute_normals(a3d_context* ctx, const float* points, const uint8_t* mask, float* normals,
-                                  uint32_t w, uint32_t h) {
-  NormalsBatch b{};
-  b.points[0] = points, b.mask[0] = mask, b.normals[0] = normals;
-  return launch_compute_normals_batch(ctx, b, 1, w, h);
-}
-
-}  // namespace
-
-namespace a3d {
 a3d_status compute_normals_device(a3d_context* ctx, const float* d_points, const uint8_t* d_mask, float* d_normals,
                                   uint32_t w, uint32_t h) {
   return launch_compute_normals(ctx, d_points, d_mask, d_normals, w, h);
@@ -274,6 +274,9 @@ a3d_status a3d_range_image_free(a3d_device_image* im) {
   // building the next frames on this context therefore does not stall the thread that frees the previous ones.
   if (im->arena) {  // arrays live in a shared arena: release it with its last user
     if (im->own_normals) hipFree(im->normals);  // (waits for the device by itself)
+    if (im->own_colors) hipFree(im->colors);
+    if (im->own_intensities) hipFree(im->intensities);
+    if (im->own_imap) hipFree(im->imap);
     if (--im->arena->refs == 0) {
       ctx_arena_release(im->ctx, im->arena);
       delete im->arena;

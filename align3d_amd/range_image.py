@@ -75,6 +75,16 @@ class RangeImage:
             self._device = DeviceRangeImage(ctx, self)
         return self._device
 
+    def pyramid(self, ctx, levels, sigma=1.0, with_intensity=True):
+        """RangeImage::pyramid(levels, sigma) (structure.rs:342-351) on the device: uploads this image (with its colours,
+        when it has them) and builds the coarser levels there (a3d_range_image_pyramids).  Returns `levels`
+        DeviceRangeImages, index 0 = this image's device copy; with_intensity adds intensities and maps on every level, as
+        RangeImageBuilder does.  The result can go straight to MultiscaleAlign."""
+        dev = DeviceRangeImage(ctx, self)
+        if self.colors is not None:
+            dev.set_colors(self.colors)
+        return dev.pyramid(levels, sigma, with_intensity)
+
 
 class DeviceRangeImage:
     """a3d_device_image: one RangeImage resident in HBM."""
@@ -96,6 +106,23 @@ class DeviceRangeImage:
     def compute_normals(self):
         _abi.check(self.ctx.lib.a3d_range_image_compute_normals(self.handle))
         return self
+
+    def set_colors(self, rgb):
+        """RangeImage::colors = Some(rgb): [h][w][3] u8 to the resident image (a3d_range_image_set_colors)."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        if rgb.shape != self.shape + (3,):
+            raise _abi.InvalidParameter(f"colours must be [h][w][3] u8 of the image's size {self.shape} (got {rgb.shape})")
+        _abi.check(self.ctx.lib.a3d_range_image_set_colors(self.handle, _abi.ptr(rgb)), "a3d_range_image_set_colors")
+        return self
+
+    def compute_intensity(self):
+        """RangeImage::compute_intensity + compute_intensity_map in place (enqueue-only)."""
+        compute_intensity_batch([self])
+        return self
+
+    def pyramid(self, levels, sigma=1.0, with_intensity=True):
+        """RangeImage::pyramid(levels, sigma) of this resident image: [self, *coarser] (see `pyramids`)."""
+        return pyramids([self], levels, sigma, with_intensity)[0]
 
     def has_normals(self):
         """Whether the resident image carries normals (RangeImage::normals is Some)."""
@@ -147,6 +174,30 @@ def compute_normals_batch(images):
     arr = (C.c_void_p * len(images))(*[im.handle for im in images])
     _abi.check(images[0].ctx.lib.a3d_range_image_compute_normals_batch(arr, len(images)),
                "a3d_range_image_compute_normals_batch")
+
+
+def compute_intensity_batch(images):
+    """RangeImage::compute_intensity + compute_intensity_map on a list of resident images of one context (any sizes; one
+    launch, enqueue-only: a3d_range_image_compute_intensity)."""
+    if not images:
+        return
+    arr = (C.c_void_p * len(images))(*[im.handle for im in images])
+    _abi.check(images[0].ctx.lib.a3d_range_image_compute_intensity(arr, len(images)), "a3d_range_image_compute_intensity")
+
+
+def pyramids(images, levels, sigma=1.0, with_intensity=True):
+    """RangeImage::pyramid(levels, sigma) (structure.rs:342-351) for resident images of one context and one size, on the
+    device in one launch per stage (a3d_range_image_pyramids).  Returns one list per image: [image, level 1, ...];
+    level 0 is the image itself (with_intensity computes its intensities and map in place), the coarser levels are new."""
+    if not images:
+        return []
+    n, L = len(images), int(levels)
+    arr = (C.c_void_p * n)(*[im.handle for im in images])
+    out = (C.c_void_p * max(1, n * max(0, L - 1)))()
+    _abi.check(images[0].ctx.lib.a3d_range_image_pyramids(arr, n, L, float(sigma), 1 if with_intensity else 0, out),
+               "a3d_range_image_pyramids")
+    return [[im] + [DeviceRangeImage(im.ctx, handle=C.c_void_p(out[i * (L - 1) + k])) for k in range(L - 1)]
+            for i, im in enumerate(images)]
 
 
 def upload_pyramid(ctx, host_images):

@@ -171,6 +171,27 @@ class RangeImage {
     return *this;
   }
   void download_normals(float* out_hw3) { check(a3d_range_image_download_normals(img_, out_hw3)); }
+  /// RangeImage::colors = Some(rgb): host [h][w][3] u8 (a3d_range_image_set_colors)
+  RangeImage& set_colors(const uint8_t* rgb_hw3) {
+    check(a3d_range_image_set_colors(img_, rgb_hw3));
+    return *this;
+  }
+  /// RangeImage::compute_intensity + compute_intensity_map in place (enqueue-only)
+  RangeImage& compute_intensity() {
+    check(a3d_range_image_compute_intensity(&img_, 1));
+    return *this;
+  }
+  /// RangeImage::pyramid(levels, sigma) on the device (a3d_range_image_pyramids): the levels - 1 coarser levels, each an
+  /// owning RangeImage; this image is level 0 (with_intensity also computes its intensities and map in place).
+  std::vector<RangeImage> pyramid(uint64_t levels, float sigma = 1.0f, bool with_intensity = true) {
+    std::vector<a3d_device_image*> out(levels > 1 ? levels - 1 : 0);
+    const a3d_device_image* level0 = img_;
+    check(a3d_range_image_pyramids(&level0, 1, levels, sigma, with_intensity ? 1u : 0u, out.data()));
+    std::vector<RangeImage> coarser;
+    coarser.reserve(out.size());
+    for (a3d_device_image* h : out) coarser.emplace_back(h);
+    return coarser;
+  }
   const a3d_device_image* raw() const { return img_; }
 
  private:

@@ -282,6 +282,27 @@ a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images
 /* Whether the resident image carries normals (RangeImage::normals is Some): 1 or 0.  No device work. */
 a3d_status a3d_range_image_has_normals(const a3d_device_image* image, int32_t* out_has_normals);
 
+/* RangeImage::colors = Some(..) (src/range_image/structure.rs:20-36): host rgb [h][w][3] u8 -> the resident image's
+ * colours, in an allocation of their own that is freed with the image.  Host-synchronous.  An image that already has
+ * colours (every builder image) gives A3D_INVALID_PARAMETER. */
+a3d_status a3d_range_image_set_colors(a3d_device_image* image, const uint8_t* rgb);
+/* RangeImage::compute_intensity + compute_intensity_map (src/range_image/structure.rs:266-297) in place on n resident
+ * images of one context; their sizes may differ (one launch for the batch).  Enqueue-only like
+ * a3d_range_image_compute_normals_batch.  An image without colours gives A3D_MISSING_FIELD (nothing is enqueued for any
+ * image); an image without intensities or a map gets them in allocations of their own.  n == 0: A3D_OK. */
+a3d_status a3d_range_image_compute_intensity(a3d_device_image* const* images, uint64_t n);
+/* RangeImage::pyramid(levels, sigma) (src/range_image/structure.rs:309-351) for n resident images of one context and one
+ * size.  out_levels[n][levels - 1] receives NEW handles for levels 1 .. levels - 1, image-major (level 0 is the caller's
+ * image and is not copied); the coarser levels of one image share one pooled arena.  Points and mask are picked from the
+ * source pixels with mask == 1, normals only if level 0 has normals, colours blurred and halved only if it has colours,
+ * intrinsics scaled by 0.5 per level.  with_intensity != 0: intensities and map on EVERY level, level 0 in place (the
+ * builder's semantics, builder.rs:83-88); A3D_MISSING_FIELD without colours.  The builder's limits: levels in
+ * 1 .. 16, a coarsest side of at least 2, a finite sigma, sigma <= 3 when levels > 1; sigma <= 0 means 1.  Mixed
+ * contexts or sizes and null handles: A3D_INVALID_PARAMETER.  All or nothing: on failure no handle is returned and
+ * level 0 is untouched.  Host-synchronous: every pyramid is complete on return.  n == 0: A3D_OK, nothing touched. */
+a3d_status a3d_range_image_pyramids(const a3d_device_image* const* level0, uint64_t n, uint64_t levels, float blur_sigma,
+                                    uint32_t with_intensity, a3d_device_image** out_levels);
+
 /* RangeImage::compute_normals, host in / host out convenience form. */
 a3d_status a3d_compute_normals(a3d_context* ctx, const float* points, const uint8_t* mask,
                                uint64_t width, uint64_t height, float* out_normals);
