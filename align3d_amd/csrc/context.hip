@@ -575,4 +575,12 @@ void a3d_bilateral_default_sigmas(double* ss, double* sc) {
   if (sc) *sc = 29.9999880000072;
 }
 
+#ifdef A3D_DIAGNOSTICS
+a3d_status a3d_acos_gate_threshold(float thr, int32_t strict, float* out) {
+  A3D_REQUIRE(out, A3D_INVALID_PARAMETER, "null argument");
+  *out = a3d::acos_gate_threshold(thr, strict != 0);
+  return A3D_OK;
+}
+#endif
+
 }  // extern "C"

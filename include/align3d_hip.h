@@ -347,6 +347,10 @@ a3d_status a3d_range_image_download_depth16(a3d_device_image* image, uint16_t* o
  * depth scale} in straight-line code: the host proof the alignment applies to every level-0 image before it takes its
  * depth plane (1 = proven, 0 = its points are read).  No device work.  Test hook. */
 a3d_status a3d_backproject_proven(uint32_t width, uint32_t height, const float backproject[5], int32_t* out_proven);
+/* The dot-product cut that stands in for the reference's normal-angle gate: a correspondence whose dot product d
+ * satisfies -1 <= d <= *out is rejected, which is |acos(d)| > thr when `strict` (point-cloud ICP) and |acos(d)| >= thr
+ * otherwise (image ICP).  The host bisection the ICP launches use.  No device work.  Test hook. */
+a3d_status a3d_acos_gate_threshold(float thr, int32_t strict, float* out);
 #endif /* A3D_DIAGNOSTICS */
 
 /* ---- instrumentation that SHIPS in the product library -------------------------------------------------------

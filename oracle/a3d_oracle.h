@@ -76,6 +76,9 @@ a3d_status orc_pcl_icp_accumulate(const a3d_icp_params* params, const orc_kdtree
 a3d_status orc_pcl_icp_align(const a3d_icp_params* params, const orc_kdtree* tree,
                              const a3d_point_cloud_view* target, const a3d_point_cloud_view* source,
                              a3d_pose* out_pose, float* trace);
+/* The normal-angle gates as the reference writes them, per dot product d[i]: out[i] = 1 iff the correspondence is
+ * rejected, i.e. acos(d).abs() > thr (strict, pcl_icp.rs) or acos(d).abs() >= thr (not strict, image_icp.rs). */
+void orc_acos_gate_rejects(const float* d, uint64_t n, float thr, int32_t strict, uint8_t* out);
 
 /* ---- frame preparation ------------------------------------------------------------------------------ */
 /* RangeImage::compute_normals (src/range_image/structure.rs:184-262) */

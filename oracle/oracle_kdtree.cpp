@@ -206,4 +206,12 @@ a3d_status orc_pcl_icp_align(const a3d_icp_params* prm, const orc_kdtree* tree,
   return A3D_OK;
 }
 
+// The gate expressions of pcl_pass (above) and image_icp_chunk (oracle_icp.cpp), one dot product at a time.
+void orc_acos_gate_rejects(const float* d, uint64_t n, float thr, int32_t strict, uint8_t* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    float ang = std::fabs(std::acos(d[i]));
+    out[i] = strict ? (ang > thr) : (ang >= thr);
+  }
+}
+
 }  // extern "C"

@@ -46,6 +46,7 @@ def load(path=None):
     lib.orc_kdtree_free.argtypes = [_P]
     lib.orc_pcl_icp_accumulate.argtypes = [_P, _P, _P, _P, _P, C.c_int32, _P]
     lib.orc_pcl_icp_align.argtypes = [_P, _P, _P, _P, _P, _P]
+    lib.orc_acos_gate_rejects.argtypes = [_P, C.c_uint64, C.c_float, C.c_int32, _P]
     lib.orc_compute_normals.argtypes = [_P, _P, C.c_uint64, C.c_uint64, _P]
     lib.orc_compute_normals_mt.argtypes = [_P, _P, C.c_uint64, C.c_uint64, C.c_int32, _P]
     lib.orc_bilateral_filter_u16.argtypes = [_P, C.c_uint64, C.c_uint64, C.c_double, C.c_double, _P, _P]
@@ -287,6 +288,15 @@ class KdTree:
         if getattr(self, "h", None) and self.h.value:
             load().orc_kdtree_free(self.h)
             self.h = C.c_void_p()
+
+
+def acos_gate_rejects(d, thr, strict):
+    """The reference's normal-angle gate over an array of dot products: True where acos(d).abs() > thr (strict,
+    pcl_icp.rs) or >= thr (not strict, image_icp.rs) rejects the correspondence."""
+    d = np.ascontiguousarray(d, np.float32)
+    out = np.empty(d.shape, np.uint8)
+    load().orc_acos_gate_rejects(ptr(d), d.size, np.float32(thr), int(bool(strict)), ptr(out))
+    return out.astype(bool)
 
 
 def pcl_view(points, normals):
