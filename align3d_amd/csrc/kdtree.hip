@@ -7,6 +7,7 @@
 
 #include "icp_engine.hpp"
 #include "kdtree.hpp"
+#include "pcl_icp.hpp"
 
 using namespace a3d;
 
@@ -162,46 +163,6 @@ __global__ void __launch_bounds__(BLOCK)
     if (i < m) {
       out_idx[i] = idx;
       out_dist[i] = dist;
-    }
-  }
-}
-
-struct PclGates {
-  float max_distance_sqr;
-  float dot_reject_max;  // reject iff -1 <= sn.tn <= dot_reject_max  (== acos(sn.tn).abs() > max_normal_angle)
-};
-
-// The body of Icp::align's point loop (src/icp/pcl_icp.rs:68-92); grid-stride.
-template <int BLOCK>
-__device__ __forceinline__ void pcl_point_loop(const KdSplits& sp, const float4* __restrict__ leaves,
-                                               const float4* __restrict__ leaf_normals, uint32_t n, uint32_t max_depth,
-                                               const float* __restrict__ src_points, const float* __restrict__ src_normals,
-                                               uint32_t m, const Pose& T, const PclGates& gates, float (&acc)[GN_ACC]) {
-  typedef float f32x3 __attribute__((ext_vector_type(3)));
-  typedef f32x3 __attribute__((aligned(4))) f32x3_u;
-  // every lane stays in the loop: the cooperative leaf scan needs the whole wave
-  const uint32_t rounds = (m + gridDim.x * BLOCK - 1) / (gridDim.x * BLOCK);
-  for (uint32_t r = 0; r < rounds; ++r) {
-    const uint32_t i = (r * gridDim.x + blockIdx.x) * BLOCK + threadIdx.x;
-    const uint32_t ii = i < m ? i : m - 1;
-    const f32x3 pv = *(const f32x3_u*)(src_points + 3 * (size_t)ii), nv = *(const f32x3_u*)(src_normals + 3 * (size_t)ii);
-    const V3 p = transform_vector(T, V3{pv.x, pv.y, pv.z});
-    const uint32_t base = kdtree_descend(sp, n, max_depth, p);
-    uint32_t slot;
-    float d2;
-    kdtree_scan_leaves_coop(leaves, base, p, &slot, &d2);
-    // the winner's record and its normal: one 16-byte gather each (the point's line was just scanned)
-    const float4 win = leaves[slot], tn4 = leaf_normals[slot];
-    const V3 sn = transform_normal(T, V3{nv.x, nv.y, nv.z});
-    const V3 tn{tn4.x, tn4.y, tn4.z};
-    const float c = dot(sn, tn);
-    const bool keep = i < m && !(d2 > gates.max_distance_sqr) && !(c >= -1.0f && c <= gates.dot_reject_max);
-    if (keep) {
-      const V3 tp{win.x, win.y, win.z};
-      const float rr = dot(tp - p, tn);
-      const V3 tw = cross(p, tn);
-      const float J[6] = {tn.x, tn.y, tn.z, tw.x, tw.y, tw.z};
-      gn_step(acc, rr, J);
     }
   }
 }

@@ -44,14 +44,23 @@ void kdtree_shape(uint32_t n, uint32_t* max_depth, uint64_t* n_leaves, uint64_t*
 // Device build: the selection build (kdtree_select.hip); diagnostics build: also the sorting build (kdtree_build.hip: one
 // segmented stable sort per level, A3D_KDTREE_BUILD=sorted); both bit-identical to the host build.
 // Expects t->n, max_depth, n_split, n_leaf_slots set; allocates and fills d_split, d_leaves, d_slot_of_point.
-a3d_status kdtree_build_device(a3d_kdtree* t, const float* d_points);
+// `arrays` (kdtree_arrays_bytes(n, max_depth) bytes, 256-byte aligned): the tree's arrays are carved from the caller's
+// memory instead of a block of the tree's own.  `deferred_flags` (2 page-locked words): the build is enqueued without
+// the wait for its flag words; the caller waits once for several builds and passes each tree's words to
+// kdtree_build_deferred_check (IcpBatch, pcl_icp_batch.hip).
+a3d_status kdtree_build_device(a3d_kdtree* t, const float* d_points, void* arrays = nullptr,
+                               uint32_t* deferred_flags = nullptr);
+size_t kdtree_arrays_bytes(uint32_t n, uint32_t max_depth);
+a3d_status kdtree_build_deferred_check(a3d_context* ctx, const uint32_t* flags);
 // The selection build: `scratch` holds kdtree_select_scratch_bytes(n) bytes.
 size_t kdtree_select_scratch_bytes(uint32_t n);
-a3d_status kdtree_build_device_select(a3d_kdtree* t, const float* d_points, void* scratch, hipEvent_t done);
+a3d_status kdtree_build_device_select(a3d_kdtree* t, const float* d_points, void* scratch, hipEvent_t done,
+                                      uint32_t* deferred_flags = nullptr);
 // Size of the context scratch region [2] a device build of n points needs: the staged points + the temporaries.
 size_t kdtree_build_scratch_bytes(uint32_t n, uint32_t max_depth, hipStream_t s);
-// leaf_normals[slot_of_point[i]] = normals[i] (device build)
-a3d_status kdtree_scatter_normals_device(a3d_kdtree* t, const float* d_normals);
+// leaf_normals[slot_of_point[i]] = normals[i] (device build); `mem`: n_leaf_slots float4 of the caller's instead of a
+// block of the tree's own
+a3d_status kdtree_scatter_normals_device(a3d_kdtree* t, const float* d_normals, void* mem = nullptr);
 
 // The hand-written stable sorts of the device build (kdtree_sort.hip).
 size_t kdtree_sort_scratch_bytes(uint32_t n);

@@ -187,14 +187,22 @@ size_t kdtree_build_scratch_bytes(uint32_t n, uint32_t max_depth, hipStream_t s)
   return std::max(sorted, pad(kdtree_select_scratch_bytes(n))) + pad((size_t)n * 12);
 }
 
+size_t kdtree_arrays_bytes(uint32_t n, uint32_t max_depth) {
+  auto pad256 = [](size_t b) { return ((b + 255) / 256) * 256; };
+  return pad256((1ull << max_depth) * 16 * sizeof(float4)) + pad256(std::max<size_t>(1, ((size_t)1 << max_depth) - 1) * 4) +
+         pad256((size_t)n * sizeof(uint32_t));
+}
+
 // The tree's three arrays in ONE allocation (hipMalloc synchronises the device): leaves first (16-byte records).
-static a3d_status kdtree_alloc_arrays(a3d_kdtree* t) {
+static a3d_status kdtree_alloc_arrays(a3d_kdtree* t, void* arrays) {
   const uint64_t n_slots = (1ull << t->max_depth) * 16;
   auto pad256 = [](size_t b) { return ((b + 255) / 256) * 256; };
   const size_t leaves_b = pad256(n_slots * sizeof(float4)), split_b = pad256(std::max<size_t>(1, (size_t)t->n_split) * 4);
-  char* block = nullptr;
-  A3D_TRY(ctx_block_alloc(t->ctx, leaves_b + split_b + (size_t)t->n * sizeof(uint32_t), (void**)&block, &t->block_bytes));
-  t->d_block = block;
+  char* block = (char*)arrays;
+  if (!block) {
+    A3D_TRY(ctx_block_alloc(t->ctx, leaves_b + split_b + (size_t)t->n * sizeof(uint32_t), (void**)&block, &t->block_bytes));
+    t->d_block = block;
+  }
   t->d_leaves = (float4*)block;
   t->d_split = (float*)(block + leaves_b);
   t->d_slot_of_point = (uint32_t*)(block + leaves_b + split_b);
@@ -207,12 +215,13 @@ static a3d_status kdtree_build_device_sorted(a3d_kdtree* t, const float* d_point
 
 // The selection build (kdtree_select.hip).  Diagnostics build: A3D_KDTREE_BUILD=sorted runs the sorting build below
 // instead (the cross-check of the selection build, as the host build and rocPRIM are of the sorting build).
-a3d_status kdtree_build_device(a3d_kdtree* t, const float* d_points) {
-  A3D_TRY(kdtree_alloc_arrays(t));
+a3d_status kdtree_build_device(a3d_kdtree* t, const float* d_points, void* arrays, uint32_t* deferred_flags) {
+  A3D_TRY(kdtree_alloc_arrays(t, arrays));
 #ifdef A3D_DIAGNOSTICS
   const char* mode = getenv("A3D_KDTREE_BUILD");
-  if (mode && !strcmp(mode, "sorted")) {
+  if (mode && !strcmp(mode, "sorted")) {  // (the cross-check build waits for itself: nothing is left to defer)
     t->built_by = 2;
+    if (deferred_flags) deferred_flags[0] = deferred_flags[1] = 0;
     return kdtree_build_device_sorted(t, d_points);
   }
 #endif
@@ -224,8 +233,8 @@ a3d_status kdtree_build_device(a3d_kdtree* t, const float* d_points) {
   // instrumentation (a3d_kdtree_build_ms): the build's launches between two events on the stream
   hipEvent_t e0 = t->ctx->kd_ev[0], e1 = t->ctx->kd_ev[1];  // (the context's: an event made and destroyed per build cost ~10 us)
   const bool timed = e0 && e1 && hipEventRecord(e0, t->ctx->stream) == hipSuccess;
-  const a3d_status st = kdtree_build_device_select(t, d_points, scratch, timed ? e1 : nullptr);
-  if (timed && st == A3D_OK) (void)hipEventElapsedTime(&t->build_ms, e0, e1);
+  const a3d_status st = kdtree_build_device_select(t, d_points, scratch, timed ? e1 : nullptr, deferred_flags);
+  if (timed && st == A3D_OK && !deferred_flags) (void)hipEventElapsedTime(&t->build_ms, e0, e1);
   return st;
 }
 
@@ -342,10 +351,13 @@ static a3d_status kdtree_build_device_sorted(a3d_kdtree* t, const float* d_point
 
 #endif  // A3D_DIAGNOSTICS (the sorting build)
 
-a3d_status kdtree_scatter_normals_device(a3d_kdtree* t, const float* d_normals) {
+a3d_status kdtree_scatter_normals_device(a3d_kdtree* t, const float* d_normals, void* mem) {
   hipStream_t s = t->ctx->stream;
-  A3D_TRY(ctx_block_alloc(t->ctx, t->n_leaf_slots * sizeof(float4), &t->d_normals_block, &t->normals_block_bytes));
-  t->d_leaf_normals = (float4*)t->d_normals_block;
+  if (!mem) {
+    A3D_TRY(ctx_block_alloc(t->ctx, t->n_leaf_slots * sizeof(float4), &t->d_normals_block, &t->normals_block_bytes));
+    mem = t->d_normals_block;
+  }
+  t->d_leaf_normals = (float4*)mem;
   A3D_HIP_TRY(hipMemsetAsync(t->d_leaf_normals, 0, t->n_leaf_slots * sizeof(float4), s));
   hipLaunchKernelGGL(scatter_normals_kernel, grid_for(t->n), dim3(256), 0, s, d_normals, t->d_slot_of_point, t->n,
                      t->d_leaf_normals);

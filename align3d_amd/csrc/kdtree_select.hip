@@ -2034,8 +2034,11 @@ namespace a3d {
 size_t kdtree_select_scratch_bytes(uint32_t n) { return sel_layout(n, narrow_len_setting(), wide_cap_setting()).total; }
 
 // d_points: [n][3] f32 on the device; `scratch`: kdtree_select_scratch_bytes(n) bytes.  Fills t->d_split, t->d_leaves,
-// t->d_slot_of_point (allocated by the caller) and synchronises.
-a3d_status kdtree_build_device_select(a3d_kdtree* t, const float* d_points, void* scratch, hipEvent_t done) {
+// t->d_slot_of_point (allocated by the caller) and synchronises.  deferred_flags (2 page-locked words): the build is only
+// enqueued — its flag words are copied there in stream order and the caller reads them behind ONE wait for several builds
+// (kdtree_build_deferred_check); the context's placement setting then holds for all of those builds.
+a3d_status kdtree_build_device_select(a3d_kdtree* t, const float* d_points, void* scratch, hipEvent_t done,
+                                      uint32_t* deferred_flags) {
   hipStream_t s = t->ctx->stream;
   const uint32_t n = t->n, D = t->max_depth;
   const SelLayout L = sel_layout(n, narrow_len_setting(), wide_cap_setting());
@@ -2148,6 +2151,10 @@ a3d_status kdtree_build_device_select(a3d_kdtree* t, const float* d_points, void
 #undef A3D_NARROW_SELECT
   A3D_HIP_TRY(hipGetLastError());
   if (done) A3D_HIP_TRY(hipEventRecord(done, s));
+  if (deferred_flags) {
+    A3D_HIP_TRY(hipMemcpyAsync((void*)deferred_flags, flags, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return A3D_OK;
+  }
   // (page-locked words of the context: a copy into pageable memory is staged by the runtime and blocks for longer)
   volatile uint32_t* h_flags = t->ctx->pinned_words + a3d_context::PINNED_WORDS;
   A3D_HIP_TRY(hipMemcpyAsync((void*)h_flags, flags, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -2158,6 +2165,16 @@ a3d_status kdtree_build_device_select(a3d_kdtree* t, const float* d_points, void
     if (t->ctx->kd_quiet_builds.fetch_add(1) + 1 >= KD_QUIET_BUILDS) t->ctx->kd_wide_place.store(false), t->ctx->kd_quiet_builds.store(0);
   }
   A3D_REQUIRE(!h_flags[FLAG_NAN], A3D_NAN_IN_INPUT,
+              "NaN coordinate in kd-tree input (the reference panics in partial_cmp().unwrap())");
+  return A3D_OK;
+}
+
+// The host's half of a deferred build, once the stream has been waited for: an oversized median bucket turns the
+// context's placement launches back on (builds that met none are not counted towards dropping them: the batch ran
+// with one setting), a NaN coordinate is the reference's panic.
+a3d_status kdtree_build_deferred_check(a3d_context* ctx, const uint32_t* flags) {
+  if (flags[FLAG_OVERSIZED]) ctx->kd_wide_place.store(true), ctx->kd_quiet_builds.store(0);
+  A3D_REQUIRE(!flags[FLAG_NAN], A3D_NAN_IN_INPUT,
               "NaN coordinate in kd-tree input (the reference panics in partial_cmp().unwrap())");
   return A3D_OK;
 }

@@ -405,3 +405,83 @@ class Icp:
             self.free()
         except Exception:
             pass
+
+
+class IcpBatch:
+    """P independent Icp::new(params, target_p).align(source_p) (src/icp/pcl_icp.rs:31-107) over resident clouds in one
+    launch sequence (a3d_pcl_icp_batch_*).  DevicePointCloud only: clouds in host memory go through Icp."""
+
+    def __init__(self, ctx, params, targets):
+        self.ctx = ctx
+        self.params = params
+        self.handle = C.c_void_p()
+        self.targets = self._resident(targets, "target")  # kept: the clouds outlive the handle
+        self.sources = []
+        self.n_pairs = len(self.targets)
+        p = params.to_c()
+        _abi.check(ctx.lib.a3d_pcl_icp_batch_new_device(ctx.handle, C.byref(p), self.n_pairs, self._views(self.targets),
+                                                        C.byref(self.handle)), "IcpBatch::new")
+
+    @staticmethod
+    def new(ctx, params, targets):
+        return IcpBatch(ctx, params, targets)
+
+    @staticmethod
+    def _resident(clouds, what):
+        clouds = list(clouds)
+        for c in clouds:
+            if not isinstance(c, DevicePointCloud):
+                raise TypeError(f"IcpBatch takes DevicePointCloud {what}s (got {type(c).__name__}); host clouds go through Icp")
+        return clouds
+
+    @staticmethod
+    def _views(clouds):
+        return (_abi.PointCloudViewC * max(1, len(clouds)))(*[c.view() for c in clouds])
+
+    def _sources(self, sources):
+        sources = self._resident(sources, "source")
+        if len(sources) != self.n_pairs:
+            raise _abi.InvalidParameter(f"IcpBatch of {self.n_pairs} pairs got {len(sources)} sources")
+        return sources
+
+    def align(self, sources):
+        """Runs all pairs; returns (list of Transform, int32 status array: A3D_OK or A3D_SOLVE_FAILED per pair)."""
+        sources = self._sources(sources)
+        poses = (_abi.PoseC * max(1, self.n_pairs))()
+        status = np.zeros(self.n_pairs, np.int32)
+        _abi.check(self.ctx.lib.a3d_pcl_icp_batch_align_device(self.handle, self._views(sources), poses,
+                                                               status.ctypes.data_as(C.POINTER(C.c_int32))),
+                   "IcpBatch::align")
+        self.sources = sources
+        return [Transform.from_c(poses[i]) for i in range(self.n_pairs)], status
+
+    def enqueue(self, sources):
+        """Enqueues one pass without synchronising the host; results() reads it."""
+        sources = self._sources(sources)
+        _abi.check(self.ctx.lib.a3d_pcl_icp_batch_align_device(self.handle, self._views(sources), None, None),
+                   "IcpBatch::enqueue")
+        self.sources = sources  # read by the device until the pass is complete
+
+    def results(self):
+        """(list of Transform, int32 status array) of the most recent pass; waits for that pass only."""
+        poses = (_abi.PoseC * max(1, self.n_pairs))()
+        status = np.zeros(self.n_pairs, np.int32)
+        _abi.check(self.ctx.lib.a3d_pcl_icp_batch_results(self.handle, poses, status.ctypes.data_as(C.POINTER(C.c_int32))),
+                   "IcpBatch::results")
+        return [Transform.from_c(poses[i]) for i in range(self.n_pairs)], status
+
+    def last_device_ms(self):
+        ms = C.c_float()
+        _abi.check(self.ctx.lib.a3d_pcl_icp_batch_last_device_ms(self.handle, C.byref(ms)))
+        return ms.value
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.a3d_pcl_icp_batch_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -457,6 +457,56 @@ class Icp {
   a3d_pcl_icp* icp_ = nullptr;
 };
 
+/// P independent Icp::new(params, &target_p).align(&source_p) over clouds resident in HBM, in one launch sequence
+/// (a3d_pcl_icp_batch_*): the views hold DEVICE pointers; the targets are read by the constructor only, the sources
+/// until the pass that reads them is complete.  status()[p] is A3D_OK or A3D_SOLVE_FAILED per pair.
+class IcpBatch {
+ public:
+  IcpBatch(const Context& ctx, const IcpParams& params, const std::vector<a3d_point_cloud_view>& d_targets)
+      : n_pairs_(d_targets.size()) {
+    check(a3d_pcl_icp_batch_new_device(ctx.raw(), &params, d_targets.size(), d_targets.data(), &b_));
+  }
+  ~IcpBatch() { a3d_pcl_icp_batch_free(b_); }
+  IcpBatch(const IcpBatch&) = delete;
+  IcpBatch& operator=(const IcpBatch&) = delete;
+  IcpBatch(IcpBatch&& o) noexcept : n_pairs_(o.n_pairs_), b_(o.b_), status_(std::move(o.status_)) { o.b_ = nullptr; }
+  std::vector<Transform> align(const std::vector<a3d_point_cloud_view>& d_sources) {
+    if (d_sources.size() != n_pairs_) throw InvalidParameter("A3D_INVALID_PARAMETER: one source per pair of the batch");
+    std::vector<a3d_pose> poses(n_pairs_);
+    status_.assign(n_pairs_, 0);
+    check(a3d_pcl_icp_batch_align_device(b_, d_sources.data(), poses.data(), status_.data()));
+    return transforms(poses);
+  }
+  /// One pass without synchronising the host; results() reads it (and waits for it alone).
+  void enqueue(const std::vector<a3d_point_cloud_view>& d_sources) {
+    if (d_sources.size() != n_pairs_) throw InvalidParameter("A3D_INVALID_PARAMETER: one source per pair of the batch");
+    check(a3d_pcl_icp_batch_align_device(b_, d_sources.data(), nullptr, nullptr));
+  }
+  std::vector<Transform> results() {
+    std::vector<a3d_pose> poses(n_pairs_);
+    status_.assign(n_pairs_, 0);
+    if (n_pairs_) check(a3d_pcl_icp_batch_results(b_, poses.data(), status_.data()));
+    return transforms(poses);
+  }
+  const std::vector<int32_t>& status() const { return status_; }
+  float last_device_ms() const {
+    float ms = 0.f;
+    check(a3d_pcl_icp_batch_last_device_ms(b_, &ms));
+    return ms;
+  }
+  size_t size() const { return n_pairs_; }
+
+ private:
+  static std::vector<Transform> transforms(const std::vector<a3d_pose>& poses) {
+    std::vector<Transform> out;
+    for (const a3d_pose& p : poses) out.push_back(Transform::from_c(p));
+    return out;
+  }
+  size_t n_pairs_ = 0;
+  a3d_pcl_icp_batch* b_ = nullptr;
+  std::vector<int32_t> status_;
+};
+
 /// P independent MultiscaleAlign jobs in one launch sequence (the per-GPU shard of a batch of frame pairs):
 /// the same parameters for every pair, pyramids[pair][level]; align() returns one Transform per pair and
 /// throws Panic if any pair's solve failed (status() then tells which).

@@ -111,6 +111,7 @@ typedef struct a3d_multi_context a3d_multi_context;     /* one a3d_context per d
 typedef struct a3d_multiscale_multi_batch a3d_multiscale_multi_batch; /* P MultiscaleAlign jobs over several GPUs */
 typedef struct a3d_kdtree a3d_kdtree;                   /* R3dTree */
 typedef struct a3d_pcl_icp a3d_pcl_icp;                 /* Icp */
+typedef struct a3d_pcl_icp_batch a3d_pcl_icp_batch;     /* P independent Icp jobs over resident clouds */
 
 /* ---- library / context -------------------------------------------------------------------
  * Threading: a context owns one HIP stream, its scratch regions, the pool of pyramid arenas and the cached
@@ -539,6 +540,38 @@ a3d_status a3d_pcl_icp_accumulate(a3d_pcl_icp* icp, const a3d_point_cloud_view* 
 /* Instrumentation: device time (ms) of the iteration launches of the most recent a3d_pcl_icp_align. */
 a3d_status a3d_pcl_icp_last_device_ms(a3d_pcl_icp* icp, float* out_ms);
 a3d_status a3d_pcl_icp_free(a3d_pcl_icp* icp);
+
+/* P independent Icp::new(params, &target_p).align(&source_p) (src/icp/pcl_icp.rs:31-107) over clouds that are resident
+ * in device memory, run as one launch sequence: every iteration is ONE launch for all pairs (grid = blocks per pair x
+ * pairs).  Per pair the behaviour is a3d_pcl_icp_new_device + a3d_pcl_icp_align_device's: the same tree bit for bit, start
+ * from Transform::eye(), the same per-point arithmetic; the block partials are grouped differently, so poses agree with
+ * the one-pair form to rounding, not bit for bit.  Results do not depend on the order of the pairs in the batch. */
+
+/* Icp::new for every pair (pcl_icp.rs:31-38): d_targets [n_pairs] views whose `points` / `normals` are DEVICE pointers,
+ * read during this call only (trees and leaf normals are copies).  The trees are built back to back on the context's
+ * stream and the call waits for the device once, after the last one.  One a3d_icp_params for all pairs.
+ * Before anything is launched: a target with 0 or >= 2^31 points is A3D_INVALID_PARAMETER; a target without normals is
+ * A3D_MISSING_FIELD (the `expect` of pcl_icp.rs:50-53, raised here instead of at align time); after the builds a NaN
+ * coordinate is A3D_NAN_IN_INPUT.  The message names the pair.  n_pairs == 0 is A3D_OK: an empty batch that never
+ * touches the context and whose align is a no-op. */
+a3d_status a3d_pcl_icp_batch_new_device(a3d_context* ctx, const a3d_icp_params* params, uint64_t n_pairs,
+                                        const a3d_point_cloud_view* d_targets, a3d_pcl_icp_batch** out);
+/* Icp::align for every pair (pcl_icp.rs:47-107): d_sources [n_pairs] views of DEVICE pointers, read until the pass is
+ * complete.  out_poses_host / out_status_host: [n_pairs] or NULL; with both NULL the call only enqueues (no host
+ * sync; a3d_pcl_icp_batch_results reads the pass).  Returns A3D_OK when the pass ran: a pair whose
+ * GaussNewton::solve() is None (pcl_icp.rs:96 `unwrap`s) has status A3D_SOLVE_FAILED, keeps the pose it had reached and
+ * does not disturb the other pairs.  Before anything is launched: a source with len == 0 (or >= 2^31) is
+ * A3D_INVALID_PARAMETER, a source without normals A3D_MISSING_FIELD (pcl_icp.rs:54-58); the message names the pair. */
+a3d_status a3d_pcl_icp_batch_align_device(a3d_pcl_icp_batch* batch, const a3d_point_cloud_view* d_sources,
+                                          a3d_pose* out_poses_host, int32_t* out_status_host);
+/* Results of the most recent pass of `batch` (the same contract as a3d_multiscale_batch_results): waits for that pass
+ * only. */
+a3d_status a3d_pcl_icp_batch_results(a3d_pcl_icp_batch* batch, a3d_pose* out_poses_host, int32_t* out_status_host);
+/* Instrumentation: device time (ms) of the most recent pass, between hipEvents round its launches (as
+ * a3d_pcl_icp_last_device_ms); waits for that pass. */
+a3d_status a3d_pcl_icp_batch_last_device_ms(a3d_pcl_icp_batch* batch, float* out_ms);
+/* Drop for the batch (the Icp objects of pcl_icp.rs:15-20 and their R3dTree). */
+a3d_status a3d_pcl_icp_batch_free(a3d_pcl_icp_batch* batch);
 
 /* ---- BilateralFilter<u16> (src/bilateral/edge_aware_filter.rs:30-135, grid.rs:32-162) ----- */
 

@@ -4,4 +4,4 @@ pub mod multiscale;
 pub mod pcl_icp;
 pub use align3d::icp::{IcpParams, MsIcpParams};
 pub use image_icp::ImageIcp;
-pub use pcl_icp::Icp;
+pub use pcl_icp::{Icp, IcpBatch};

@@ -40,6 +40,54 @@ impl<'target> Icp<'target> {
     }
 }
 
+/// P independent `Icp::new(params, target_p).align(source_p)` over clouds that are resident in device memory, as one
+/// launch sequence (a3d_pcl_icp_batch_*).  No counterpart in the reference.  The views hold DEVICE pointers; the
+/// caller keeps the clouds alive while the batch reads them (targets: during `new`; sources: during `align`).
+pub struct IcpBatch {
+    n_pairs: usize,
+    handle: *mut sys::a3d_pcl_icp_batch,
+}
+
+impl IcpBatch {
+    /// Builds the P kd-trees behind one host wait.  Panics where `Icp::new` / `align` would (NaN coordinate,
+    /// kdtree.rs:43; target without normals, pcl_icp.rs:50-53).
+    pub fn new(params: &IcpParams, device_targets: &[sys::a3d_point_cloud_view]) -> Self {
+        let ctx = device::Context::current();
+        let c_params = device::params_of(params);
+        let mut handle = std::ptr::null_mut();
+        device::check(
+            unsafe {
+                sys::a3d_pcl_icp_batch_new_device(ctx, &c_params, device_targets.len() as u64, device_targets.as_ptr(),
+                                                  &mut handle)
+            },
+            "IcpBatch::new",
+        );
+        Self { n_pairs: device_targets.len(), handle }
+    }
+
+    /// One transform per pair; `None` where the reference's `solve().unwrap()` (pcl_icp.rs:96) would panic: a failed
+    /// pair does not disturb the others.
+    pub fn align(&self, device_sources: &[sys::a3d_point_cloud_view]) -> Vec<Option<Transform>> {
+        assert_eq!(device_sources.len(), self.n_pairs, "one source per pair of the batch");
+        let mut poses = vec![sys::a3d_pose::default(); self.n_pairs];
+        let mut status = vec![0i32; self.n_pairs];
+        device::check(
+            unsafe {
+                sys::a3d_pcl_icp_batch_align_device(self.handle, device_sources.as_ptr(), poses.as_mut_ptr(),
+                                                    status.as_mut_ptr())
+            },
+            "IcpBatch::align",
+        );
+        poses.iter().zip(&status).map(|(p, s)| (*s == sys::A3D_OK).then(|| device::transform_of(p))).collect()
+    }
+}
+
+impl Drop for IcpBatch {
+    fn drop(&mut self) {
+        unsafe { sys::a3d_pcl_icp_batch_free(self.handle) };
+    }
+}
+
 impl Drop for Icp<'_> {
     fn drop(&mut self) {
         unsafe { sys::a3d_pcl_icp_free(self.handle) };
