@@ -168,6 +168,11 @@ SIGNATURES = {
     "a3d_range_image_to_point_cloud": (_ST, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "a3d_range_image_to_point_clouds": (_ST, [_PP, C.c_uint64, _PP, _PP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "a3d_range_image_has_normals": (_ST, [_P, C.POINTER(C.c_int32)]),
+    "a3d_point_clouds_transform_device": (_ST, [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, _PP, _PP]),
+    "a3d_point_clouds_merge_device": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)],
+    ),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

@@ -1,0 +1,239 @@
+// &Transform * &PointCloud (src/pointcloud.rs:40-52 over Transform::transform_vectors / transform_normals,
+// src/transform.rs:164-187) on resident clouds, and the same written back to back into one cloud (a map of frames in one
+// coordinate system).  Per point k of cloud i: out_points[k] = transform_vector(pose_i, points[k]) and, with normals,
+// out_normals[k] = transform_normal(pose_i, normals[k]) — the devmath.hpp functions the ICP kernels call, so the value is
+// the reference's f32 bit for bit (no contraction).  A job without a pose copies verbatim: no arithmetic, so NaN
+// payloads, -0 and infinities survive.
+//
+// One launch over every tile of every cloud of a batch (the shape of pointcloud.hip): a job table in the context's
+// scratch region 3, blocks map to tiles, a block-uniform search over first_tile finds the block's job.  A tile is
+// XF_THREADS * PPT consecutive points; in round r thread t takes point tile_base + r * XF_THREADS + t, so a wave touches
+// one contiguous 768-byte span per array per round.  A thread loads every point (and normal) of its tile before it
+// stores any, which puts PPT (2 PPT) independent 12-byte loads in flight per thread and makes an output that is exactly
+// its input safe.  A pure streaming pass: no LDS, no atomics, no block waits on another block; 24 B read and 24 B written
+// per point with normals against ~60 flops: the bound is HBM bandwidth.
+#include <algorithm>
+#include <vector>
+
+#include "common.hpp"
+
+using namespace a3d;
+
+namespace {
+
+constexpr uint32_t XF_THREADS = 256;
+// Points per thread.  Measured on MI355X (scripts/cloud_transform_probe.py) against 1 and 4.
+constexpr uint32_t XF_PPT = 2;
+
+// One non-empty cloud of a batch as the kernel sees it (uploaded per call).
+struct XformJob {
+  const float* points;
+  const float* normals;  // read only when out_normals is set
+  float* out_points;
+  float* out_normals;  // null: no normals are written
+  uint32_t len, first_tile, has_pose, pad;
+  Pose pose;
+  uint32_t pad2;
+};
+static_assert(sizeof(XformJob) == 80, "XformJob layout");
+
+typedef float xf32x3 __attribute__((ext_vector_type(3)));
+typedef xf32x3 __attribute__((aligned(4))) xf32x3_u;
+// The arrays' pointers come out of the job table, where the compiler only knows them as generic addresses (flat_load /
+// flat_store); they are device memory, and saying so gives global_load_dwordx3 / global_store_dwordx3.
+#define XF_GLOBAL __attribute__((address_space(1)))
+
+// The job whose tiles hold `tile` (jobs are in tile order and none is empty; the search is uniform over the block).
+__device__ __forceinline__ uint32_t find_job(const XformJob* __restrict__ jobs, uint32_t n_jobs, uint32_t tile) {
+  uint32_t lo = 0, hi = n_jobs - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].first_tile <= tile) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// (no __restrict__ on the arrays: an output may be exactly its input; every load of a thread precedes its stores)
+template <uint32_t PPT>
+__global__ void __launch_bounds__(XF_THREADS) cloud_transform_kernel(const XformJob* __restrict__ jobs, uint32_t n_jobs) {
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const XformJob& j = jobs[ji];
+  const XF_GLOBAL float* points = (const XF_GLOBAL float*)j.points;
+  const XF_GLOBAL float* normals = (const XF_GLOBAL float*)j.normals;
+  XF_GLOBAL float* out_points = (XF_GLOBAL float*)j.out_points;
+  XF_GLOBAL float* out_normals = (XF_GLOBAL float*)j.out_normals;
+  const uint32_t len = j.len;
+  const uint32_t k0 = (tile - j.first_tile) * (XF_THREADS * PPT) + threadIdx.x;
+  xf32x3 p[PPT], n[PPT];
+#pragma unroll
+  for (uint32_t r = 0; r < PPT; ++r) {
+    const uint32_t k = k0 + r * XF_THREADS;
+    p[r] = n[r] = xf32x3{0.f, 0.f, 0.f};
+    if (k < len) {
+      p[r] = *(const XF_GLOBAL xf32x3_u*)(points + 3 * (size_t)k);
+      if (out_normals) n[r] = *(const XF_GLOBAL xf32x3_u*)(normals + 3 * (size_t)k);
+    }
+  }
+  if (j.has_pose) {
+    const Pose pose = j.pose;
+#pragma unroll
+    for (uint32_t r = 0; r < PPT; ++r) {
+      const V3 v = transform_vector(pose, V3{p[r].x, p[r].y, p[r].z});
+      p[r] = xf32x3{v.x, v.y, v.z};
+      if (out_normals) {
+        const V3 w = transform_normal(pose, V3{n[r].x, n[r].y, n[r].z});
+        n[r] = xf32x3{w.x, w.y, w.z};
+      }
+    }
+  }
+#pragma unroll
+  for (uint32_t r = 0; r < PPT; ++r) {
+    const uint32_t k = k0 + r * XF_THREADS;
+    if (k < len) {
+      *(XF_GLOBAL xf32x3_u*)(out_points + 3 * (size_t)k) = p[r];
+      if (out_normals) *(XF_GLOBAL xf32x3_u*)(out_normals + 3 * (size_t)k) = n[r];
+    }
+  }
+}
+
+uint32_t points_per_thread_setting() {
+  uint32_t v = XF_PPT;
+  if (const char* env = A3D_DIAG_ENV("A3D_CLOUD_TRANSFORM_PPT"))  // diagnostics build: the variants the probe times
+    if (*env) v = (uint32_t)atoi(env);
+  return v == 1 || v == 2 || v == 4 ? v : XF_PPT;
+}
+
+struct ByteRange {
+  uintptr_t begin, end;
+  bool output;
+};
+
+// Whether any output range overlaps any other range (inputs may overlap inputs).
+bool outputs_overlap(std::vector<ByteRange>& ranges) {
+  std::sort(ranges.begin(), ranges.end(), [](const ByteRange& a, const ByteRange& b) { return a.begin < b.begin; });
+  uintptr_t end_any = 0, end_out = 0;  // furthest end among the ranges / the output ranges seen so far
+  for (const ByteRange& r : ranges) {
+    if (r.begin < (r.output ? end_any : end_out)) return true;
+    end_any = std::max(end_any, r.end);
+    if (r.output) end_out = std::max(end_out, r.end);
+  }
+  return false;
+}
+
+// Uploads the job table and runs the one launch; complete on return.
+a3d_status run_jobs(a3d_context* ctx, std::vector<XformJob>& jobs, uint32_t ppt) {
+  uint64_t tiles = 0;
+  const uint32_t tile_points = XF_THREADS * ppt;
+  for (XformJob& j : jobs) {
+    j.first_tile = (uint32_t)tiles;
+    tiles += (j.len + tile_points - 1) / tile_points;
+    A3D_REQUIRE(tiles < (1ull << 31), A3D_INVALID_PARAMETER, "batch too large");
+  }
+  if (jobs.empty()) return A3D_OK;
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  void* region = nullptr;
+  A3D_TRY(ctx_scratch(ctx, 3, jobs.size() * sizeof(XformJob), &region));
+  hipStream_t s = ctx->stream;
+  A3D_HIP_TRY(hipMemcpyAsync(region, jobs.data(), jobs.size() * sizeof(XformJob), hipMemcpyHostToDevice, s));
+  const XformJob* d_jobs = (const XformJob*)region;
+  const dim3 grid((uint32_t)tiles), block(XF_THREADS);
+#ifdef A3D_DIAGNOSTICS  // (the product library holds the one variant it launches)
+  if (ppt == 1) hipLaunchKernelGGL(cloud_transform_kernel<1>, grid, block, 0, s, d_jobs, (uint32_t)jobs.size());
+  else if (ppt == 4) hipLaunchKernelGGL(cloud_transform_kernel<4>, grid, block, 0, s, d_jobs, (uint32_t)jobs.size());
+  else
+#endif
+    hipLaunchKernelGGL(cloud_transform_kernel<XF_PPT>, grid, block, 0, s, d_jobs, (uint32_t)jobs.size());
+  A3D_HIP_TRY(hipGetLastError());
+  // host-synchronous: the caller may free inputs and outputs right after
+  A3D_HIP_TRY(hipStreamSynchronize(s));
+  return A3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+a3d_status a3d_point_clouds_transform_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                             const a3d_pose* poses_host, uint64_t n, float* const* d_out_points,
+                                             float* const* d_out_normals) {
+  if (n == 0) return A3D_OK;
+  A3D_REQUIRE(ctx && d_clouds && d_out_points, A3D_INVALID_PARAMETER, "null argument");
+  std::vector<XformJob> jobs;
+  std::vector<ByteRange> ranges;
+  jobs.reserve(n), ranges.reserve(4 * n);
+  for (uint64_t i = 0; i < n; ++i) {
+    const a3d_point_cloud_view& c = d_clouds[i];
+    if (c.len == 0) continue;  // contributes nothing; its pointers may be null
+    A3D_REQUIRE(c.len < (1ull << 31), A3D_INVALID_PARAMETER, "a cloud of 2^31 points or more");
+    A3D_REQUIRE(c.points && d_out_points[i], A3D_INVALID_PARAMETER, "null points or output pointer");
+    float* out_normals = d_out_normals ? d_out_normals[i] : nullptr;
+    A3D_REQUIRE(!out_normals || c.normals, A3D_MISSING_FIELD, "cloud has no normals");
+    XformJob j{};
+    j.points = c.points, j.normals = out_normals ? c.normals : nullptr;
+    j.out_points = d_out_points[i], j.out_normals = out_normals;
+    j.len = (uint32_t)c.len;
+    if (poses_host) j.has_pose = 1, j.pose = pose_from_c(&poses_host[i]);
+    jobs.push_back(j);
+    // an output that is exactly its own input (in place) stands for both; everything else must be disjoint
+    const uintptr_t bytes = (uintptr_t)c.len * 12;
+    const uintptr_t ip = (uintptr_t)j.points, op = (uintptr_t)j.out_points;
+    if (ip != op) ranges.push_back({ip, ip + bytes, false});
+    ranges.push_back({op, op + bytes, true});
+    if (out_normals) {
+      const uintptr_t in = (uintptr_t)j.normals, on = (uintptr_t)j.out_normals;
+      if (in != on) ranges.push_back({in, in + bytes, false});
+      ranges.push_back({on, on + bytes, true});
+    }
+  }
+  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_transform_device: an output overlaps an input or another output (only output i == input i "
+              "is allowed)");
+  return run_jobs(ctx, jobs, points_per_thread_setting());
+}
+
+a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
+                                         uint64_t n, float* d_out_points, float* d_out_normals, uint64_t capacity,
+                                         uint64_t* out_len) {
+  if (n == 0) {
+    if (out_len) *out_len = 0;
+    return A3D_OK;
+  }
+  A3D_REQUIRE(ctx && d_clouds && d_out_points && out_len, A3D_INVALID_PARAMETER, "null argument");
+  std::vector<XformJob> jobs;
+  std::vector<ByteRange> ranges;
+  jobs.reserve(n), ranges.reserve(2 * n + 2);
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const a3d_point_cloud_view& c = d_clouds[i];
+    if (c.len == 0) continue;
+    A3D_REQUIRE(c.len < (1ull << 31), A3D_INVALID_PARAMETER, "a cloud of 2^31 points or more");
+    A3D_REQUIRE(c.points, A3D_INVALID_PARAMETER, "null points pointer");
+    A3D_REQUIRE(!d_out_normals || c.normals, A3D_MISSING_FIELD, "a cloud of the merge has no normals");
+    XformJob j{};
+    j.points = c.points, j.normals = d_out_normals ? c.normals : nullptr;
+    j.out_points = d_out_points + 3 * total, j.out_normals = d_out_normals ? d_out_normals + 3 * total : nullptr;
+    j.len = (uint32_t)c.len;
+    if (poses_host) j.has_pose = 1, j.pose = pose_from_c(&poses_host[i]);
+    jobs.push_back(j);
+    const uintptr_t bytes = (uintptr_t)c.len * 12;
+    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + bytes, false});
+    if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + bytes, false});
+    total += c.len;
+  }
+  if (capacity < total) {
+    *out_len = total;
+    set_error("a3d_point_clouds_merge_device: capacity %llu is smaller than the %llu points of the clouds (nothing was written)",
+              (unsigned long long)capacity, (unsigned long long)total);
+    return A3D_INVALID_PARAMETER;
+  }
+  ranges.push_back({(uintptr_t)d_out_points, (uintptr_t)d_out_points + total * 12, true});
+  if (d_out_normals) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + total * 12, true});
+  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_merge_device: the output overlaps an input (or its own normals)");
+  A3D_TRY(run_jobs(ctx, jobs, points_per_thread_setting()));
+  *out_len = total;
+  return A3D_OK;
+}
+
+}  // extern "C"

@@ -95,7 +95,8 @@ struct a3d_context {
   int num_cus = 0;
   // Grow-only scratch regions for per-call temporaries (all work on a context is ordered on its one stream,
   // so successive calls may reuse them): [0] frame builder temporaries, [1] bilateral grids, [2] kd-tree build,
-  // [3] range image -> point cloud conversion (its per-image table and tile counts, pointcloud.hip), [4] the per-image,
+  // [3] range image -> point cloud conversion (its per-image table and tile counts, pointcloud.hip) and the job table of the
+  // cloud transform / merge (cloud_transform.hip; both calls are host-synchronous), [4] the per-image,
   // per-level pointer table of a3d_range_image_pyramids / a3d_range_image_compute_intensity (pyramid.hip).
   void* scratch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t scratch_size[5] = {0, 0, 0, 0, 0};

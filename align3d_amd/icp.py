@@ -332,6 +332,115 @@ class DevicePointCloud:
             c.n = int(k)
         return clouds
 
+    @staticmethod
+    def _allocate(ctx, n, with_normals):
+        """An uninitialised resident cloud of n points (at least one point's worth of memory, so that `d_normals is None`
+        keeps meaning "no normals")."""
+        c = DevicePointCloud.__new__(DevicePointCloud)
+        c.ctx, c.n = ctx, int(n)
+        c.d_points, c.d_normals = None, None
+        try:
+            c.d_points = ctx.malloc(max(1, c.n) * 12)
+            c.d_normals = ctx.malloc(max(1, c.n) * 12) if with_normals else None
+        except BaseException:
+            c.free()
+            raise
+        return c
+
+    @staticmethod
+    def _resident_batch(clouds, transforms, what):
+        """(clouds, their shared context, PoseC array or None) for the a3d_point_clouds_* calls."""
+        clouds = list(clouds)
+        for c in clouds:
+            if not isinstance(c, DevicePointCloud):
+                raise TypeError(f"{what} takes DevicePointCloud (got {type(c).__name__}); there is no host fallback")
+        ctx = clouds[0].ctx
+        if any(c.ctx is not ctx for c in clouds):
+            raise _abi.InvalidParameter(f"{what}: the clouds must share a context")
+        poses = None
+        if transforms is not None:
+            transforms = list(transforms)
+            if len(transforms) != len(clouds):
+                raise _abi.InvalidParameter(f"{what}: {len(clouds)} clouds but {len(transforms)} transforms")
+            poses = (_abi.PoseC * len(clouds))(*[t.to_c() for t in transforms])
+        return clouds, ctx, poses
+
+    @staticmethod
+    def _views(clouds):
+        return (_abi.PointCloudViewC * len(clouds))(*[c.view() for c in clouds])
+
+    @staticmethod
+    def transform_many(clouds, transforms):
+        """[transforms[i] * clouds[i]] (&Transform * &PointCloud, src/pointcloud.rs:40-52) as new resident clouds, in ONE
+        call and one launch (a3d_point_clouds_transform_device).  Each result has normals iff its input has them."""
+        if transforms is None:
+            raise TypeError("transform_many needs one Transform per cloud")
+        clouds = list(clouds)
+        if not clouds:
+            return []
+        clouds, ctx, poses = DevicePointCloud._resident_batch(clouds, transforms, "transform_many")
+        n, outs = len(clouds), []
+        try:
+            for c in clouds:
+                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None))
+            _abi.check(
+                ctx.lib.a3d_point_clouds_transform_device(ctx.handle, DevicePointCloud._views(clouds), poses, n,
+                                                          (C.c_void_p * n)(*[o.d_points for o in outs]),
+                                                          (C.c_void_p * n)(*[o.d_normals for o in outs])),
+                "a3d_point_clouds_transform_device",
+            )
+        except BaseException:
+            for o in outs:
+                o.free()
+            raise
+        return outs
+
+    def transformed(self, transform):
+        """transform * self as a new resident cloud (normals iff this cloud has them)."""
+        return DevicePointCloud.transform_many([self], [transform])[0]
+
+    def transform_(self, transform):
+        """self = transform * self, in place (every point is read before it is written); returns self."""
+        pose = transform.to_c()
+        v = self.view()
+        _abi.check(
+            self.ctx.lib.a3d_point_clouds_transform_device(self.ctx.handle, C.byref(v), C.byref(pose), 1,
+                                                           (C.c_void_p * 1)(self.d_points),
+                                                           (C.c_void_p * 1)(self.d_normals)),
+            "a3d_point_clouds_transform_device",
+        )
+        return self
+
+    @staticmethod
+    def merge(clouds, transforms=None, normals=None):
+        """One resident cloud holding transforms[i] * clouds[i] back to back, cloud order then point order
+        (a3d_point_clouds_merge_device): frames brought into one coordinate system, a valid target for Icp / IcpBatch.
+        transforms=None concatenates bit for bit.  The result has normals when the non-empty clouds all have them and
+        none when none has; a mix raises InvalidParameter unless normals=False asks for points only."""
+        clouds = list(clouds)
+        if not clouds:
+            raise _abi.InvalidParameter("merge needs at least one cloud (an empty list has no context to allocate on)")
+        clouds, ctx, poses = DevicePointCloud._resident_batch(clouds, transforms, "merge")
+        if normals is None:
+            have = {c.d_normals is not None for c in clouds if c.n > 0} or {c.d_normals is not None for c in clouds}
+            if len(have) > 1:
+                raise _abi.InvalidParameter("merge: some clouds have normals and some do not (normals=False merges the points only)")
+            normals = have.pop()
+        total = sum(c.n for c in clouds)
+        out = DevicePointCloud._allocate(ctx, total, bool(normals))
+        try:
+            n_out = C.c_uint64()
+            _abi.check(
+                ctx.lib.a3d_point_clouds_merge_device(ctx.handle, DevicePointCloud._views(clouds), poses, len(clouds),
+                                                      out.d_points, out.d_normals, total, C.byref(n_out)),
+                "a3d_point_clouds_merge_device",
+            )
+        except BaseException:
+            out.free()
+            raise
+        out.n = int(n_out.value)
+        return out
+
     def len(self):
         return self.n
 

@@ -41,7 +41,15 @@ class Transform:
         return (self._rotate(self.q, v) + self.t).astype(np.float32)
 
     def __mul__(self, rhs):
-        """self * rhs (rhs applied first): t = t1 + R1 t2, q = q1 q2 (Hamilton product, not renormalised)."""
+        """self * rhs (rhs applied first): t = t1 + R1 t2, q = q1 q2 (Hamilton product, not renormalised).
+        With a DevicePointCloud on the right: &Transform * &PointCloud (src/pointcloud.rs:40-52) on the device, a new
+        resident cloud (rhs.transformed(self)).  A host PointCloud is not accepted: there is no CPU path and no hidden upload."""
+        if not isinstance(rhs, Transform):
+            from .icp import DevicePointCloud  # (icp imports this module)
+
+            if isinstance(rhs, DevicePointCloud):
+                return rhs.transformed(self)
+            raise TypeError(f"Transform * {type(rhs).__name__}: expected a Transform or a DevicePointCloud")
         f = np.float32
         a0, a1, a2, a3 = f(self.q[0]), f(self.q[1]), f(self.q[2]), f(self.q[3])
         b0, b1, b2, b3 = f(rhs.q[0]), f(rhs.q[1]), f(rhs.q[2]), f(rhs.q[3])

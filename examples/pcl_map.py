@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""A map from a recorded sequence without leaving the device:
+    python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N] [--out map.npy]
+examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
+DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
+camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
+back in one resident cloud (one launch).  The map is downloaded once, for its bounding box; prints the point count and
+the box, and --out writes the points ([N, 3] f32)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from align3d_amd import (Context, DevicePointCloud, IcpBatch, IcpParams, RangeImageBuilder, SlamTbDataset,  # noqa: E402
+                         Transform, TrajectoryBuilder)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("dataset", nargs="?", default=os.path.join(ROOT, "tests", "golden", "rgbd", "sample1"))
+ap.add_argument("--max-frames", type=int, default=None)
+ap.add_argument("--out", default=None, help="write the map's points to this .npy file")
+args = ap.parse_args()
+
+ctx = Context(0)
+ds = SlamTbDataset.load(args.dataset)
+frames = [ds.get(i) for i in range(min(ds.len(), args.max_frames or ds.len()))]
+cam, _, _, depth_scale = frames[0]
+built = RangeImageBuilder(ctx).pyramid_levels(1).with_intensity(False).build_many(cam, [(f[1], f[2]) for f in frames],
+                                                                                  depth_scale)
+images = [pyramid[0] for pyramid in built]
+clouds = DevicePointCloud.from_range_images(images)  # frame k's cloud, resident
+# pair k: frame k + 1 (source) onto frame k (target)
+batch = IcpBatch(ctx, IcpParams.default(), clouds[:-1])
+poses, status = batch.align(clouds[1:])
+traj = TrajectoryBuilder.with_start(Transform.eye(), 0.0)  # frame 0 is the world
+camera_to_world = [traj.current_camera_to_world()]
+for k, (now_to_previous, st) in enumerate(zip(poses, status)):
+    if st != 0:
+        print(f"pair {k} <- {k + 1}: solve failed (status {st}); frame {k + 1} keeps frame {k}'s pose")
+    else:
+        traj.accumulate(now_to_previous, float(k + 1))
+    camera_to_world.append(traj.current_camera_to_world())
+world_map = DevicePointCloud.merge(clouds, camera_to_world)  # the last step: all frames in one coordinate system
+points, _ = world_map.download()
+finite = points[np.isfinite(points).all(axis=1)]
+print(f"{len(clouds)} frames, map of {world_map.len()} points" + (" with normals" if world_map.d_normals is not None else ""))
+if len(finite):
+    print("bounding box: min", finite.min(axis=0).tolist(), "max", finite.max(axis=0).tolist())
+if args.out:
+    np.save(args.out, points)
+    print("wrote", args.out)
+batch.free()
+for x in [world_map] + clouds + images:
+    x.free()
+ctx.close()

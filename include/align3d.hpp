@@ -413,7 +413,53 @@ class DevicePointCloud {
   const float* d_normals() const { return normals_; }  // nullptr: the image had no normals
   a3d_point_cloud_view view() const { return a3d_point_cloud_view{points_, normals_, len_}; }
 
+  /// &Transform * &PointCloud (src/pointcloud.rs:40-52) on the device: a new resident cloud, normals iff this one has
+  /// them (a3d_point_clouds_transform_device).
+  DevicePointCloud transformed(const Transform& t) const {
+    DevicePointCloud out(ctx_, len_, normals_ != nullptr);
+    const a3d_point_cloud_view v = view();
+    const a3d_pose pose = t.to_c();
+    check(a3d_point_clouds_transform_device(ctx_, &v, &pose, 1, &out.points_, &out.normals_));
+    return out;
+  }
+  /// The same in place (every point is read before it is written).
+  DevicePointCloud& transform_in_place(const Transform& t) {
+    const a3d_point_cloud_view v = view();
+    const a3d_pose pose = t.to_c();
+    check(a3d_point_clouds_transform_device(ctx_, &v, &pose, 1, &points_, &normals_));
+    return *this;
+  }
+  /// transforms[i] * clouds[i] back to back in one resident cloud, cloud order then point order
+  /// (a3d_point_clouds_merge_device); an empty `transforms` concatenates bit for bit.  with_normals needs normals on
+  /// every non-empty cloud (Panic: A3D_MISSING_FIELD otherwise).
+  static DevicePointCloud merge(const Context& ctx, const std::vector<const DevicePointCloud*>& clouds,
+                                const std::vector<Transform>& transforms, bool with_normals) {
+    if (!transforms.empty() && transforms.size() != clouds.size())
+      throw InvalidParameter("DevicePointCloud::merge: one transform per cloud, or none");
+    std::vector<a3d_point_cloud_view> views;
+    std::vector<a3d_pose> poses;
+    uint64_t total = 0;
+    for (const DevicePointCloud* c : clouds) views.push_back(c->view()), total += c->len();
+    for (const Transform& t : transforms) poses.push_back(t.to_c());
+    DevicePointCloud out(ctx.raw(), total, with_normals);
+    check(a3d_point_clouds_merge_device(ctx.raw(), views.data(), poses.empty() ? nullptr : poses.data(), views.size(),
+                                        out.points_, out.normals_, total, &out.len_));
+    return out;
+  }
+
  private:
+  // an uninitialised cloud of `len` points (at least one point's worth of memory per array)
+  DevicePointCloud(a3d_context* ctx, uint64_t len, bool with_normals) : ctx_(ctx), len_(len) {
+    const size_t bytes = (len ? len : 1) * 12;
+    void *p = nullptr, *q = nullptr;
+    check(a3d_malloc(ctx_, bytes, &p));
+    points_ = static_cast<float*>(p);
+    if (with_normals) {
+      a3d_status s = a3d_malloc(ctx_, bytes, &q);
+      if (s != A3D_OK) release(), check(s);
+      normals_ = static_cast<float*>(q);
+    }
+  }
   void release() {
     if (points_) a3d_free(ctx_, points_);
     if (normals_) a3d_free(ctx_, normals_);

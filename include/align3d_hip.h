@@ -482,6 +482,31 @@ a3d_status a3d_multiscale_multi_batch_align(a3d_multiscale_multi_batch* batch, a
                                             const float** out_matrices_device0);
 a3d_status a3d_multiscale_multi_batch_free(a3d_multiscale_multi_batch* batch);
 
+/* ---- PointCloud resident on the device (src/pointcloud.rs:8-52) ---------------------------- */
+
+/* Both entries take views whose `points` / `normals` are DEVICE pointers on ctx's GPU ([len][3] f32) and are
+ * host-synchronous like a3d_range_image_to_point_clouds: complete on return, so buffers may be freed right after.  Per
+ * point the value is Transform::transform_vector / transform_normal (src/transform.rs:138-153) in the reference's own
+ * operation order, bit for bit; quaternions are used as given (the reference does not validate them either).  Decided on
+ * the host before anything is launched: n == 0 is A3D_OK and touches nothing; a cloud with len == 0 may have null
+ * pointers and contributes nothing; a len or a batch of 2^31 points' worth of tiles or more is A3D_INVALID_PARAMETER. */
+
+/* &Transform * &PointCloud (src/pointcloud.rs:40-52) for n resident clouds in one launch.
+ * poses_host: n poses, or NULL = copy bit for bit.  d_out_normals may be NULL (no normals
+ * written); an entry that is non-NULL while clouds[i].normals is NULL -> A3D_MISSING_FIELD.
+ * Output i may be exactly input i (points on points, normals on normals: in place); any other overlap of an output with
+ * an input or with another output is A3D_INVALID_PARAMETER. */
+a3d_status a3d_point_clouds_transform_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                             const a3d_pose* poses_host, uint64_t n, float* const* d_out_points,
+                                             float* const* d_out_normals);
+/* The same, written back to back in cloud order then point order into one cloud:
+ * cloud i starts at sum(len[0..i)).  *out_len = total.  capacity < total ->
+ * A3D_INVALID_PARAMETER, *out_len = total, nothing written.  d_out_normals non-NULL requires
+ * normals on every cloud with len > 0 (else A3D_MISSING_FIELD).  The output may overlap no input. */
+a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                         const a3d_pose* poses_host, uint64_t n, float* d_out_points, float* d_out_normals,
+                                         uint64_t capacity, uint64_t* out_len);
+
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
 /* R3dTree::new(&points): `points` [n][3] f32 in host memory are uploaded and the tree is built ON THE DEVICE
