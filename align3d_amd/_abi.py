@@ -173,6 +173,11 @@ SIGNATURES = {
         _ST,
         [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)],
     ),
+    "a3d_point_clouds_voxel_downsample_device": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), C.c_uint64, C.c_float, C.POINTER(C.c_float), _PP, _PP, _PP, C.POINTER(C.c_uint64),
+         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    ),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

@@ -1,0 +1,411 @@
+// Voxel-grid downsampling of resident clouds: of the points that share a cell of a grid of pitch v anchored at o, the one
+// nearest to the cell's centre is kept (ties: the lowest index), and the kept points come out in input order, copied bit
+// for bit.  It is the rule of the reference's only downsampler (src/range_image/resize.rs:4-40: one real sample per cell,
+// never an average, so normals stay true normals) carried over to clouds, with the cell CENTRE in place of the cell mean:
+// an f32 mean depends on the summation order, the centre does not, and the pick becomes one integer minimum.
+//
+// Per point i, all in f32, every operation rounded on its own (-ffp-contract=off, correctly rounded divide):
+//   c_k   = floorf((p_k - o_k) / v)            dropped unless every c_k is finite and in [-2^20, 2^20)
+//   key   = (c_x + 2^20) << 42 | (c_y + 2^20) << 21 | (c_z + 2^20)
+//   ctr_k = (c_k + 0.5f) * v + o_k,  d_k = p_k - ctr_k,  dist = (d_x * d_x + d_y * d_y) + d_z * d_z   (never NaN, may be +inf)
+//   the winner of a key minimises  bits(dist) << 32 | i   (dist >= 0: its bit pattern is monotone)
+//
+// Three launches over every tile of every cloud of a batch plus one fill of the hash tables, whatever the batch size (job
+// table in the context's scratch region 3, blocks find their cloud with a block-uniform search, as cloud_transform.hip and
+// pointcloud.hip do); no block waits on another block:
+//  1. voxel_insert_kernel: a thread per point claims the slot of its key in the cloud's open-addressing table (linear
+//     probing, 64-bit atomicCAS on the key word; at most half the slots can ever be taken) and atomicMins its word into
+//     the slot's second word.  Both are preceded by a device-scope load of the word: a slot that already holds the key
+//     needs no CAS, a slot that already holds a smaller word needs no atomicMin (a stale value can only be larger than
+//     the true one, so the test never skips a needed update).  Dropped points only count themselves.
+//  2. voxel_flag_kernel: each point finds its key's slot again; it is the winner iff the slot's low 32 bits are its
+//     index.  A wave stores its 64-bit ballot (one bit per point: the whole flag array is len / 8 bytes) and the block
+//     its tile's winner count.
+//  3. voxel_compact_kernel: each block sums its cloud's earlier tile counts for its offset (pointcloud.hip's form: at most
+//     VX_MAX_TILES tiles per cloud), ranks its winners from the stored ballots and writes point, normal and index at
+//     offset + rank: input order.  It writes nothing if any cloud of the batch has more winners than its capacity, so
+//     the host needs one wait, after everything, to read the counts back.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "common.hpp"
+
+using namespace a3d;
+
+namespace {
+
+constexpr uint32_t VX_THREADS = 256;
+constexpr uint32_t VX_WAVES = VX_THREADS / 64;
+constexpr uint32_t VX_ROUNDS = 4;
+constexpr uint32_t VX_CHUNK = VX_ROUNDS * VX_THREADS;  // points per chunk: a multiple of 64, so a ballot word never straddles tiles
+constexpr uint32_t VX_GROUPS = VX_CHUNK / 64;          // ballot words per chunk
+constexpr uint32_t VX_MAX_TILES = 4096;                // tiles per cloud at most (the offset sum of a block stays short)
+constexpr unsigned long long VX_EMPTY = ~0ull;         // no key has bit 63 set
+constexpr float VX_CELL_LIMIT = 1048576.0f;            // 2^20
+static_assert(VX_GROUPS <= 64, "a wave's lanes hold the chunk's ballot words");
+
+struct VoxelSlot {
+  unsigned long long key;   // VX_EMPTY or the 63-bit cell key
+  unsigned long long best;  // min over the key's points of bits(dist) << 32 | index
+};
+static_assert(sizeof(VoxelSlot) == 16, "VoxelSlot layout");
+
+// One non-empty cloud of a batch as the kernels see it (uploaded per call).
+struct VoxelJob {
+  const float* points;
+  const float* normals;  // read only when out_normals is set
+  float* out_points;
+  float* out_normals;   // null: no normals are written
+  uint32_t* out_index;  // null: no indices are written
+  VoxelSlot* table;     // slot_mask + 1 slots, filled with VX_EMPTY / ~0 before the insert
+  unsigned long long* flags;  // (len + 63) / 64 ballot words
+  unsigned long long slot_mask;
+  unsigned long long capacity;
+  uint32_t len, first_tile, chunks_per_tile, pad;
+};
+static_assert(sizeof(VoxelJob) == 88, "VoxelJob layout");
+
+struct VoxelGrid {
+  float v, ox, oy, oz;
+};
+
+typedef float vf32x3 __attribute__((ext_vector_type(3)));
+typedef vf32x3 __attribute__((aligned(4))) vf32x3_u;
+
+__device__ __forceinline__ uint32_t find_job(const VoxelJob* __restrict__ jobs, uint32_t n_jobs, uint32_t tile) {
+  uint32_t lo = 0, hi = n_jobs - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].first_tile <= tile) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint32_t lane_rank(uint64_t ballot) {  // set lanes below this one
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// The cell key of a point and (with_dist) its squared distance to the cell centre; false = the point is dropped.
+__device__ __forceinline__ bool voxel_key(const vf32x3 p, const VoxelGrid g, unsigned long long* key, float* dist) {
+  const float cx = floorf((p.x - g.ox) / g.v), cy = floorf((p.y - g.oy) / g.v), cz = floorf((p.z - g.oz) / g.v);
+  // (a NaN fails every comparison, an infinity the range)
+  const bool ok = cx >= -VX_CELL_LIMIT && cx < VX_CELL_LIMIT && cy >= -VX_CELL_LIMIT && cy < VX_CELL_LIMIT &&
+                  cz >= -VX_CELL_LIMIT && cz < VX_CELL_LIMIT;
+  if (!ok) return false;
+  const unsigned long long kx = (unsigned long long)((int)cx + (1 << 20)), ky = (unsigned long long)((int)cy + (1 << 20)),
+                           kz = (unsigned long long)((int)cz + (1 << 20));
+  *key = kx << 42 | ky << 21 | kz;
+  if (dist) {
+    const float dx = p.x - ((cx + 0.5f) * g.v + g.ox), dy = p.y - ((cy + 0.5f) * g.v + g.oy),
+                dz = p.z - ((cz + 0.5f) * g.v + g.oz);
+    *dist = (dx * dx + dy * dy) + dz * dz;
+  }
+  return true;
+}
+
+__device__ __forceinline__ unsigned long long slot_hash(unsigned long long k) {  // the 64-bit finaliser of MurmurHash3
+  k ^= k >> 33, k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33, k *= 0xc4ceb9fe1a85ec53ull;
+  return k ^ k >> 33;
+}
+
+#define VX_LOAD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+// Pass 1.  dropped[job] += dropped points (zeroed by the host upload); *fault is set if a table were ever full (it cannot
+// be: it has at least two slots per point).
+__global__ void __launch_bounds__(VX_THREADS)
+    voxel_insert_kernel(const VoxelJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid,
+                        unsigned long long* __restrict__ dropped, unsigned long long* __restrict__ fault) {
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const VoxelJob& j = jobs[ji];
+  const float* __restrict__ points = j.points;
+  VoxelSlot* table = j.table;
+  const unsigned long long mask = j.slot_mask;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VX_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (len < 2^32 - span: checked by the host)
+  uint32_t n_dropped = 0;
+  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += VX_THREADS) {
+    const vf32x3 pt = *(const vf32x3_u*)(points + 3 * (size_t)p);
+    unsigned long long key;
+    float dist;
+    if (!voxel_key(pt, grid, &key, &dist)) {
+      ++n_dropped;
+      continue;
+    }
+    const unsigned long long word = (unsigned long long)__float_as_uint(dist) << 32 | p;
+    unsigned long long s = slot_hash(key) & mask;
+    bool placed = false;
+    for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
+      unsigned long long k = VX_LOAD_AGENT(&table[s].key);
+      if (k == VX_EMPTY) k = atomicCAS(&table[s].key, VX_EMPTY, key);
+      if (k == VX_EMPTY || k == key) {
+        placed = true;
+        break;
+      }
+    }
+    if (!placed) {
+      atomicMax(fault, 1ull);
+      continue;
+    }
+    if (VX_LOAD_AGENT(&table[s].best) > word) atomicMin(&table[s].best, word);
+  }
+  n_dropped = wave_sum(n_dropped);
+  if ((threadIdx.x & 63u) == 0 && n_dropped) atomicAdd(&dropped[ji], (unsigned long long)n_dropped);
+}
+
+// Pass 2: flags[p / 64] bit p % 64 = point p is its voxel's winner; tile_counts[tile] = winners of the tile; lens[job] +=
+// the same (zeroed by the host upload).
+__global__ void __launch_bounds__(VX_THREADS)
+    voxel_flag_kernel(const VoxelJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, uint32_t* __restrict__ tile_counts,
+                      unsigned long long* __restrict__ lens) {
+  __shared__ uint32_t s_wave[VX_WAVES];
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const VoxelJob& j = jobs[ji];
+  const float* __restrict__ points = j.points;
+  const VoxelSlot* __restrict__ table = j.table;
+  unsigned long long* __restrict__ flags = j.flags;
+  const unsigned long long mask = j.slot_mask;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VX_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t c = 0;  // wave-uniform
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += VX_THREADS) {  // wave-uniform
+    const uint32_t p = base + lane;
+    bool win = false;
+    unsigned long long key;
+    if (p < p_end && voxel_key(*(const vf32x3_u*)(points + 3 * (size_t)p), grid, &key, nullptr)) {
+      unsigned long long s = slot_hash(key) & mask;
+      for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
+        const unsigned long long k = table[s].key;
+        if (k == key) {
+          win = (uint32_t)table[s].best == p;
+          break;
+        }
+        if (k == VX_EMPTY) break;  // (cannot happen: pass 1 placed every kept point)
+      }
+    }
+    const uint64_t ballot = __builtin_amdgcn_ballot_w64(win);
+    if (lane == 0) flags[base >> 6] = ballot;
+    c += (uint32_t)__builtin_popcountll(ballot);
+  }
+  if (lane == 0) s_wave[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t total = 0;
+    for (uint32_t w = 0; w < VX_WAVES; ++w) total += s_wave[w];
+    tile_counts[tile] = total;
+    if (total) atomicAdd(&lens[ji], (unsigned long long)total);
+  }
+}
+
+// Pass 3: every winner of the tile to out[offset + rank].  Nothing is written anywhere if any cloud of the batch has
+// more winners than its capacity (the host then returns A3D_INVALID_PARAMETER).
+__global__ void __launch_bounds__(VX_THREADS)
+    voxel_compact_kernel(const VoxelJob* __restrict__ jobs, uint32_t n_jobs, const uint32_t* __restrict__ tile_counts,
+                         const unsigned long long* __restrict__ lens) {
+  __shared__ uint32_t s_base, s_over;
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const VoxelJob& j = jobs[ji];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t t = tile - j.first_tile;
+  if (wave == 0) {
+    uint32_t s = 0;
+    for (uint32_t k = lane; k < t; k += 64) s += tile_counts[j.first_tile + k];
+    bool over = false;
+    for (uint32_t k = lane; k < n_jobs; k += 64) over |= lens[k] > jobs[k].capacity;
+    s = wave_sum(s);
+    const bool any_over = __builtin_amdgcn_ballot_w64(over) != 0ull;
+    if (lane == 0) s_base = s, s_over = any_over ? 1u : 0u;
+  }
+  __syncthreads();
+  if (s_over) return;
+  const float* __restrict__ points = j.points;
+  const float* __restrict__ normals = j.normals;
+  const unsigned long long* __restrict__ flags = j.flags;
+  float* __restrict__ out_points = j.out_points;
+  float* __restrict__ out_normals = j.out_normals;
+  uint32_t* __restrict__ out_index = j.out_index;
+  const unsigned long long capacity = j.capacity;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VX_CHUNK, n_groups = (len + 63u) >> 6;
+  const uint32_t p0 = t * span, p_end = min(len, p0 + span);
+  uint32_t base = s_base;  // winners of the cloud before this chunk
+  for (uint32_t px0 = p0; px0 < p_end; px0 += VX_CHUNK) {
+    // lane g < VX_GROUPS of every wave holds the ballot word of the chunk's group g (points px0 + 64 g ...), their
+    // exclusive prefix gives every group's offset: no LDS, no block barrier
+    const uint32_t g = (px0 >> 6) + lane;
+    const uint64_t word = lane < VX_GROUPS && g < n_groups ? flags[g] : 0ull;
+    const uint32_t cnt = (uint32_t)__builtin_popcountll(word);
+    uint32_t incl = cnt;
+#pragma unroll
+    for (int o = 1; o < (int)VX_GROUPS; o <<= 1) {
+      const uint32_t up = __shfl_up(incl, o, 64);
+      if (lane >= (uint32_t)o) incl += up;
+    }
+    const uint32_t excl = incl - cnt;
+    uint64_t ballots[VX_ROUNDS];
+    uint32_t offs[VX_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < VX_ROUNDS; ++r) {  // (every lane takes part in the shuffles: no divergence yet)
+      const int src = (int)(r * VX_WAVES + wave);  // the group of this wave's round r (round-major, then wave, then lane)
+      ballots[r] = (uint64_t)__shfl((unsigned long long)word, src, 64);
+      offs[r] = base + __shfl(excl, src, 64);
+    }
+    base += __shfl(incl, (int)VX_GROUPS - 1, 64);
+#pragma unroll
+    for (uint32_t r = 0; r < VX_ROUNDS; ++r) {
+      const uint64_t ballot = ballots[r];
+      if (!((ballot >> lane) & 1ull)) continue;
+      const uint32_t p = px0 + r * VX_THREADS + threadIdx.x;
+      const unsigned long long dst = (unsigned long long)offs[r] + lane_rank(ballot);
+      if (p >= p_end || dst >= capacity) continue;  // (cannot happen: the bit is a point's, the total fits; a bound on every store)
+      *(vf32x3_u*)(out_points + 3 * dst) = *(const vf32x3_u*)(points + 3 * (size_t)p);
+      if (out_normals) *(vf32x3_u*)(out_normals + 3 * dst) = *(const vf32x3_u*)(normals + 3 * (size_t)p);
+      if (out_index) out_index[dst] = p;
+    }
+  }
+}
+
+struct ByteRange {
+  uintptr_t begin, end;
+  bool output;
+};
+
+// Whether any output range overlaps any other range (inputs may overlap inputs).
+bool outputs_overlap(std::vector<ByteRange>& ranges) {
+  std::sort(ranges.begin(), ranges.end(), [](const ByteRange& a, const ByteRange& b) { return a.begin < b.begin; });
+  uintptr_t end_any = 0, end_out = 0;  // furthest end among the ranges / the output ranges seen so far
+  for (const ByteRange& r : ranges) {
+    if (r.begin < (r.output ? end_any : end_out)) return true;
+    end_any = std::max(end_any, r.end);
+    if (r.output) end_out = std::max(end_out, r.end);
+  }
+  return false;
+}
+
+size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+}  // namespace
+
+extern "C" {
+
+a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
+                                                    float voxel_size, const float origin[3], float* const* d_out_points,
+                                                    float* const* d_out_normals, uint32_t* const* d_out_index,
+                                                    const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped) {
+  if (n == 0) return A3D_OK;
+  A3D_REQUIRE(ctx && d_clouds && d_out_points && capacities && out_lens, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.f, A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_voxel_downsample_device: the voxel size must be finite and positive");
+  VoxelGrid grid{voxel_size, 0.f, 0.f, 0.f};
+  if (origin) {
+    A3D_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), A3D_INVALID_PARAMETER,
+                "a3d_point_clouds_voxel_downsample_device: the origin must be finite");
+    grid.ox = origin[0], grid.oy = origin[1], grid.oz = origin[2];
+  }
+  std::vector<VoxelJob> jobs;
+  std::vector<uint64_t> cloud_of_job;
+  std::vector<ByteRange> ranges;
+  jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(5 * n);
+  uint64_t tiles = 0;
+  size_t flag_bytes = 0, table_bytes = 0;  // offsets of a job's arrays inside their parts of the scratch region, for now
+  for (uint64_t i = 0; i < n; ++i) {
+    const a3d_point_cloud_view& c = d_clouds[i];
+    A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
+    if (c.len == 0) continue;  // yields no points; its pointers may be null
+    A3D_REQUIRE(c.points && d_out_points[i], A3D_INVALID_PARAMETER, "null points or output pointer");
+    float* out_normals = d_out_normals ? d_out_normals[i] : nullptr;
+    A3D_REQUIRE(!out_normals || c.normals, A3D_MISSING_FIELD, "cloud has no normals");
+    VoxelJob j{};
+    j.points = c.points, j.normals = out_normals ? c.normals : nullptr;
+    j.out_points = d_out_points[i], j.out_normals = out_normals;
+    j.out_index = d_out_index ? d_out_index[i] : nullptr;
+    j.capacity = capacities[i];
+    j.len = (uint32_t)c.len;
+    const uint64_t chunks = (c.len + VX_CHUNK - 1) / VX_CHUNK;
+    j.chunks_per_tile = (uint32_t)((chunks + VX_MAX_TILES - 1) / VX_MAX_TILES);
+    j.first_tile = (uint32_t)tiles;
+    tiles += (chunks + j.chunks_per_tile - 1) / j.chunks_per_tile;
+    A3D_REQUIRE(tiles < (1ull << 31), A3D_INVALID_PARAMETER, "batch too large");
+    // the kernels' 32-bit point positions run up to one tile span past len
+    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * VX_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
+                "a3d_point_clouds_voxel_downsample_device: a cloud within one tile of 2^32 points");
+    uint64_t slots = 2;
+    while (slots < 2 * c.len) slots <<= 1;
+    j.slot_mask = slots - 1;
+    j.flags = (unsigned long long*)flag_bytes, j.table = (VoxelSlot*)table_bytes;
+    flag_bytes += round256((c.len + 63) / 64 * 8), table_bytes += slots * sizeof(VoxelSlot);
+    jobs.push_back(j), cloud_of_job.push_back(i);
+    // what the call may write is the first min(len, capacity) elements of each output
+    const uintptr_t in_bytes = (uintptr_t)c.len * 12, kept = (uintptr_t)std::min<uint64_t>(c.len, j.capacity);
+    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + in_bytes, false});
+    if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + in_bytes, false});
+    if (kept) {
+      ranges.push_back({(uintptr_t)j.out_points, (uintptr_t)j.out_points + kept * 12, true});
+      if (out_normals) ranges.push_back({(uintptr_t)out_normals, (uintptr_t)out_normals + kept * 12, true});
+      if (j.out_index) ranges.push_back({(uintptr_t)j.out_index, (uintptr_t)j.out_index + kept * 4, true});
+    }
+  }
+  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_voxel_downsample_device: an output overlaps an input or another output (there is no in-place "
+              "form)");
+  for (uint64_t i = 0; i < n; ++i) out_lens[i] = 0;
+  if (out_dropped)
+    for (uint64_t i = 0; i < n; ++i) out_dropped[i] = 0;
+  if (jobs.empty()) return A3D_OK;
+  const size_t n_jobs = jobs.size();
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  // scratch: jobs | lens, dropped, fault (zeroed by the same upload) | tile counts | ballot words | hash tables
+  const size_t jobs_bytes = round256(n_jobs * sizeof(VoxelJob)), words_bytes = round256((2 * n_jobs + 1) * 8),
+               counts_bytes = round256(tiles * 4);
+  const size_t flags_at = jobs_bytes + words_bytes + counts_bytes, tables_at = flags_at + flag_bytes;
+  void* region = nullptr;
+  A3D_TRY(ctx_scratch(ctx, 3, tables_at + table_bytes, &region));
+  char* base = (char*)region;
+  for (VoxelJob& j : jobs) {
+    j.flags = (unsigned long long*)(base + flags_at + (size_t)j.flags);
+    j.table = (VoxelSlot*)(base + tables_at + (size_t)j.table);
+  }
+  std::vector<char> staging(jobs_bytes + words_bytes, 0);
+  memcpy(staging.data(), jobs.data(), n_jobs * sizeof(VoxelJob));
+  const VoxelJob* d_jobs = (const VoxelJob*)base;
+  unsigned long long* d_lens = (unsigned long long*)(base + jobs_bytes);
+  unsigned long long* d_dropped = d_lens + n_jobs;
+  unsigned long long* d_fault = d_lens + 2 * n_jobs;
+  uint32_t* d_tile_counts = (uint32_t*)(base + jobs_bytes + words_bytes);
+  hipStream_t s = ctx->stream;
+  A3D_HIP_TRY(hipMemcpyAsync(region, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
+  A3D_HIP_TRY(hipMemsetAsync(base + tables_at, 0xFF, table_bytes, s));  // every key VX_EMPTY, every best word ~0
+  const dim3 grid_dim((uint32_t)tiles), block(VX_THREADS);
+  hipLaunchKernelGGL(voxel_insert_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, d_dropped, d_fault);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(voxel_flag_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, d_tile_counts, d_lens);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(voxel_compact_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, (const uint32_t*)d_tile_counts,
+                     (const unsigned long long*)d_lens);
+  A3D_HIP_TRY(hipGetLastError());
+  std::vector<unsigned long long> words(2 * n_jobs + 1);
+  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_lens, words.size() * 8, hipMemcpyDeviceToHost, s));
+  // host-synchronous: the caller may free inputs and outputs right after
+  A3D_HIP_TRY(hipStreamSynchronize(s));
+  A3D_REQUIRE(words[2 * n_jobs] == 0, A3D_HIP_ERROR, "a3d_point_clouds_voxel_downsample_device: a hash table filled up");
+  bool over = false;
+  for (size_t k = 0; k < n_jobs; ++k) {
+    out_lens[cloud_of_job[k]] = words[k];
+    if (out_dropped) out_dropped[cloud_of_job[k]] = words[n_jobs + k];
+    over |= words[k] > jobs[k].capacity;
+  }
+  A3D_REQUIRE(!over, A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_voxel_downsample_device: a capacity is smaller than its cloud's kept points (nothing was "
+              "written)");
+  return A3D_OK;
+}
+
+}  // extern "C"

@@ -441,6 +441,65 @@ class DevicePointCloud:
         out.n = int(n_out.value)
         return out
 
+    @staticmethod
+    def _voxel_downsample(clouds, voxel_size, origin, return_index):
+        """([downsampled clouds], [uint32 host index arrays] or None): one a3d_point_clouds_voxel_downsample_device call."""
+        clouds = list(clouds)
+        if not clouds:
+            return [], ([] if return_index else None)
+        clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "voxel_downsample")
+        o = None
+        if origin is not None:
+            o = np.ascontiguousarray(origin, np.float32).reshape(-1)
+            if o.size != 3:
+                raise _abi.InvalidParameter("voxel_downsample: the origin has three coordinates")
+            o = (C.c_float * 3)(*o.tolist())
+        n, outs, d_index = len(clouds), [], []
+        try:
+            for c in clouds:
+                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None))
+                if return_index:
+                    d_index.append(ctx.malloc(max(1, c.n) * 4))
+            lens = (C.c_uint64 * n)()
+            _abi.check(
+                ctx.lib.a3d_point_clouds_voxel_downsample_device(
+                    ctx.handle, DevicePointCloud._views(clouds), n, float(voxel_size), o,
+                    (C.c_void_p * n)(*[x.d_points for x in outs]), (C.c_void_p * n)(*[x.d_normals for x in outs]),
+                    (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens, None),
+                "a3d_point_clouds_voxel_downsample_device",
+            )
+            for x, k in zip(outs, lens):
+                x.n = int(k)
+            index = None
+            if return_index:
+                index = [ctx.to_host(d, np.empty(x.n, np.uint32)) if x.n else np.empty(0, np.uint32)
+                         for d, x in zip(d_index, outs)]
+        except BaseException:
+            for x in outs:
+                x.free()
+            raise
+        finally:
+            for d in d_index:
+                ctx.free(d)
+        return outs, index
+
+    @staticmethod
+    def voxel_downsample_many(clouds, voxel_size, origin=None):
+        """[c.voxel_downsample(voxel_size, origin) for c in clouds] as new resident clouds of one context, in ONE call
+        whose launch count does not depend on the number of clouds (a3d_point_clouds_voxel_downsample_device).  Each
+        result keeps the buffers sized for its input (len() is the kept count) and has normals iff its input has them."""
+        return DevicePointCloud._voxel_downsample(clouds, voxel_size, origin, False)[0]
+
+    def voxel_downsample(self, voxel_size, origin=None, return_index=False):
+        """One point per occupied cell of the grid of pitch `voxel_size` anchored at `origin` (default (0, 0, 0)), as a
+        new resident cloud: the input point nearest to the cell's centre (ties: the lowest index), never an average, so
+        the result is a subsequence of this cloud, points and normals bit for bit, and does not depend on the order of
+        the points.  Points whose cell is not finite or outside [-2^20, 2^20) per axis (NaN, infinities, far outliers)
+        are dropped.  return_index=True returns (cloud, index): `index` is a HOST uint32 array, index[k] = the position
+        in this cloud of the result's point k (one 4-byte-per-kept-point download; nothing else leaves the device)."""
+        outs, index = DevicePointCloud._voxel_downsample([self], voxel_size, origin, return_index)
+        return (outs[0], index[0]) if return_index else outs[0]
+
     def len(self):
         return self.n
 

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """A map from a recorded sequence without leaving the device:
-    python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N] [--out map.npy]
+    python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N] [--voxel V] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
-back in one resident cloud (one launch).  The map is downloaded once, for its bounding box; prints the point count and
-the box, and --out writes the points ([N, 3] f32)."""
+back in one resident cloud (one launch).  With --voxel V the map is then thinned to one point per V-sized cell
+(DevicePointCloud.voxel_downsample: still on the device) and the last frame is aligned against the thinned map with Icp,
+frame to map.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the
+points ([N, 3] f32)."""
 import argparse
 import os
 import sys
@@ -14,12 +16,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from align3d_amd import (Context, DevicePointCloud, IcpBatch, IcpParams, RangeImageBuilder, SlamTbDataset,  # noqa: E402
-                         Transform, TrajectoryBuilder)
+from align3d_amd import (Context, DevicePointCloud, Icp, IcpBatch, IcpParams, RangeImageBuilder,  # noqa: E402
+                         SlamTbDataset, Transform, TrajectoryBuilder)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("dataset", nargs="?", default=os.path.join(ROOT, "tests", "golden", "rgbd", "sample1"))
 ap.add_argument("--max-frames", type=int, default=None)
+ap.add_argument("--voxel", type=float, default=None, help="thin the map to one point per cell of this size (metres)")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file")
 args = ap.parse_args()
 
@@ -43,6 +46,19 @@ for k, (now_to_previous, st) in enumerate(zip(poses, status)):
         traj.accumulate(now_to_previous, float(k + 1))
     camera_to_world.append(traj.current_camera_to_world())
 world_map = DevicePointCloud.merge(clouds, camera_to_world)  # the last step: all frames in one coordinate system
+if args.voxel:
+    full = world_map
+    world_map = full.voxel_downsample(args.voxel)
+    print(f"voxel {args.voxel}: {full.len()} points -> {world_map.len()}")
+    full.free()
+    # frame to map: the last frame, brought to the world by its odometry pose, against the thinned map; what Icp
+    # returns is the correction the map asks of that pose
+    last = camera_to_world[-1] * clouds[-1]
+    icp = Icp(ctx, IcpParams.default(), world_map)
+    correction = icp.align(last)
+    print(f"last frame against the thinned map: correction angle {correction.angle():.3e} rad, "
+          f"translation {float(np.linalg.norm(correction.t)):.3e}")
+    icp.free(), last.free()
 points, _ = world_map.download()
 finite = points[np.isfinite(points).all(axis=1)]
 print(f"{len(clouds)} frames, map of {world_map.len()} points" + (" with normals" if world_map.d_normals is not None else ""))

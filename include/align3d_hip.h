@@ -507,6 +507,34 @@ a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud
                                          const a3d_pose* poses_host, uint64_t n, float* d_out_points, float* d_out_normals,
                                          uint64_t capacity, uint64_t* out_len);
 
+/* Voxel-grid downsampling of n resident clouds, each exactly as if it were passed alone, in a number of launches that
+ * does not depend on n; host-synchronous like the two entries above.  Of the points of a cloud that share a cell of the
+ * grid of pitch voxel_size anchored at origin (NULL = (0,0,0)), the one nearest to the cell's centre is kept (ties: the
+ * lowest index); the kept points are written in input order and copied bit for bit, normals too.  The rule of
+ * src/range_image/resize.rs:4-40 (one real sample per cell, never an average) with the cell centre in place of the cell
+ * mean, which makes the result independent of the order of the points.  In f32, every operation rounded on its own:
+ *   c_k = floorf((p_k - o_k) / v); the point is DROPPED unless every c_k is finite and in [-2^20, 2^20) (so NaN and
+ *   infinite coordinates never reach a kd-tree build); cell key (c_x + 2^20) << 42 | (c_y + 2^20) << 21 | (c_z + 2^20);
+ *   ctr_k = (c_k + 0.5f) * v + o_k, d_k = p_k - ctr_k, dist = (d_x * d_x + d_y * d_y) + d_z * d_z;
+ *   the winner of a key minimises bits(dist) << 32 | index.
+ * d_out_points[i]: room for capacities[i] points; d_out_normals (NULL, or NULL entries: no normals written; a non-NULL
+ * entry while clouds[i].normals is NULL -> A3D_MISSING_FIELD); d_out_index (NULL, or NULL entries): the input index of
+ * each kept point, capacities[i] u32.  out_lens[i] = kept points, out_dropped[i] (NULL ok) = dropped points of cloud i.
+ * capacities[i] >= len_i always suffices; if any cloud's result does not fit the call returns A3D_INVALID_PARAMETER with
+ * every count in out_lens (and out_dropped) and NOTHING written to any output.
+ * Decided on the host before anything is launched (nothing is touched): n == 0 is A3D_OK; a NULL ctx, d_clouds,
+ * d_out_points, capacities or out_lens, a voxel_size that is not finite or <= 0, a non-finite origin, a cloud of 2^32
+ * points or more (or within one tile, < 2^21 points, of it), any overlap of an output (its first min(len_i,
+ * capacities[i]) elements) with an input or another output — there is no in-place form — are A3D_INVALID_PARAMETER.  A
+ * cloud with len == 0 may have null pointers and yields out_lens[i] = 0.
+ * Scratch memory (context-owned, grow-only, shared with the calls above): 16 bytes per slot of each cloud's hash table,
+ * whose slot count is the smallest power of two >= 2 * len_i (so 32 to 64 bytes per point), plus len_i / 8 bytes of
+ * flags, 4 bytes per 1024 points and 88 bytes per cloud. */
+a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
+                                                    float voxel_size, const float origin[3], float* const* d_out_points,
+                                                    float* const* d_out_normals, uint32_t* const* d_out_index,
+                                                    const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped);
+
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
 /* R3dTree::new(&points): `points` [n][3] f32 in host memory are uploaded and the tree is built ON THE DEVICE
