@@ -1026,7 +1026,7 @@ a3d_status bilateral_filter_device(a3d_context* ctx, const uint16_t* d_img, uint
     g.gd = (uint32_t)((double)(cmax - cmin) / sigma_color) + 1 + 4;
     if (out_grid_dims) out_grid_dims[0] = g.gh, out_grid_dims[1] = g.gw, out_grid_dims[2] = g.gd;
     const size_t cells = (size_t)g.gh * g.gw * g.gd;
-    const size_t grid_bytes = ((cells * sizeof(double2) + 255) / 256) * 256;
+    const size_t grid_bytes = pad256(cells * sizeof(double2));
     // images below 2^24 pixels: packed integer splat + all six blur passes in one LDS-tiled kernel
     const char* mode = A3D_DIAG_ENV("A3D_BILATERAL");  // diagnostics build: force the pass-per-launch path
     // (and grids whose cells 32-bit offsets can address: the fused kernels index them so)
@@ -1141,18 +1141,17 @@ a3d_status bilateral_grids_enqueue(a3d_context* ctx, const uint16_t* d_depth, ui
   const unsigned long long plane_tiles = (unsigned long long)((gh + BT - 1) / BT) * ((gw + BT - 1) / BT);
   const unsigned long long max_gd = capacity / ((unsigned long long)gh * gw) + 1;
   const uint32_t tiles = (uint32_t)std::min<unsigned long long>(plane_tiles * ((max_gd + BT - 1) / BT), 1u << 30);
-  const uint32_t flags_stride = ((tiles + 255) / 256) * 256;
+  const uint32_t flags_stride = (uint32_t)pad256(tiles);  // one flag byte per tile
   const uint32_t columns = (gh - 3) * (gw - 3);  // the (row, column)s of the grid pixels can splat into
   constexpr uint32_t PARTIALS = 64;              // min / max blocks per frame
   // [scalars][min / max partials][tile flags][tile lists][colour -> channel tables][splat extents][packed][blurred]
-  auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
-  const size_t scal_only = pad((size_t)lf * SC_STRIDE * 4);
-  const size_t partial_bytes = pad((size_t)lf * PARTIALS * 2 * 4);
+  const size_t scal_only = pad256((size_t)lf * SC_STRIDE * 4);
+  const size_t partial_bytes = pad256((size_t)lf * PARTIALS * 2 * 4);
   const size_t flag_bytes = (size_t)lf * flags_stride;
   const bool lists_in_blur = flags_stride <= BLUR_LIST_MAX;
   const size_t list_bytes = lists_in_blur ? 0 : (size_t)lf * 2 * flags_stride * 4;  // the two tile lists
   const size_t table_bytes = (size_t)lf * 65536 * 4;
-  const size_t extent_bytes = pad((size_t)lf * columns * sizeof(uint2));
+  const size_t extent_bytes = pad256((size_t)lf * columns * sizeof(uint2));
   const size_t head_bytes = scal_only + partial_bytes + flag_bytes + list_bytes + table_bytes + extent_bytes;
   capacity = (capacity + 3) & ~3ull;  // a multiple of four cells: every frame's packed grid starts 16-byte aligned
   // at most floor(sigma) + 1 image rows (columns) round to one grid row (column): 4-byte cells while a (row, column)
@@ -1161,7 +1160,7 @@ a3d_status bilateral_grids_enqueue(a3d_context* ctx, const uint16_t* d_depth, ui
   const char* cells_mode = A3D_DIAG_ENV("A3D_BILATERAL_CELLS");
   const bool narrow = reach * reach <= 255 && !(cells_mode && !strcmp(cells_mode, "wide"));
   const uint32_t cell_bytes = narrow ? 4 : 8;
-  const size_t packed_bytes = pad((size_t)lf * capacity * cell_bytes);
+  const size_t packed_bytes = pad256((size_t)lf * capacity * cell_bytes);
   void* region = nullptr;
   A3D_TRY(ctx_scratch(ctx, 1, head_bytes + packed_bytes + (size_t)lf * capacity * 8 + 256, &region));
   out->scal = (uint32_t*)region;
@@ -1253,7 +1252,7 @@ extern "C" a3d_status a3d_bilateral_filter_u16(a3d_context* ctx, const uint16_t*
   hipStream_t s = ctx->stream;
   const uint32_t w = (uint32_t)width, h = (uint32_t)height, n = w * h;
   // image and result staged in the context's grow-only scratch region (no hipMalloc / hipFree per call)
-  const size_t stride = (((size_t)n * 2 + 255) / 256) * 256;
+  const size_t stride = pad256((size_t)n * 2);
   void* region = nullptr;
   A3D_TRY(ctx_scratch(ctx, 0, 2 * stride, &region));
   uint16_t *d_img = (uint16_t*)region, *d_out = (uint16_t*)((char*)region + stride);

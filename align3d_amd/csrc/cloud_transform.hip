@@ -5,17 +5,15 @@
 // the reference's f32 bit for bit (no contraction).  A job without a pose copies verbatim: no arithmetic, so NaN
 // payloads, -0 and infinities survive.
 //
-// One launch over every tile of every cloud of a batch (the shape of pointcloud.hip): a job table in the context's
-// scratch region 3, blocks map to tiles, a block-uniform search over first_tile finds the block's job.  A tile is
+// One launch over every tile of every cloud of a batch (the job table of cloud_batch.hpp).  A tile is
 // XF_THREADS * PPT consecutive points; in round r thread t takes point tile_base + r * XF_THREADS + t, so a wave touches
 // one contiguous 768-byte span per array per round.  A thread loads every point (and normal) of its tile before it
 // stores any, which puts PPT (2 PPT) independent 12-byte loads in flight per thread and makes an output that is exactly
 // its input safe.  A pure streaming pass: no LDS, no atomics, no block waits on another block; 24 B read and 24 B written
 // per point with normals against ~60 flops: the bound is HBM bandwidth.
-#include <algorithm>
 #include <vector>
 
-#include "common.hpp"
+#include "cloud_batch.hpp"
 
 using namespace a3d;
 
@@ -37,22 +35,9 @@ struct XformJob {
 };
 static_assert(sizeof(XformJob) == 80, "XformJob layout");
 
-typedef float xf32x3 __attribute__((ext_vector_type(3)));
-typedef xf32x3 __attribute__((aligned(4))) xf32x3_u;
 // The arrays' pointers come out of the job table, where the compiler only knows them as generic addresses (flat_load /
 // flat_store); they are device memory, and saying so gives global_load_dwordx3 / global_store_dwordx3.
 #define XF_GLOBAL __attribute__((address_space(1)))
-
-// The job whose tiles hold `tile` (jobs are in tile order and none is empty; the search is uniform over the block).
-__device__ __forceinline__ uint32_t find_job(const XformJob* __restrict__ jobs, uint32_t n_jobs, uint32_t tile) {
-  uint32_t lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].first_tile <= tile) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 // (no __restrict__ on the arrays: an output may be exactly its input; every load of a thread precedes its stores)
 template <uint32_t PPT>
@@ -65,14 +50,14 @@ __global__ void __launch_bounds__(XF_THREADS) cloud_transform_kernel(const Xform
   XF_GLOBAL float* out_normals = (XF_GLOBAL float*)j.out_normals;
   const uint32_t len = j.len;
   const uint32_t k0 = (tile - j.first_tile) * (XF_THREADS * PPT) + threadIdx.x;
-  xf32x3 p[PPT], n[PPT];
+  f32x3 p[PPT], n[PPT];
 #pragma unroll
   for (uint32_t r = 0; r < PPT; ++r) {
     const uint32_t k = k0 + r * XF_THREADS;
-    p[r] = n[r] = xf32x3{0.f, 0.f, 0.f};
+    p[r] = n[r] = f32x3{0.f, 0.f, 0.f};
     if (k < len) {
-      p[r] = *(const XF_GLOBAL xf32x3_u*)(points + 3 * (size_t)k);
-      if (out_normals) n[r] = *(const XF_GLOBAL xf32x3_u*)(normals + 3 * (size_t)k);
+      p[r] = *(const XF_GLOBAL f32x3_u*)(points + 3 * (size_t)k);
+      if (out_normals) n[r] = *(const XF_GLOBAL f32x3_u*)(normals + 3 * (size_t)k);
     }
   }
   if (j.has_pose) {
@@ -80,10 +65,10 @@ __global__ void __launch_bounds__(XF_THREADS) cloud_transform_kernel(const Xform
 #pragma unroll
     for (uint32_t r = 0; r < PPT; ++r) {
       const V3 v = transform_vector(pose, V3{p[r].x, p[r].y, p[r].z});
-      p[r] = xf32x3{v.x, v.y, v.z};
+      p[r] = f32x3{v.x, v.y, v.z};
       if (out_normals) {
         const V3 w = transform_normal(pose, V3{n[r].x, n[r].y, n[r].z});
-        n[r] = xf32x3{w.x, w.y, w.z};
+        n[r] = f32x3{w.x, w.y, w.z};
       }
     }
   }
@@ -91,8 +76,8 @@ __global__ void __launch_bounds__(XF_THREADS) cloud_transform_kernel(const Xform
   for (uint32_t r = 0; r < PPT; ++r) {
     const uint32_t k = k0 + r * XF_THREADS;
     if (k < len) {
-      *(XF_GLOBAL xf32x3_u*)(out_points + 3 * (size_t)k) = p[r];
-      if (out_normals) *(XF_GLOBAL xf32x3_u*)(out_normals + 3 * (size_t)k) = n[r];
+      *(XF_GLOBAL f32x3_u*)(out_points + 3 * (size_t)k) = p[r];
+      if (out_normals) *(XF_GLOBAL f32x3_u*)(out_normals + 3 * (size_t)k) = n[r];
     }
   }
 }
@@ -102,23 +87,6 @@ uint32_t points_per_thread_setting() {
   if (const char* env = A3D_DIAG_ENV("A3D_CLOUD_TRANSFORM_PPT"))  // diagnostics build: the variants the probe times
     if (*env) v = (uint32_t)atoi(env);
   return v == 1 || v == 2 || v == 4 ? v : XF_PPT;
-}
-
-struct ByteRange {
-  uintptr_t begin, end;
-  bool output;
-};
-
-// Whether any output range overlaps any other range (inputs may overlap inputs).
-bool outputs_overlap(std::vector<ByteRange>& ranges) {
-  std::sort(ranges.begin(), ranges.end(), [](const ByteRange& a, const ByteRange& b) { return a.begin < b.begin; });
-  uintptr_t end_any = 0, end_out = 0;  // furthest end among the ranges / the output ranges seen so far
-  for (const ByteRange& r : ranges) {
-    if (r.begin < (r.output ? end_any : end_out)) return true;
-    end_any = std::max(end_any, r.end);
-    if (r.output) end_out = std::max(end_out, r.end);
-  }
-  return false;
 }
 
 // Uploads the job table and runs the one launch; complete on return.

@@ -64,6 +64,9 @@ inline void pose_to_c(const Pose& p, a3d_pose* o) {
   o->q[0] = p.q.i, o->q[1] = p.q.j, o->q[2] = p.q.k, o->q[3] = p.q.w;
 }
 
+// Bytes rounded up to the 256-byte granule every part of a device region is aligned to.
+inline size_t pad256(size_t bytes) { return ((bytes + 255) / 256) * 256; }
+
 // Largest f32 d in [-1, 1] with  acosf(d) >= thr  (strict = false)  or  acosf(d) > thr  (strict =
 // true), found by bisection over the f32 ordering with the host libm (the libm the reference's
 // f32::acos resolves to).  Returns -2.0f when no d qualifies.  The kernels then test
@@ -95,9 +98,11 @@ struct a3d_context {
   int num_cus = 0;
   // Grow-only scratch regions for per-call temporaries (all work on a context is ordered on its one stream,
   // so successive calls may reuse them): [0] frame builder temporaries, [1] bilateral grids, [2] kd-tree build,
-  // [3] range image -> point cloud conversion (its per-image table and tile counts, pointcloud.hip) and the job table of the
-  // cloud transform / merge (cloud_transform.hip; both calls are host-synchronous), [4] the per-image,
-  // per-level pointer table of a3d_range_image_pyramids / a3d_range_image_compute_intensity (pyramid.hip).
+  // [3] the batched cloud operations, each host-synchronous: range image -> point cloud conversion (job table, lengths,
+  // tile counts: pointcloud.hip), voxel-grid downsample (the same plus its ballot words and hash tables:
+  // voxel_downsample.hip; both laid out by cloud_batch.hpp) and the bare job table of the cloud transform / merge
+  // (cloud_transform.hip), [4] the per-image, per-level pointer table of a3d_range_image_pyramids /
+  // a3d_range_image_compute_intensity (pyramid.hip).
   void* scratch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t scratch_size[5] = {0, 0, 0, 0, 0};
   // Device blocks handed back by freed kd-trees / Icp objects (ctx_block_release), kept for the next one of about the

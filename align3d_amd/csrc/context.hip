@@ -184,7 +184,7 @@ a3d_status ctx_arena_acquire(a3d_context* ctx, size_t bytes, DeviceArena* out) {
     const char* v = getenv("A3D_ARENA_SLAB_MB");
     return (size_t)(v ? std::max(0, atoi(v)) : 512) << 20;
   }();
-  const size_t padded = ((bytes + 255) / 256) * 256;
+  const size_t padded = pad256(bytes);
   std::lock_guard<std::mutex> lock(ctx->pool_mutex);
   A3D_REQUIRE(!ctx->zombie, A3D_INVALID_PARAMETER, "this context has been destroyed");
   for (size_t i = 0; i < ctx->arena_pool.size(); ++i) {

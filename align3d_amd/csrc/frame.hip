@@ -541,7 +541,7 @@ __global__ void __launch_bounds__(256)
 }
 
 
-inline size_t padded(size_t bytes) { return ((std::max<size_t>(1, bytes) + 255) / 256) * 256; }
+inline size_t padded(size_t bytes) { return pad256(std::max<size_t>(1, bytes)); }
 
 // Where each array of each level lives inside a frame's arena (256-byte aligned pieces, same for every frame).
 struct ArenaPlan {

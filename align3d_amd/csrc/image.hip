@@ -179,7 +179,7 @@ a3d_status upload_pyramid(a3d_context* ctx, const a3d_range_image_view* views, u
   size_t total = 0;
   auto take = [&](size_t bytes) {
     const size_t at = total;
-    total += ((bytes + 255) / 256) * 256;
+    total += pad256(bytes);
     return at;
   };
   struct Offsets {

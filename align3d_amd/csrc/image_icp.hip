@@ -1447,7 +1447,7 @@ a3d_status batch_create(a3d_context* ctx, const a3d_icp_params* params, uint32_t
     size_t total = 0;
     auto take = [&](size_t bytes) {
       const size_t at = total;
-      total += ((bytes + 255) / 256) * 256;
+      total += pad256(bytes);
       return at;
     };
     const size_t o_descs = take(b->h_descs.size() * sizeof(LevelDesc)), o_states = take(2 * n_pairs * sizeof(JobState)),

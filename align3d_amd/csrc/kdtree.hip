@@ -459,9 +459,8 @@ static a3d_status pcl_icp_new_impl(a3d_context* ctx, const a3d_icp_params* param
   icp->launch = kd_launch_config(t, 1ull << 31, "A3D_PCL", 1024, 15, 1);
   icp->blocks = icp->launch.blocks;
   if (st == A3D_OK) {  // the object's device state: one block of the context's (no hipMalloc once a previous Icp was freed)
-    auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
-    const size_t state_b = pad(2 * sizeof(JobState)), part_b = pad(2 * (size_t)icp->blocks * GN_PARTIAL * sizeof(float)),
-                 pose_b = 256, read_b = pad(GN_PARTIAL * sizeof(double)), count_b = 256;
+    const size_t state_b = pad256(2 * sizeof(JobState)), part_b = pad256(2 * (size_t)icp->blocks * GN_PARTIAL * sizeof(float)),
+                 pose_b = 256, read_b = pad256(GN_PARTIAL * sizeof(double)), count_b = 256;
     char* blk = nullptr;
     st = ctx_block_alloc(ctx, state_b + part_b + pose_b + read_b + count_b, (void**)&blk, &icp->block_bytes);
     if (st == A3D_OK) {
@@ -508,7 +507,7 @@ static a3d_status pcl_upload_source(a3d_pcl_icp* icp, const a3d_point_cloud_view
     *d_nrm = const_cast<float*>(source->normals);
     return A3D_OK;
   }
-  const size_t bytes = source->len * 12, stride = ((bytes + 255) / 256) * 256;
+  const size_t bytes = source->len * 12, stride = pad256(bytes);
   void* region = nullptr;
   A3D_TRY(ctx_scratch(icp->ctx, 2, 2 * stride, &region));
   *d_pts = (float*)region;

@@ -166,7 +166,6 @@ namespace a3d {
 // d_points: [n][3] on the device.  Fills t->d_split, t->d_leaves, t->d_slot_of_point (all device).
 // Bytes of temporaries kdtree_build_device needs for n points (behind the staged points, see a3d_kdtree_new).
 size_t kdtree_build_scratch_bytes(uint32_t n, uint32_t max_depth, hipStream_t s) {
-  auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
   size_t sorted = 0;
 #ifdef A3D_DIAGNOSTICS  // the sorting build's temporaries share the region with the selection build's: the larger of the two
   const size_t max_nodes = max_depth ? (1ull << (max_depth - 1)) : 1;
@@ -179,16 +178,15 @@ size_t kdtree_build_scratch_bytes(uint32_t n, uint32_t max_depth, hipStream_t s)
                                     (uint32_t*)nullptr, n, 0, 64, s);
     sort_bytes = std::max(sort_bytes, wide_bytes);
   }
-  sorted = 2 * pad((size_t)n * 4) + 2 * pad((size_t)n * 8) + 2 * pad(max_nodes * 4) + 256 + pad(sort_bytes) +
-           pad(kdtree_sort_scratch_bytes(n));
+  sorted = 2 * pad256((size_t)n * 4) + 2 * pad256((size_t)n * 8) + 2 * pad256(max_nodes * 4) + 256 + pad256(sort_bytes) +
+           pad256(kdtree_sort_scratch_bytes(n));
 #else
   (void)max_depth, (void)s;
 #endif
-  return std::max(sorted, pad(kdtree_select_scratch_bytes(n))) + pad((size_t)n * 12);
+  return std::max(sorted, pad256(kdtree_select_scratch_bytes(n))) + pad256((size_t)n * 12);
 }
 
 size_t kdtree_arrays_bytes(uint32_t n, uint32_t max_depth) {
-  auto pad256 = [](size_t b) { return ((b + 255) / 256) * 256; };
   return pad256((1ull << max_depth) * 16 * sizeof(float4)) + pad256(std::max<size_t>(1, ((size_t)1 << max_depth) - 1) * 4) +
          pad256((size_t)n * sizeof(uint32_t));
 }
@@ -196,7 +194,6 @@ size_t kdtree_arrays_bytes(uint32_t n, uint32_t max_depth) {
 // The tree's three arrays in ONE allocation (hipMalloc synchronises the device): leaves first (16-byte records).
 static a3d_status kdtree_alloc_arrays(a3d_kdtree* t, void* arrays) {
   const uint64_t n_slots = (1ull << t->max_depth) * 16;
-  auto pad256 = [](size_t b) { return ((b + 255) / 256) * 256; };
   const size_t leaves_b = pad256(n_slots * sizeof(float4)), split_b = pad256(std::max<size_t>(1, (size_t)t->n_split) * 4);
   char* block = (char*)arrays;
   if (!block) {
@@ -226,9 +223,8 @@ a3d_status kdtree_build_device(a3d_kdtree* t, const float* d_points, void* array
   }
 #endif
   t->built_by = 1;  // (3 once the context's builds add the wide placement launches: kdtree_build_device_select)
-  auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
-  char* scratch = (char*)t->ctx->scratch[2] + pad((size_t)t->n * 12);  // behind the points the caller may have staged there
-  A3D_REQUIRE(t->ctx->scratch[2] && t->ctx->scratch_size[2] >= pad((size_t)t->n * 12) + kdtree_select_scratch_bytes(t->n),
+  char* scratch = (char*)t->ctx->scratch[2] + pad256((size_t)t->n * 12);  // behind the points the caller may have staged there
+  A3D_REQUIRE(t->ctx->scratch[2] && t->ctx->scratch_size[2] >= pad256((size_t)t->n * 12) + kdtree_select_scratch_bytes(t->n),
               A3D_INVALID_PARAMETER, "internal: kd-tree scratch region too small");
   // instrumentation (a3d_kdtree_build_ms): the build's launches between two events on the stream
   hipEvent_t e0 = t->ctx->kd_ev[0], e1 = t->ctx->kd_ev[1];  // (the context's: an event made and destroyed per build cost ~10 us)
@@ -275,23 +271,22 @@ static a3d_status kdtree_build_device_sorted(a3d_kdtree* t, const float* d_point
     sort_bytes = std::max(sort_bytes, wide_bytes);
   }
 #endif
-  auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
-  const size_t hist_bytes = pad(kdtree_sort_scratch_bytes(n));
-  const size_t total = 2 * pad((size_t)n * 4) + 2 * pad((size_t)n * 8) + 2 * pad(max_nodes * 4) + 256 +
-                       pad(sort_bytes) + hist_bytes;
+  const size_t hist_bytes = pad256(kdtree_sort_scratch_bytes(n));
+  const size_t total = 2 * pad256((size_t)n * 4) + 2 * pad256((size_t)n * 8) + 2 * pad256(max_nodes * 4) + 256 +
+                       pad256(sort_bytes) + hist_bytes;
   // temporaries live in the context's grow-only kd-tree scratch region, BEHIND the points the caller staged there
-  char* base = (char*)ctx->scratch[2] + pad((size_t)n * 12);
-  A3D_REQUIRE(ctx->scratch[2] && ctx->scratch_size[2] >= pad((size_t)n * 12) + total, A3D_INVALID_PARAMETER,
+  char* base = (char*)ctx->scratch[2] + pad256((size_t)n * 12);
+  A3D_REQUIRE(ctx->scratch[2] && ctx->scratch_size[2] >= pad256((size_t)n * 12) + total, A3D_INVALID_PARAMETER,
               "internal: kd-tree scratch region too small");
   uint32_t* idx_a = (uint32_t*)base;
-  uint32_t* idx_b = (uint32_t*)(base + pad((size_t)n * 4));
-  char* keys_a = base + 2 * pad((size_t)n * 4);
-  char* keys_b = keys_a + pad((size_t)n * 8);
-  uint32_t* begin = (uint32_t*)(keys_b + pad((size_t)n * 8));
-  uint32_t* end = (uint32_t*)((char*)begin + pad(max_nodes * 4));
-  uint32_t* nan_flag = (uint32_t*)((char*)end + pad(max_nodes * 4));
+  uint32_t* idx_b = (uint32_t*)(base + pad256((size_t)n * 4));
+  char* keys_a = base + 2 * pad256((size_t)n * 4);
+  char* keys_b = keys_a + pad256((size_t)n * 8);
+  uint32_t* begin = (uint32_t*)(keys_b + pad256((size_t)n * 8));
+  uint32_t* end = (uint32_t*)((char*)begin + pad256(max_nodes * 4));
+  uint32_t* nan_flag = (uint32_t*)((char*)end + pad256(max_nodes * 4));
   void* sort_tmp = (char*)nan_flag + 256;
-  uint32_t* hist = (uint32_t*)((char*)sort_tmp + pad(sort_bytes));
+  uint32_t* hist = (uint32_t*)((char*)sort_tmp + pad256(sort_bytes));
 
   A3D_HIP_TRY(hipMemsetAsync(nan_flag, 0, 4, s));
   hipLaunchKernelGGL(iota_kernel, grid_for(n), dim3(256), 0, s, idx_a, n);

@@ -1991,23 +1991,22 @@ SelLayout sel_layout(uint32_t n, uint32_t narrow_len, uint32_t wide_cap) {
     L.nb[d] = nb;
     hist_words = std::max(hist_words, ((size_t)1 << d) * nb);
   }
-  auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
   const size_t nodes = (size_t)1 << L.wide_levels;  // heap-indexed tables over all wide levels: 2^levels - 1 entries
   L.pack_blocks = (n + PACK_TILE - 1) / PACK_TILE;
   size_t off = 0;
-  L.recs_a = off, off += pad((size_t)n * 16);
-  L.recs_b = off, off += pad((size_t)n * 16);
-  L.mid = off, off += pad((size_t)n * 16);
-  L.boxes = off, off += pad(nodes * sizeof(SelBox));
-  L.plans = off, off += pad(nodes * sizeof(SelPlan));
-  L.partials = off, off += pad((size_t)L.pack_blocks * 6 * sizeof(float));
+  L.recs_a = off, off += pad256((size_t)n * 16);
+  L.recs_b = off, off += pad256((size_t)n * 16);
+  L.mid = off, off += pad256((size_t)n * 16);
+  L.boxes = off, off += pad256(nodes * sizeof(SelBox));
+  L.plans = off, off += pad256(nodes * sizeof(SelPlan));
+  L.partials = off, off += pad256((size_t)L.pack_blocks * 6 * sizeof(float));
   L.zero_begin = off;
   L.flags = off, off += 256;
-  L.cursors = off, off += pad(nodes * 4 * CURSOR_STRIDE * sizeof(uint32_t));
+  L.cursors = off, off += pad256(nodes * 4 * CURSOR_STRIDE * sizeof(uint32_t));
   L.hist_words = hist_words;
-  L.hist = off, off += pad(2 * hist_words * sizeof(uint32_t));
-  L.wide = off, off += pad(((size_t)1 << L.place_levels) * sizeof(SelWide));  // heap-indexed over the levels that can hold one
-  L.whist = off, off += pad(((size_t)1 << (L.place_levels ? L.place_levels - 1 : 0)) * 2 * NSUB * sizeof(uint32_t));  // per node of a level
+  L.hist = off, off += pad256(2 * hist_words * sizeof(uint32_t));
+  L.wide = off, off += pad256(((size_t)1 << L.place_levels) * sizeof(SelWide));  // heap-indexed over the levels that can hold one
+  L.whist = off, off += pad256(((size_t)1 << (L.place_levels ? L.place_levels - 1 : 0)) * 2 * NSUB * sizeof(uint32_t));  // per node of a level
   L.zero_bytes = off - L.zero_begin;
   L.total = off;
   return L;

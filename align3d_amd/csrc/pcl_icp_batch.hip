@@ -70,8 +70,6 @@ struct PairTree {
   uint32_t n, max_depth;
 };
 
-size_t pad256(size_t b) { return ((b + 255) / 256) * 256; }
-
 }  // namespace
 
 struct a3d_pcl_icp_batch {

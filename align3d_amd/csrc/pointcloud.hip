@@ -3,18 +3,16 @@
 // row-major order, points and normals are copied verbatim (no arithmetic: NaN payloads, -0 and inf survive), and an image
 // without normals gives a cloud without normals (the reference's Option, structure.rs:384-390).
 //
-// Two launches over every tile of every image of a batch, no block waiting on another block:
-//  1. cloud_count_kernel: each block counts the kept pixels of its tile (reads the mask only) and adds them to its image's
-//     total;
-//  2. cloud_write_kernel: each block sums its image's earlier tile counts (a few hundred L2-resident words) for its
-//     offset, ranks its own pixels with a 64-bit ballot and mbcnt plus a scan of the per-wave counts in LDS, and writes
-//     [len][3] f32 with 12-byte vector stores.
-// A tile is one or more chunks of 2048 pixels (8 rounds of 256): at most CLOUD_MAX_TILES tiles per image, so the offset
-// sum of a block stays short whatever the image size.
-#include <algorithm>
+// Two launches over every tile of every image of a batch (the job table of cloud_batch.hpp), no block waiting on another:
+//  1. cloud_count_kernel: each block counts the kept pixels of its tile (reads the mask only) and adds them to its
+//     image's total;
+//  2. cloud_write_kernel: each block sums its image's earlier tile counts for its offset, ranks its own pixels with a
+//     64-bit ballot and mbcnt plus a scan of the per-wave counts in LDS, and writes [len][3] f32 with 12-byte vector
+//     stores.
+// A tile is one or more chunks of 2048 pixels (8 rounds of 256), at most CLOUD_MAX_TILES tiles per image.
 #include <vector>
 
-#include "common.hpp"
+#include "cloud_batch.hpp"
 
 using namespace a3d;
 
@@ -38,30 +36,6 @@ struct CloudJob {
   uint32_t npx, width, first_tile, n_tiles, chunks_per_tile, pad;
   float bp_fx, bp_fy, bp_cx, bp_cy, depth_scale, pad2;
 };
-
-typedef float cf32x3 __attribute__((ext_vector_type(3)));
-typedef cf32x3 __attribute__((aligned(4))) cf32x3_u;
-
-// The job whose tiles hold `tile` (jobs are in tile order; the search is uniform over the block).
-__device__ __forceinline__ uint32_t find_job(const CloudJob* __restrict__ jobs, uint32_t n_jobs, uint32_t tile) {
-  uint32_t lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].first_tile <= tile) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t lane_rank(uint64_t ballot) {  // kept lanes below this one
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
 
 // Pass 1: tile_counts[tile] = kept pixels of the tile; lens[image] += the same (lens zeroed by the host upload).
 __global__ void __launch_bounds__(CLOUD_THREADS)
@@ -157,17 +131,17 @@ __global__ void __launch_bounds__(CLOUD_THREADS)
       const uint32_t p = px0 + r * CLOUD_THREADS + threadIdx.x;
       const uint64_t dst = (uint64_t)off[r] + lane_rank(ballot[r]);
       if (dst >= capacity) continue;  // (cannot happen: the image's total fits; kept as a bound on every store)
-      cf32x3 pt;
+      f32x3 pt;
       if (depth16) {
         const uint32_t row = p / width, col = p - row * width;
         const V3 v = backproject_px(depth[r], (int)row, (int)col, j.bp_fx, j.bp_fy, j.bp_cx, j.bp_cy, j.depth_scale, dfx,
                                     dfy, focal_ok);
-        pt = cf32x3{v.x, v.y, v.z};
+        pt = f32x3{v.x, v.y, v.z};
       } else {
-        pt = *(const cf32x3_u*)(points + 3 * (size_t)p);
+        pt = *(const f32x3_u*)(points + 3 * (size_t)p);
       }
-      *(cf32x3_u*)(out_points + 3 * dst) = pt;
-      if (out_normals) *(cf32x3_u*)(out_normals + 3 * dst) = *(const cf32x3_u*)(normals + 3 * (size_t)p);
+      *(f32x3_u*)(out_points + 3 * dst) = pt;
+      if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)p);
     }
   }
 }
@@ -204,29 +178,21 @@ a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images
     j.out_points = d_points[i], j.out_normals = out_normals;
     j.capacity = capacities[i];
     j.npx = (uint32_t)npx, j.width = im->width;
-    const uint64_t chunks = (npx + CLOUD_CHUNK - 1) / CLOUD_CHUNK;
-    j.chunks_per_tile = (uint32_t)((chunks + CLOUD_MAX_TILES - 1) / CLOUD_MAX_TILES);
-    j.n_tiles = (uint32_t)((chunks + j.chunks_per_tile - 1) / j.chunks_per_tile);
-    j.first_tile = (uint32_t)tiles;
-    tiles += j.n_tiles;
-    A3D_REQUIRE(tiles < (1ull << 31), A3D_INVALID_PARAMETER, "batch too large");
+    A3D_TRY(plan_tiles(npx, CLOUD_CHUNK, CLOUD_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
+    j.n_tiles = (uint32_t)tiles - j.first_tile;
     if (im->points_from_depth && im->depth16) {  // (builder level 0: 2 bytes of depth instead of 1 + 12 of mask + point)
       j.depth16 = im->depth16;
       j.bp_fx = im->bp_fx, j.bp_fy = im->bp_fy, j.bp_cx = im->bp_cx, j.bp_cy = im->bp_cy, j.depth_scale = im->depth_scale;
     }
   }
   A3D_HIP_TRY(hipSetDevice(ctx->device));
-  // scratch: jobs | lens (zeroed by the same upload) | tile counts
-  const size_t jobs_bytes = ((n * sizeof(CloudJob) + 255) / 256) * 256, lens_bytes = ((n * 8 + 255) / 256) * 256;
-  void* region = nullptr;
-  A3D_TRY(ctx_scratch(ctx, 3, jobs_bytes + lens_bytes + tiles * 4, &region));
-  std::vector<char> staging(jobs_bytes + lens_bytes, 0);
-  memcpy(staging.data(), jobs.data(), n * sizeof(CloudJob));
-  const CloudJob* d_jobs = (const CloudJob*)region;
-  unsigned long long* d_lens = (unsigned long long*)((char*)region + jobs_bytes);
-  uint32_t* d_tile_counts = (uint32_t*)((char*)region + jobs_bytes + lens_bytes);
+  BatchScratch scratch;  // the words: one length per image
+  A3D_TRY(batch_scratch(ctx, n * sizeof(CloudJob), n, tiles, 0, &scratch));
+  const CloudJob* d_jobs = (const CloudJob*)scratch.jobs;
+  unsigned long long* d_lens = scratch.words;
+  uint32_t* d_tile_counts = scratch.tile_counts;
   hipStream_t s = ctx->stream;
-  A3D_HIP_TRY(hipMemcpyAsync(region, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
+  A3D_TRY(batch_upload(scratch, jobs.data(), s));
   hipLaunchKernelGGL(cloud_count_kernel, dim3((uint32_t)tiles), dim3(CLOUD_THREADS), 0, s, d_jobs, (uint32_t)n, d_tile_counts,
                      d_lens);
   A3D_HIP_TRY(hipGetLastError());

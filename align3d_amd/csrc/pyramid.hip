@@ -237,7 +237,7 @@ void adopt_intensity(a3d_device_image* im, uint8_t* inten, float* imap) {
   if (!im->has_imap) im->imap = imap, im->has_imap = true, im->own_imap = true;
 }
 
-inline size_t padded(size_t bytes) { return ((std::max<size_t>(1, bytes) + 255) / 256) * 256; }
+inline size_t padded(size_t bytes) { return pad256(std::max<size_t>(1, bytes)); }
 
 }  // namespace
 

@@ -10,9 +10,8 @@
 //   ctr_k = (c_k + 0.5f) * v + o_k,  d_k = p_k - ctr_k,  dist = (d_x * d_x + d_y * d_y) + d_z * d_z   (never NaN, may be +inf)
 //   the winner of a key minimises  bits(dist) << 32 | i   (dist >= 0: its bit pattern is monotone)
 //
-// Three launches over every tile of every cloud of a batch plus one fill of the hash tables, whatever the batch size (job
-// table in the context's scratch region 3, blocks find their cloud with a block-uniform search, as cloud_transform.hip and
-// pointcloud.hip do); no block waits on another block:
+// Three launches over every tile of every cloud of a batch plus one fill of the hash tables, whatever the batch size (the
+// job table of cloud_batch.hpp); no block waits on another block:
 //  1. voxel_insert_kernel: a thread per point claims the slot of its key in the cloud's open-addressing table (linear
 //     probing, 64-bit atomicCAS on the key word; at most half the slots can ever be taken) and atomicMins its word into
 //     the slot's second word.  Both are preceded by a device-scope load of the word: a slot that already holds the key
@@ -21,15 +20,14 @@
 //  2. voxel_flag_kernel: each point finds its key's slot again; it is the winner iff the slot's low 32 bits are its
 //     index.  A wave stores its 64-bit ballot (one bit per point: the whole flag array is len / 8 bytes) and the block
 //     its tile's winner count.
-//  3. voxel_compact_kernel: each block sums its cloud's earlier tile counts for its offset (pointcloud.hip's form: at most
-//     VX_MAX_TILES tiles per cloud), ranks its winners from the stored ballots and writes point, normal and index at
+//  3. voxel_compact_kernel: each block sums its cloud's earlier tile counts for its offset (cloud_write_kernel's form: at
+//     most VX_MAX_TILES tiles per cloud), ranks its winners from the stored ballots and writes point, normal and index at
 //     offset + rank: input order.  It writes nothing if any cloud of the batch has more winners than its capacity, so
 //     the host needs one wait, after everything, to read the counts back.
-#include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
+#include "cloud_batch.hpp"
 
 using namespace a3d;
 
@@ -70,31 +68,8 @@ struct VoxelGrid {
   float v, ox, oy, oz;
 };
 
-typedef float vf32x3 __attribute__((ext_vector_type(3)));
-typedef vf32x3 __attribute__((aligned(4))) vf32x3_u;
-
-__device__ __forceinline__ uint32_t find_job(const VoxelJob* __restrict__ jobs, uint32_t n_jobs, uint32_t tile) {
-  uint32_t lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].first_tile <= tile) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t lane_rank(uint64_t ballot) {  // set lanes below this one
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
 // The cell key of a point and (with_dist) its squared distance to the cell centre; false = the point is dropped.
-__device__ __forceinline__ bool voxel_key(const vf32x3 p, const VoxelGrid g, unsigned long long* key, float* dist) {
+__device__ __forceinline__ bool voxel_key(const f32x3 p, const VoxelGrid g, unsigned long long* key, float* dist) {
   const float cx = floorf((p.x - g.ox) / g.v), cy = floorf((p.y - g.oy) / g.v), cz = floorf((p.z - g.oz) / g.v);
   // (a NaN fails every comparison, an infinity the range)
   const bool ok = cx >= -VX_CELL_LIMIT && cx < VX_CELL_LIMIT && cy >= -VX_CELL_LIMIT && cy < VX_CELL_LIMIT &&
@@ -133,7 +108,7 @@ __global__ void __launch_bounds__(VX_THREADS)
   const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (len < 2^32 - span: checked by the host)
   uint32_t n_dropped = 0;
   for (uint32_t p = p0 + threadIdx.x; p < p_end; p += VX_THREADS) {
-    const vf32x3 pt = *(const vf32x3_u*)(points + 3 * (size_t)p);
+    const f32x3 pt = *(const f32x3_u*)(points + 3 * (size_t)p);
     unsigned long long key;
     float dist;
     if (!voxel_key(pt, grid, &key, &dist)) {
@@ -181,7 +156,7 @@ __global__ void __launch_bounds__(VX_THREADS)
     const uint32_t p = base + lane;
     bool win = false;
     unsigned long long key;
-    if (p < p_end && voxel_key(*(const vf32x3_u*)(points + 3 * (size_t)p), grid, &key, nullptr)) {
+    if (p < p_end && voxel_key(*(const f32x3_u*)(points + 3 * (size_t)p), grid, &key, nullptr)) {
       unsigned long long s = slot_hash(key) & mask;
       for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
         const unsigned long long k = table[s].key;
@@ -266,31 +241,12 @@ __global__ void __launch_bounds__(VX_THREADS)
       const uint32_t p = px0 + r * VX_THREADS + threadIdx.x;
       const unsigned long long dst = (unsigned long long)offs[r] + lane_rank(ballot);
       if (p >= p_end || dst >= capacity) continue;  // (cannot happen: the bit is a point's, the total fits; a bound on every store)
-      *(vf32x3_u*)(out_points + 3 * dst) = *(const vf32x3_u*)(points + 3 * (size_t)p);
-      if (out_normals) *(vf32x3_u*)(out_normals + 3 * dst) = *(const vf32x3_u*)(normals + 3 * (size_t)p);
+      *(f32x3_u*)(out_points + 3 * dst) = *(const f32x3_u*)(points + 3 * (size_t)p);
+      if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)p);
       if (out_index) out_index[dst] = p;
     }
   }
 }
-
-struct ByteRange {
-  uintptr_t begin, end;
-  bool output;
-};
-
-// Whether any output range overlaps any other range (inputs may overlap inputs).
-bool outputs_overlap(std::vector<ByteRange>& ranges) {
-  std::sort(ranges.begin(), ranges.end(), [](const ByteRange& a, const ByteRange& b) { return a.begin < b.begin; });
-  uintptr_t end_any = 0, end_out = 0;  // furthest end among the ranges / the output ranges seen so far
-  for (const ByteRange& r : ranges) {
-    if (r.begin < (r.output ? end_any : end_out)) return true;
-    end_any = std::max(end_any, r.end);
-    if (r.output) end_out = std::max(end_out, r.end);
-  }
-  return false;
-}
-
-size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -329,11 +285,7 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
     j.out_index = d_out_index ? d_out_index[i] : nullptr;
     j.capacity = capacities[i];
     j.len = (uint32_t)c.len;
-    const uint64_t chunks = (c.len + VX_CHUNK - 1) / VX_CHUNK;
-    j.chunks_per_tile = (uint32_t)((chunks + VX_MAX_TILES - 1) / VX_MAX_TILES);
-    j.first_tile = (uint32_t)tiles;
-    tiles += (chunks + j.chunks_per_tile - 1) / j.chunks_per_tile;
-    A3D_REQUIRE(tiles < (1ull << 31), A3D_INVALID_PARAMETER, "batch too large");
+    A3D_TRY(plan_tiles(c.len, VX_CHUNK, VX_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
     // the kernels' 32-bit point positions run up to one tile span past len
     A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * VX_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
                 "a3d_point_clouds_voxel_downsample_device: a cloud within one tile of 2^32 points");
@@ -341,7 +293,7 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
     while (slots < 2 * c.len) slots <<= 1;
     j.slot_mask = slots - 1;
     j.flags = (unsigned long long*)flag_bytes, j.table = (VoxelSlot*)table_bytes;
-    flag_bytes += round256((c.len + 63) / 64 * 8), table_bytes += slots * sizeof(VoxelSlot);
+    flag_bytes += pad256((c.len + 63) / 64 * 8), table_bytes += slots * sizeof(VoxelSlot);
     jobs.push_back(j), cloud_of_job.push_back(i);
     // what the call may write is the first min(len, capacity) elements of each output
     const uintptr_t in_bytes = (uintptr_t)c.len * 12, kept = (uintptr_t)std::min<uint64_t>(c.len, j.capacity);
@@ -362,27 +314,22 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
   if (jobs.empty()) return A3D_OK;
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
-  // scratch: jobs | lens, dropped, fault (zeroed by the same upload) | tile counts | ballot words | hash tables
-  const size_t jobs_bytes = round256(n_jobs * sizeof(VoxelJob)), words_bytes = round256((2 * n_jobs + 1) * 8),
-               counts_bytes = round256(tiles * 4);
-  const size_t flags_at = jobs_bytes + words_bytes + counts_bytes, tables_at = flags_at + flag_bytes;
-  void* region = nullptr;
-  A3D_TRY(ctx_scratch(ctx, 3, tables_at + table_bytes, &region));
-  char* base = (char*)region;
+  BatchScratch scratch;  // the words: lens, dropped, fault; the tail: ballot words | hash tables
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(VoxelJob), 2 * n_jobs + 1, tiles, flag_bytes + table_bytes, &scratch));
+  char* d_flags = scratch.tail;
+  char* d_tables = scratch.tail + flag_bytes;
   for (VoxelJob& j : jobs) {
-    j.flags = (unsigned long long*)(base + flags_at + (size_t)j.flags);
-    j.table = (VoxelSlot*)(base + tables_at + (size_t)j.table);
+    j.flags = (unsigned long long*)(d_flags + (size_t)j.flags);
+    j.table = (VoxelSlot*)(d_tables + (size_t)j.table);
   }
-  std::vector<char> staging(jobs_bytes + words_bytes, 0);
-  memcpy(staging.data(), jobs.data(), n_jobs * sizeof(VoxelJob));
-  const VoxelJob* d_jobs = (const VoxelJob*)base;
-  unsigned long long* d_lens = (unsigned long long*)(base + jobs_bytes);
+  const VoxelJob* d_jobs = (const VoxelJob*)scratch.jobs;
+  unsigned long long* d_lens = scratch.words;
   unsigned long long* d_dropped = d_lens + n_jobs;
   unsigned long long* d_fault = d_lens + 2 * n_jobs;
-  uint32_t* d_tile_counts = (uint32_t*)(base + jobs_bytes + words_bytes);
+  uint32_t* d_tile_counts = scratch.tile_counts;
   hipStream_t s = ctx->stream;
-  A3D_HIP_TRY(hipMemcpyAsync(region, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
-  A3D_HIP_TRY(hipMemsetAsync(base + tables_at, 0xFF, table_bytes, s));  // every key VX_EMPTY, every best word ~0
+  A3D_TRY(batch_upload(scratch, jobs.data(), s));
+  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0xFF, table_bytes, s));  // every key VX_EMPTY, every best word ~0
   const dim3 grid_dim((uint32_t)tiles), block(VX_THREADS);
   hipLaunchKernelGGL(voxel_insert_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, d_dropped, d_fault);
   A3D_HIP_TRY(hipGetLastError());

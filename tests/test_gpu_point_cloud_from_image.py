@@ -94,6 +94,17 @@ def test_bit_identity_with_host_path_on_uploaded_images(ctx):
     dev.free()
 
 
+def test_image_of_more_chunks_than_tiles(ctx):
+    # 4096 x 2049 pixels are 4098 chunks of 2048, above the 4096 tiles an image may have: 2049 tiles of 2 chunks
+    host = _synthetic(14, 2049, 4096, mask_values=(0, 1), normals=False)
+    assert 0.45 < host.valid_points_count() / host.len() < 0.55
+    dev = _upload(ctx, host)
+    dc = DevicePointCloud.from_range_image(dev)
+    _assert_same(dc, PointCloud.from_range_image(host))
+    dc.free()
+    dev.free()
+
+
 @pytest.mark.parametrize("bilateral", [False, True])
 def test_builder_pyramid_levels(ctx, bilateral):
     for frame in (0, 5):

@@ -175,6 +175,17 @@ def test_size_and_parameter_grid(ctx):
         with_n.free(), without_n.free()
 
 
+def test_cloud_of_more_chunks_than_tiles(ctx):
+    # the smallest cloud whose tiles hold two chunks: 4096 * 1024 + 1 points are 4097 chunks of 1024, above the 4096 tiles a
+    # cloud may have, so 2049 tiles of 2 chunks, the last of them with one point
+    points, _ = _uniform(150, 4096 * 1024 + 1, with_normals=False)
+    cloud = _device_cloud(ctx, points, None)
+    st, lens, dropped, outs = _call(ctx, [cloud], 0.02, None)
+    assert st == _abi.A3D_OK and outs[0]["normals"] is None and outs[0]["index"] is not None
+    _assert_matches(outs[0], lens[0], dropped[0], points, None, 0.02, None)
+    cloud.free()
+
+
 def test_merged_map_of_fixture_frames(ctx):
     w = _sample1_world(ctx)
     points, normals = w["host"]
