@@ -76,6 +76,19 @@ class PointCloudViewC(C.Structure):
     _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("len", C.c_uint64)]
 
 
+class VoxelMapStatsC(C.Structure):
+    _fields_ = [
+        ("cells", C.c_uint64),
+        ("slots", C.c_uint64),
+        ("total", C.c_uint64),
+        ("dropped_total", C.c_uint64),
+        ("growths", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class BuilderParamsC(C.Structure):
     _fields_ = [
         ("with_normals", C.c_uint32),
@@ -178,6 +191,15 @@ SIGNATURES = {
         [_P, C.POINTER(PointCloudViewC), C.c_uint64, C.c_float, C.POINTER(C.c_float), _PP, _PP, _PP, C.POINTER(C.c_uint64),
          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
+    "a3d_voxel_map_new": (_ST, [_P, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_uint64, _PP]),
+    "a3d_voxel_map_insert": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    ),
+    "a3d_voxel_map_extract": (_ST, [_P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "a3d_voxel_map_get_stats": (_ST, [_P, C.POINTER(VoxelMapStatsC)]),
+    "a3d_voxel_map_clear": (_ST, [_P]),
+    "a3d_voxel_map_free": (None, [_P]),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

@@ -27,7 +27,7 @@
 #include <cmath>
 #include <vector>
 
-#include "cloud_batch.hpp"
+#include "voxel_grid.hpp"  // VoxelGrid, voxel_key, slot_hash, VoxelSlot: shared with voxel_map.hip
 
 using namespace a3d;
 
@@ -39,15 +39,7 @@ constexpr uint32_t VX_ROUNDS = 4;
 constexpr uint32_t VX_CHUNK = VX_ROUNDS * VX_THREADS;  // points per chunk: a multiple of 64, so a ballot word never straddles tiles
 constexpr uint32_t VX_GROUPS = VX_CHUNK / 64;          // ballot words per chunk
 constexpr uint32_t VX_MAX_TILES = 4096;                // tiles per cloud at most (the offset sum of a block stays short)
-constexpr unsigned long long VX_EMPTY = ~0ull;         // no key has bit 63 set
-constexpr float VX_CELL_LIMIT = 1048576.0f;            // 2^20
 static_assert(VX_GROUPS <= 64, "a wave's lanes hold the chunk's ballot words");
-
-struct VoxelSlot {
-  unsigned long long key;   // VX_EMPTY or the 63-bit cell key
-  unsigned long long best;  // min over the key's points of bits(dist) << 32 | index
-};
-static_assert(sizeof(VoxelSlot) == 16, "VoxelSlot layout");
 
 // One non-empty cloud of a batch as the kernels see it (uploaded per call).
 struct VoxelJob {
@@ -63,36 +55,6 @@ struct VoxelJob {
   uint32_t len, first_tile, chunks_per_tile, pad;
 };
 static_assert(sizeof(VoxelJob) == 88, "VoxelJob layout");
-
-struct VoxelGrid {
-  float v, ox, oy, oz;
-};
-
-// The cell key of a point and (with_dist) its squared distance to the cell centre; false = the point is dropped.
-__device__ __forceinline__ bool voxel_key(const f32x3 p, const VoxelGrid g, unsigned long long* key, float* dist) {
-  const float cx = floorf((p.x - g.ox) / g.v), cy = floorf((p.y - g.oy) / g.v), cz = floorf((p.z - g.oz) / g.v);
-  // (a NaN fails every comparison, an infinity the range)
-  const bool ok = cx >= -VX_CELL_LIMIT && cx < VX_CELL_LIMIT && cy >= -VX_CELL_LIMIT && cy < VX_CELL_LIMIT &&
-                  cz >= -VX_CELL_LIMIT && cz < VX_CELL_LIMIT;
-  if (!ok) return false;
-  const unsigned long long kx = (unsigned long long)((int)cx + (1 << 20)), ky = (unsigned long long)((int)cy + (1 << 20)),
-                           kz = (unsigned long long)((int)cz + (1 << 20));
-  *key = kx << 42 | ky << 21 | kz;
-  if (dist) {
-    const float dx = p.x - ((cx + 0.5f) * g.v + g.ox), dy = p.y - ((cy + 0.5f) * g.v + g.oy),
-                dz = p.z - ((cz + 0.5f) * g.v + g.oz);
-    *dist = (dx * dx + dy * dy) + dz * dz;
-  }
-  return true;
-}
-
-__device__ __forceinline__ unsigned long long slot_hash(unsigned long long k) {  // the 64-bit finaliser of MurmurHash3
-  k ^= k >> 33, k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33, k *= 0xc4ceb9fe1a85ec53ull;
-  return k ^ k >> 33;
-}
-
-#define VX_LOAD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
 // Pass 1.  dropped[job] += dropped points (zeroed by the host upload); *fault is set if a table were ever full (it cannot
 // be: it has at least two slots per point).

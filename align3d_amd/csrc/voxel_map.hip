@@ -1,0 +1,554 @@
+// A persistent voxel map: the hash table of the voxel-grid downsample (voxel_downsample.hip) kept between calls, so that
+// resident clouds go in frame by frame.  After any sequence of inserts the map's contents equal merge(all inserted clouds
+// under their poses, in insertion order) followed by voxel_downsample(v, origin): points, normals, order and winner
+// indices, however the inserts were grouped into calls and whatever the table's size history was.  The downsample's rule
+// is a pure minimum per key of bits(dist) << 32 | index (voxel_grid.hpp), and a minimum over a union is the minimum of
+// the minima as long as `index` is the point's position in the merged cloud: point i of cloud j of a call gets
+// seq = total + sum(len[0..j)) + i, where total counts every point ever offered, dropped ones included.
+//
+// State (one device block per table size, from the context's block pool): slots x VoxelSlot {key, best} | slots x 3 f32
+// points | slots x 3 f32 normals (maps with normals) | one 64-bit count of occupied slots.  The payload is held BY SLOT in
+// arrays of its own: a probe touches 16-byte slots only, and a winner's row has a fixed home that a later, better point
+// simply overwrites, so there is no free list and nothing to compact between calls.
+//
+// Insert, two launches over every tile of every cloud of the call (the job table of cloud_batch.hpp), no block waits on
+// another block, no LDS:
+//  A. voxel_map_insert_kernel: a thread per point transforms it in registers (transform_vector of devmath.hpp, what
+//     cloud_transform.hip calls), computes voxel_key, claims the key's slot (load before CAS) and atomicMins its word into
+//     `best` (load before min), exactly as voxel_insert_kernel.  The threads whose CAS claimed an empty slot add themselves
+//     to the cell count (one atomicAdd per wave).
+//  B. voxel_map_commit_kernel: each kept point finds its slot again; iff the slot's low 32 bits of `best` are its seq it
+//     is the final winner (unique per slot) and writes its transformed point and normal into the slot's row.  It cannot
+//     be part of A: a thread whose atomicMin succeeded is not yet the final winner.
+// The table never fills: before launching, the host makes sure slots >= 2 * (cells + L), L the points of the call, growing
+// to the next sufficient power of two with one rehash launch over the old slots (keys are unique: only the claim is
+// contended).  The `fault` word of the downsample stays as a guard.
+//
+// Extract writes the occupied slots' rows in ascending seq, the order voxel_downsample gives on the merged cloud (slot
+// order depends on which colliding key claimed first, i.e. on timing): a bitmap of `total` bits in scratch, set per
+// occupied slot (32-bit atomicOr), counted per tile, turned into one exclusive prefix per 64-bit word, and a last pass over
+// the slots writes each row to prefix(word of seq) + popcount(lower bits of the word).
+#include <cmath>
+#include <vector>
+
+#include "voxel_grid.hpp"
+
+using namespace a3d;
+
+struct a3d_voxel_map {
+  a3d_context* ctx = nullptr;
+  VoxelGrid grid{};
+  bool with_normals = false;
+  uint64_t reserve_cells = 0;
+  // the device block of the current table (null until the first insert that holds a point)
+  void* block = nullptr;
+  size_t block_bytes = 0;
+  uint64_t slots = 0;
+  VoxelSlot* table = nullptr;
+  float* points = nullptr;
+  float* normals = nullptr;
+  unsigned long long* cell_count = nullptr;
+  uint64_t cells = 0, total = 0, dropped_total = 0, growths = 0;
+};
+
+namespace {
+
+constexpr uint32_t VM_THREADS = 256;
+constexpr uint32_t VM_WAVES = VM_THREADS / 64;
+constexpr uint32_t VM_CHUNK = 4 * VM_THREADS;  // points per chunk of an insert tile, as the downsample's
+constexpr uint32_t VM_MAX_TILES = 4096;        // tiles per cloud (insert) / per bitmap (extract) at most
+constexpr uint64_t VM_SEQ_MARGIN = 1ull << 21;  // above any tile span (a cloud has < 2^32 points: <= 1024 chunks per tile)
+constexpr uint32_t VM_MAX_SLOT_BLOCKS = 1u << 20;  // grid of the passes over the slots (grid-stride beyond)
+constexpr uint32_t VM_NO_SLOT = ~0u;
+
+// One non-empty cloud of a call as the kernels see it (uploaded per call).
+struct MapJob {
+  const float* points;
+  const float* normals;  // read only by maps with normals
+  uint32_t len, first_tile, chunks_per_tile, has_pose;
+  uint32_t seq0;  // sequence number of the cloud's point 0
+  Pose pose;
+};
+static_assert(sizeof(MapJob) == 64, "MapJob layout");
+
+struct MapTable {
+  VoxelSlot* table;
+  float* points;   // [slots][3]
+  float* normals;  // [slots][3] or null
+  unsigned long long mask;  // slots - 1
+  unsigned long long* cell_count;
+};
+
+__device__ __forceinline__ f32x3 world_point(const MapJob& j, uint32_t p) {
+  const f32x3 pt = *(const f32x3_u*)(j.points + 3 * (size_t)p);
+  if (!j.has_pose) return pt;  // verbatim, as the merge without poses
+  const V3 v = transform_vector(j.pose, V3{pt.x, pt.y, pt.z});
+  return f32x3{v.x, v.y, v.z};
+}
+
+// The slot that holds `key`, claimed if no slot does yet (*claimed); false = the table is full (it cannot be).
+__device__ __forceinline__ bool claim_slot(VoxelSlot* table, unsigned long long mask, unsigned long long key,
+                                           unsigned long long* slot, bool* claimed) {
+  unsigned long long s = slot_hash(key) & mask;
+  for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
+    unsigned long long k = VX_LOAD_AGENT(&table[s].key);
+    if (k == VX_EMPTY) {
+      k = atomicCAS(&table[s].key, VX_EMPTY, key);
+      if (k == VX_EMPTY) *claimed = true;
+    }
+    if (k == VX_EMPTY || k == key) {
+      *slot = s;
+      return true;
+    }
+  }
+  return false;
+}
+
+// Pass A.  dropped[job] += dropped points (zeroed by the host upload); *fault is set if the table were ever full.
+// STORE_SLOT (diagnostics build): slot_of[seq - seq_base] = the point's slot, VM_NO_SLOT for a dropped point.
+template <bool STORE_SLOT>
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_insert_kernel(const MapJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, MapTable m,
+                            unsigned long long* __restrict__ dropped, unsigned long long* __restrict__ fault,
+                            uint32_t* __restrict__ slot_of, uint32_t seq_base) {
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MapJob& j = jobs[ji];
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (total + L < 2^32 - span: checked by the host)
+  uint32_t n_dropped = 0, n_claimed = 0;
+  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += VM_THREADS) {
+    const f32x3 pt = world_point(j, p);
+    const uint32_t seq = j.seq0 + p;
+    unsigned long long key, s;
+    float dist;
+    if (!voxel_key(pt, grid, &key, &dist)) {
+      ++n_dropped;
+      if (STORE_SLOT) slot_of[seq - seq_base] = VM_NO_SLOT;
+      continue;
+    }
+    bool claimed = false;
+    if (!claim_slot(m.table, m.mask, key, &s, &claimed)) {
+      atomicMax(fault, 1ull);
+      if (STORE_SLOT) slot_of[seq - seq_base] = VM_NO_SLOT;
+      continue;
+    }
+    n_claimed += claimed ? 1u : 0u;
+    const unsigned long long word = (unsigned long long)__float_as_uint(dist) << 32 | seq;
+    if (VX_LOAD_AGENT(&m.table[s].best) > word) atomicMin(&m.table[s].best, word);
+    if (STORE_SLOT) slot_of[seq - seq_base] = (uint32_t)s;
+  }
+  n_dropped = wave_sum(n_dropped), n_claimed = wave_sum(n_claimed);
+  if ((threadIdx.x & 63u) == 0) {
+    if (n_dropped) atomicAdd(&dropped[ji], (unsigned long long)n_dropped);
+    if (n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
+  }
+}
+
+// Pass B: the final winner of a slot writes the slot's row.
+template <bool STORED_SLOT>
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_commit_kernel(const MapJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, MapTable m,
+                            const uint32_t* __restrict__ slot_of, uint32_t seq_base) {
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MapJob& j = jobs[ji];
+  const VoxelSlot* __restrict__ table = m.table;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);
+  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += VM_THREADS) {
+    const uint32_t seq = j.seq0 + p;
+    unsigned long long s = 0;
+    bool found = false;
+    f32x3 pt;
+    if (STORED_SLOT) {
+      const uint32_t stored = slot_of[seq - seq_base];
+      if (stored == VM_NO_SLOT) continue;
+      s = stored, found = true;
+      pt = world_point(j, p);
+    } else {
+      pt = world_point(j, p);
+      unsigned long long key;
+      if (!voxel_key(pt, grid, &key, nullptr)) continue;
+      s = slot_hash(key) & m.mask;
+      for (unsigned long long tries = 0; tries <= m.mask; ++tries, s = (s + 1) & m.mask) {
+        const unsigned long long k = table[s].key;
+        if (k == key) {
+          found = true;
+          break;
+        }
+        if (k == VX_EMPTY) break;  // (cannot happen: pass A placed every kept point)
+      }
+    }
+    if (!found || s > m.mask || (uint32_t)table[s].best != seq) continue;  // (a bound on every store)
+    *(f32x3_u*)(m.points + 3 * (size_t)s) = pt;
+    if (m.normals) {
+      f32x3 nv = *(const f32x3_u*)(j.normals + 3 * (size_t)p);
+      if (j.has_pose) {
+        const V3 w = transform_normal(j.pose, V3{nv.x, nv.y, nv.z});
+        nv = f32x3{w.x, w.y, w.z};
+      }
+      *(f32x3_u*)(m.normals + 3 * (size_t)s) = nv;
+    }
+  }
+}
+
+// Growth: every occupied slot of the old table into the new one (key, best, row); counts the new table's cells.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_rehash_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                            const float* __restrict__ old_normals, unsigned long long old_slots, MapTable m,
+                            unsigned long long* __restrict__ fault) {
+  uint32_t n_claimed = 0;
+  for (unsigned long long o = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; o < old_slots;
+       o += (unsigned long long)gridDim.x * VM_THREADS) {
+    const unsigned long long key = old_table[o].key;
+    if (key == VX_EMPTY) continue;
+    unsigned long long s;
+    bool claimed = false;
+    if (!claim_slot(m.table, m.mask, key, &s, &claimed) || !claimed) {  // (keys are unique: the slot is always a fresh claim)
+      atomicMax(fault, 1ull);
+      continue;
+    }
+    ++n_claimed;
+    m.table[s].best = old_table[o].best;
+    *(f32x3_u*)(m.points + 3 * (size_t)s) = *(const f32x3_u*)(old_points + 3 * (size_t)o);
+    if (m.normals) *(f32x3_u*)(m.normals + 3 * (size_t)s) = *(const f32x3_u*)(old_normals + 3 * (size_t)o);
+  }
+  n_claimed = wave_sum(n_claimed);
+  if ((threadIdx.x & 63u) == 0 && n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
+}
+
+// Extract 1: bit seq of the bitmap for every occupied slot (32-bit halves of the 64-bit words, little endian).
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_mark_kernel(const VoxelSlot* __restrict__ table, unsigned long long slots, uint32_t* __restrict__ bitmap32,
+                          unsigned long long total) {
+  for (unsigned long long s = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; s < slots;
+       s += (unsigned long long)gridDim.x * VM_THREADS) {
+    if (table[s].key == VX_EMPTY) continue;
+    const uint32_t seq = (uint32_t)table[s].best;
+    if (seq < total) atomicOr(&bitmap32[seq >> 5], 1u << (seq & 31u));
+  }
+}
+
+// Extract 2: tile_counts[tile] = set bits of the tile's words (a tile: chunks_per_tile * VM_THREADS 64-bit words).
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_count_kernel(const unsigned long long* __restrict__ bitmap, uint32_t n_words, uint32_t chunks_per_tile,
+                           uint32_t* __restrict__ tile_counts) {
+  __shared__ uint32_t s_wave[VM_WAVES];
+  const uint32_t tile = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint64_t w0 = (uint64_t)tile * chunks_per_tile * VM_THREADS;
+  const uint64_t w_end = min((uint64_t)n_words, w0 + (uint64_t)chunks_per_tile * VM_THREADS);
+  uint32_t c = 0;
+  for (uint64_t w = w0 + threadIdx.x; w < w_end; w += VM_THREADS) c += (uint32_t)__builtin_popcountll(bitmap[w]);
+  c = wave_sum(c);
+  if (lane == 0) s_wave[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t sum = 0;
+    for (uint32_t w = 0; w < VM_WAVES; ++w) sum += s_wave[w];
+    tile_counts[tile] = sum;
+  }
+}
+
+// Extract 3: word_prefix[w] = set bits of all words before w.  A block sums the earlier tiles' counts for its base
+// (cloud_write_kernel's form: at most VM_MAX_TILES tiles) and scans its own words chunk by chunk.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_prefix_kernel(const unsigned long long* __restrict__ bitmap, uint32_t n_words, uint32_t chunks_per_tile,
+                            const uint32_t* __restrict__ tile_counts, uint32_t* __restrict__ word_prefix) {
+  __shared__ uint32_t s_base, s_wave[VM_WAVES];
+  const uint32_t tile = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (wave == 0) {
+    uint32_t s = 0;
+    for (uint32_t k = lane; k < tile; k += 64) s += tile_counts[k];
+    s = wave_sum(s);
+    if (lane == 0) s_base = s;
+  }
+  __syncthreads();
+  uint32_t base = s_base;
+  const uint64_t w0 = (uint64_t)tile * chunks_per_tile * VM_THREADS;
+  const uint64_t w_end = min((uint64_t)n_words, w0 + (uint64_t)chunks_per_tile * VM_THREADS);
+  for (uint64_t c0 = w0; c0 < w_end; c0 += VM_THREADS) {  // block-uniform
+    const uint64_t w = c0 + threadIdx.x;
+    const uint32_t cnt = w < w_end ? (uint32_t)__builtin_popcountll(bitmap[w]) : 0u;
+    uint32_t incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t up = __shfl_up(incl, o, 64);
+      if (lane >= (uint32_t)o) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < VM_WAVES; ++k) {
+      const uint32_t t = s_wave[k];
+      before += k < wave ? t : 0u;
+      all += t;
+    }
+    if (w < w_end) word_prefix[w] = base + before + incl - cnt;
+    base += all;
+    __syncthreads();  // s_wave is rewritten by the next chunk
+  }
+}
+
+// Extract 4: every occupied slot's row to its rank among the set bits: ascending seq.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_write_kernel(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
+                           const float* __restrict__ normals, unsigned long long slots,
+                           const unsigned long long* __restrict__ bitmap, const uint32_t* __restrict__ word_prefix,
+                           unsigned long long total, unsigned long long rows, float* __restrict__ out_points,
+                           float* __restrict__ out_normals, uint32_t* __restrict__ out_index) {
+  for (unsigned long long s = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; s < slots;
+       s += (unsigned long long)gridDim.x * VM_THREADS) {
+    if (table[s].key == VX_EMPTY) continue;
+    const uint32_t seq = (uint32_t)table[s].best;
+    if (seq >= total) continue;  // (cannot happen: every occupied slot holds the seq of an offered point)
+    const uint32_t w = seq >> 6;
+    const unsigned long long dst =
+        (unsigned long long)word_prefix[w] + (unsigned long long)__builtin_popcountll(bitmap[w] & ((1ull << (seq & 63u)) - 1ull));
+    if (dst >= rows) continue;  // (cannot happen: rows = the occupied slots; a bound on every store)
+    *(f32x3_u*)(out_points + 3 * dst) = *(const f32x3_u*)(points + 3 * (size_t)s);
+    if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)s);
+    if (out_index) out_index[dst] = seq;
+  }
+}
+
+uint32_t slot_blocks(uint64_t slots) {
+  return (uint32_t)std::min<uint64_t>((slots + VM_THREADS - 1) / VM_THREADS, VM_MAX_SLOT_BLOCKS);
+}
+
+MapTable table_of(const a3d_voxel_map* m) {
+  return MapTable{m->table, m->points, m->normals, m->slots - 1, m->cell_count};
+}
+
+// Makes sure the table has at least 2 * (cells + incoming) slots; `fault` is the call's guard word in scratch.
+a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long* d_fault) {
+  const uint64_t need = 2 * (m->cells + incoming);
+  if (m->block && m->slots >= need) return A3D_OK;
+  uint64_t slots = 64;
+  while (slots < need || slots < 2 * m->reserve_cells) slots <<= 1;
+  a3d_context* ctx = m->ctx;
+  const size_t table_bytes = pad256(slots * sizeof(VoxelSlot)), row_bytes = pad256(slots * 12);
+  const size_t bytes = table_bytes + row_bytes * (m->with_normals ? 2 : 1) + 256;
+  void* block = nullptr;
+  size_t block_bytes = 0;
+  A3D_TRY(ctx_block_alloc(ctx, bytes, &block, &block_bytes));
+  char* base = (char*)block;
+  a3d_voxel_map old = *m;
+  m->block = block, m->block_bytes = block_bytes, m->slots = slots;
+  m->table = (VoxelSlot*)base;
+  m->points = (float*)(base + table_bytes);
+  m->normals = m->with_normals ? (float*)(base + table_bytes + row_bytes) : nullptr;
+  m->cell_count = (unsigned long long*)(base + bytes - 256);
+  hipStream_t s = ctx->stream;
+  hipError_t e = hipMemsetAsync(m->table, 0xFF, slots * sizeof(VoxelSlot), s);  // every key VX_EMPTY, every best word ~0
+  if (e == hipSuccess) e = hipMemsetAsync(m->cell_count, 0, 8, s);
+  if (e == hipSuccess && old.block && old.cells) {
+    hipLaunchKernelGGL(voxel_map_rehash_kernel, dim3(slot_blocks(old.slots)), dim3(VM_THREADS), 0, s,
+                       (const VoxelSlot*)old.table, (const float*)old.points, (const float*)old.normals,
+                       (unsigned long long)old.slots, table_of(m), d_fault);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {  // the old table stays the map's
+    (void)hipStreamSynchronize(s);
+    ctx_block_release(ctx, block, block_bytes);
+    *m = old;
+    set_error("a3d_voxel_map_insert: growing the table failed: %s", hipGetErrorString(e));
+    return A3D_HIP_ERROR;
+  }
+  if (old.block) {
+    ++m->growths;
+    ctx_block_release(ctx, old.block, old.block_bytes);  // reuse is ordered on the context's stream, behind the rehash
+  }
+  return A3D_OK;
+}
+
+bool stored_slot_setting() {
+  const char* env = A3D_DIAG_ENV("A3D_VOXEL_MAP_STORED_SLOT");  // diagnostics build: the pass-B form the probe times
+  return env && *env == '1';
+}
+
+}  // namespace
+
+extern "C" {
+
+a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
+                             uint64_t reserve_cells, a3d_voxel_map** out) {
+  A3D_REQUIRE(ctx && out, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.f, A3D_INVALID_PARAMETER,
+              "a3d_voxel_map_new: the voxel size must be finite and positive");
+  VoxelGrid grid{voxel_size, 0.f, 0.f, 0.f};
+  if (origin) {
+    A3D_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), A3D_INVALID_PARAMETER,
+                "a3d_voxel_map_new: the origin must be finite");
+    grid.ox = origin[0], grid.oy = origin[1], grid.oz = origin[2];
+  }
+  A3D_REQUIRE(reserve_cells < (1ull << 32), A3D_INVALID_PARAMETER, "a3d_voxel_map_new: a reservation of 2^32 cells or more");
+  a3d_voxel_map* m = new a3d_voxel_map();
+  m->ctx = ctx, m->grid = grid, m->with_normals = with_normals != 0, m->reserve_cells = reserve_cells;
+  *out = m;  // the table is allocated by the first insert that holds a point
+  return A3D_OK;
+}
+
+a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
+                                uint64_t n, uint64_t* out_dropped, uint64_t* out_cells) {
+  if (n == 0) return A3D_OK;
+  A3D_REQUIRE(map && d_clouds, A3D_INVALID_PARAMETER, "null argument");
+  std::vector<MapJob> jobs;
+  std::vector<uint64_t> cloud_of_job;
+  jobs.reserve(n), cloud_of_job.reserve(n);
+  uint64_t tiles = 0, incoming = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const a3d_point_cloud_view& c = d_clouds[i];
+    A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
+    if (c.len == 0) continue;  // offers no points; its pointers may be null
+    A3D_REQUIRE(c.points, A3D_INVALID_PARAMETER, "null points pointer");
+    A3D_REQUIRE(!map->with_normals || c.normals, A3D_MISSING_FIELD,
+                "a3d_voxel_map_insert: the map has normals and a cloud has none (nothing was inserted)");
+    // (a sum of < 2^32 terms below 2^32 cannot wrap 64 bits; the limit below bounds it)
+    A3D_REQUIRE(map->total + incoming + c.len + VM_SEQ_MARGIN < (1ull << 32), A3D_INVALID_PARAMETER,
+                "a3d_voxel_map_insert: the map would pass 2^32 - 2^21 offered points (renumbering is not built)");
+    MapJob j{};
+    j.points = c.points, j.normals = map->with_normals ? c.normals : nullptr;
+    j.len = (uint32_t)c.len;
+    j.seq0 = (uint32_t)(map->total + incoming);
+    if (poses_host) j.has_pose = 1, j.pose = pose_from_c(&poses_host[i]);
+    A3D_TRY(plan_tiles(c.len, VM_CHUNK, VM_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
+    incoming += c.len;
+    jobs.push_back(j), cloud_of_job.push_back(i);
+  }
+  if (out_dropped)
+    for (uint64_t i = 0; i < n; ++i) out_dropped[i] = 0;
+  if (jobs.empty()) {
+    if (out_cells) *out_cells = map->cells;
+    return A3D_OK;
+  }
+  a3d_context* ctx = map->ctx;
+  const size_t n_jobs = jobs.size();
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  const bool want_stored = stored_slot_setting();
+  BatchScratch scratch;  // the words: dropped per job, fault; the tail: the per-point slots of the stored-slot form
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(MapJob), n_jobs + 1, 0, want_stored ? incoming * 4 : 0, &scratch));
+  const MapJob* d_jobs = (const MapJob*)scratch.jobs;
+  unsigned long long* d_dropped = scratch.words;
+  unsigned long long* d_fault = d_dropped + n_jobs;
+  uint32_t* d_slot_of = (uint32_t*)scratch.tail;
+  hipStream_t s = ctx->stream;
+  A3D_TRY(batch_upload(scratch, jobs.data(), s));  // (before a rehash: it zeroes the fault word)
+  A3D_TRY(ensure_slots(map, incoming, d_fault));
+  const MapTable table = table_of(map);
+  const bool stored = want_stored && map->slots <= (1ull << 31);  // (a slot fits the 32-bit word, VM_NO_SLOT apart)
+  const dim3 grid_dim((uint32_t)tiles), block(VM_THREADS);
+  const uint32_t seq_base = (uint32_t)map->total;
+#ifdef A3D_DIAGNOSTICS  // (the product library holds the one form it launches)
+  if (stored) {
+    hipLaunchKernelGGL(voxel_map_insert_kernel<true>, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, table,
+                       d_dropped, d_fault, d_slot_of, seq_base);
+    A3D_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(voxel_map_commit_kernel<true>, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, table,
+                       (const uint32_t*)d_slot_of, seq_base);
+  } else
+#endif
+  {
+    hipLaunchKernelGGL(voxel_map_insert_kernel<false>, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, table,
+                       d_dropped, d_fault, d_slot_of, seq_base);
+    A3D_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(voxel_map_commit_kernel<false>, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, table,
+                       (const uint32_t*)d_slot_of, seq_base);
+  }
+  A3D_HIP_TRY(hipGetLastError());
+  std::vector<unsigned long long> words(n_jobs + 1);
+  unsigned long long cells = 0;
+  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_dropped, words.size() * 8, hipMemcpyDeviceToHost, s));
+  A3D_HIP_TRY(hipMemcpyAsync(&cells, map->cell_count, 8, hipMemcpyDeviceToHost, s));
+  // host-synchronous, the one wait of the call: the caller may free the inputs right after
+  A3D_HIP_TRY(hipStreamSynchronize(s));
+  map->cells = cells, map->total += incoming;
+  for (size_t k = 0; k < n_jobs; ++k) {
+    map->dropped_total += words[k];
+    if (out_dropped) out_dropped[cloud_of_job[k]] = words[k];
+  }
+  if (out_cells) *out_cells = map->cells;
+  A3D_REQUIRE(words[n_jobs] == 0, A3D_HIP_ERROR, "a3d_voxel_map_insert: the hash table filled up");
+  return A3D_OK;
+}
+
+a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint32_t* d_out_index,
+                                 uint64_t capacity, uint64_t* out_len) {
+  A3D_REQUIRE(map && d_out_points && out_len, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE(!d_out_normals || map->with_normals, A3D_MISSING_FIELD, "a3d_voxel_map_extract: the map has no normals");
+  {  // the outputs as the caller declared them: `capacity` rows each (no map has 2^32 cells)
+    const uintptr_t rows = (uintptr_t)std::min<uint64_t>(capacity, 1ull << 32);
+    std::vector<ByteRange> ranges;
+    if (rows) {
+      ranges.push_back({(uintptr_t)d_out_points, (uintptr_t)d_out_points + rows * 12, true});
+      if (d_out_normals) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + rows * 12, true});
+      if (d_out_index) ranges.push_back({(uintptr_t)d_out_index, (uintptr_t)d_out_index + rows * 4, true});
+    }
+    A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER, "a3d_voxel_map_extract: the outputs overlap one another");
+  }
+  *out_len = map->cells;
+  if (capacity < map->cells) {
+    set_error("a3d_voxel_map_extract: capacity %llu is smaller than the map's %llu cells (nothing was written)",
+              (unsigned long long)capacity, (unsigned long long)map->cells);
+    return A3D_INVALID_PARAMETER;
+  }
+  if (map->cells == 0) return A3D_OK;
+  a3d_context* ctx = map->ctx;
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  // scratch: one count per tile | the bitmap of `total` bits | one prefix per 64-bit word of it
+  const uint64_t n_words = (map->total + 63) / 64;  // < 2^26
+  uint64_t tiles = 0;
+  uint32_t first_tile = 0, chunks_per_tile = 0;
+  A3D_TRY(plan_tiles(n_words, VM_THREADS, VM_MAX_TILES, &tiles, &first_tile, &chunks_per_tile));
+  const size_t counts_bytes = pad256(tiles * 4), bitmap_bytes = pad256(n_words * 8), prefix_bytes = pad256(n_words * 4);
+  void* region = nullptr;
+  A3D_TRY(ctx_scratch(ctx, 3, counts_bytes + bitmap_bytes + prefix_bytes, &region));
+  uint32_t* d_tile_counts = (uint32_t*)region;
+  unsigned long long* d_bitmap = (unsigned long long*)((char*)region + counts_bytes);
+  uint32_t* d_prefix = (uint32_t*)((char*)region + counts_bytes + bitmap_bytes);
+  hipStream_t s = ctx->stream;
+  A3D_HIP_TRY(hipMemsetAsync(d_bitmap, 0, bitmap_bytes, s));
+  const dim3 over_slots(slot_blocks(map->slots)), over_words((uint32_t)tiles), block(VM_THREADS);
+  hipLaunchKernelGGL(voxel_map_mark_kernel, over_slots, block, 0, s, (const VoxelSlot*)map->table,
+                     (unsigned long long)map->slots, (uint32_t*)d_bitmap, (unsigned long long)map->total);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(voxel_map_count_kernel, over_words, block, 0, s, (const unsigned long long*)d_bitmap, (uint32_t)n_words,
+                     chunks_per_tile, d_tile_counts);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(voxel_map_prefix_kernel, over_words, block, 0, s, (const unsigned long long*)d_bitmap, (uint32_t)n_words,
+                     chunks_per_tile, (const uint32_t*)d_tile_counts, d_prefix);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(voxel_map_write_kernel, over_slots, block, 0, s, (const VoxelSlot*)map->table, (const float*)map->points,
+                     (const float*)map->normals, (unsigned long long)map->slots, (const unsigned long long*)d_bitmap,
+                     (const uint32_t*)d_prefix, (unsigned long long)map->total, (unsigned long long)map->cells, d_out_points,
+                     d_out_normals, d_out_index);
+  A3D_HIP_TRY(hipGetLastError());
+  // host-synchronous: the caller may read or free the outputs right after
+  A3D_HIP_TRY(hipStreamSynchronize(s));
+  return A3D_OK;
+}
+
+a3d_status a3d_voxel_map_get_stats(const a3d_voxel_map* map, a3d_voxel_map_stats* out) {
+  A3D_REQUIRE(map && out, A3D_INVALID_PARAMETER, "null argument");
+  out->cells = map->cells, out->slots = map->slots, out->total = map->total;
+  out->dropped_total = map->dropped_total, out->growths = map->growths;
+  return A3D_OK;
+}
+
+a3d_status a3d_voxel_map_clear(a3d_voxel_map* map) {
+  A3D_REQUIRE(map, A3D_INVALID_PARAMETER, "null argument");
+  if (map->block) {  // the allocation stays; ordered on the context's stream like every other use of the table
+    A3D_HIP_TRY(hipSetDevice(map->ctx->device));
+    A3D_HIP_TRY(hipMemsetAsync(map->table, 0xFF, map->slots * sizeof(VoxelSlot), map->ctx->stream));
+    A3D_HIP_TRY(hipMemsetAsync(map->cell_count, 0, 8, map->ctx->stream));
+  }
+  map->cells = map->total = map->dropped_total = 0;
+  return A3D_OK;
+}
+
+void a3d_voxel_map_free(a3d_voxel_map* map) {
+  if (!map) return;
+  if (map->block) ctx_block_release(map->ctx, map->block, map->block_bytes);
+  delete map;
+}
+
+}  // extern "C"

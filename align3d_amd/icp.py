@@ -525,6 +525,99 @@ class DevicePointCloud:
         self.d_points = self.d_normals = None
 
 
+class DeviceVoxelMap:
+    """A persistent voxel map in HBM (a3d_voxel_map_*): resident clouds go in frame by frame, and after any sequence of
+    inserts extract() is DevicePointCloud.merge(all inserted clouds, their transforms).voxel_downsample(voxel_size,
+    origin) bit for bit — points, normals, order and indices — however the inserts were grouped.  normals=True: the map
+    keeps a normal per cell and every inserted cloud must have normals.  reserve_cells: cells the first table holds
+    without growing."""
+
+    def __init__(self, ctx, voxel_size, origin=None, normals=True, reserve_cells=0):
+        self.ctx = ctx
+        self.normals = bool(normals)
+        self.handle = C.c_void_p()
+        o = None
+        if origin is not None:
+            o = np.ascontiguousarray(origin, np.float32).reshape(-1)
+            if o.size != 3:
+                raise _abi.InvalidParameter("DeviceVoxelMap: the origin has three coordinates")
+            o = (C.c_float * 3)(*o.tolist())
+        _abi.check(ctx.lib.a3d_voxel_map_new(ctx.handle, float(voxel_size), o, int(self.normals), int(reserve_cells),
+                                             C.byref(self.handle)), "a3d_voxel_map_new")
+
+    def insert_many(self, clouds, transforms=None):
+        """Inserts resident clouds of the map's context, cloud i under transforms[i] (None: as they are), in ONE call;
+        returns the dropped count of each cloud (points whose cell is not finite or out of range: they still consume a
+        sequence number)."""
+        clouds = list(clouds)
+        if not clouds:
+            return []
+        clouds, ctx, poses = DevicePointCloud._resident_batch(clouds, transforms, "DeviceVoxelMap.insert_many")
+        if ctx is not self.ctx:
+            raise _abi.InvalidParameter("DeviceVoxelMap.insert_many: the clouds must live on the map's context")
+        n = len(clouds)
+        dropped = (C.c_uint64 * n)()
+        _abi.check(self.ctx.lib.a3d_voxel_map_insert(self.handle, DevicePointCloud._views(clouds), poses, n, dropped, None),
+                   "a3d_voxel_map_insert")
+        return [int(d) for d in dropped]
+
+    def insert(self, cloud, transform=None):
+        """Inserts one resident cloud (under `transform`); returns its dropped count."""
+        return self.insert_many([cloud], None if transform is None else [transform])[0]
+
+    def extract(self, return_index=False):
+        """The map as a new DevicePointCloud of exactly cells() rows, in ascending sequence number (the order of the
+        downsampled merged cloud; the same bits on every run).  return_index=True returns (cloud, index): `index` is a
+        HOST uint32 array, index[k] = the position of row k in the merged cloud of everything inserted."""
+        ctx, cells = self.ctx, self.cells()
+        out = DevicePointCloud._allocate(ctx, cells, self.normals)
+        d_index = None
+        try:
+            if return_index:
+                d_index = ctx.malloc(max(1, cells) * 4)
+            n_out = C.c_uint64()
+            _abi.check(ctx.lib.a3d_voxel_map_extract(self.handle, out.d_points, out.d_normals, d_index, cells, C.byref(n_out)),
+                       "a3d_voxel_map_extract")
+            out.n = int(n_out.value)
+            index = None
+            if return_index:
+                index = ctx.to_host(d_index, np.empty(out.n, np.uint32)) if out.n else np.empty(0, np.uint32)
+        except BaseException:
+            out.free()
+            raise
+        finally:
+            if d_index is not None:
+                ctx.free(d_index)
+        return (out, index) if return_index else out
+
+    def stats(self):
+        """{cells, slots, total, dropped_total, growths} (a3d_voxel_map_stats)."""
+        s = _abi.VoxelMapStatsC()
+        _abi.check(self.ctx.lib.a3d_voxel_map_get_stats(self.handle, C.byref(s)), "a3d_voxel_map_get_stats")
+        return s.as_dict()
+
+    def cells(self):
+        return self.stats()["cells"]
+
+    def total(self):
+        return self.stats()["total"]
+
+    def clear(self):
+        """Empties the map and keeps its allocation; sequence numbers restart at 0."""
+        _abi.check(self.ctx.lib.a3d_voxel_map_clear(self.handle), "a3d_voxel_map_clear")
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.a3d_voxel_map_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Icp:
     """Icp (src/icp/pcl_icp.rs:15-108): point-to-plane ICP with kd-tree correspondences.  `target` / `source` may be
     PointCloud (host arrays, as in the reference) or DevicePointCloud (already resident)."""

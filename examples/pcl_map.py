@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """A map from a recorded sequence without leaving the device:
-    python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N] [--voxel V] [--out map.npy]
+    python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N] [--voxel V [--online [--check-batch]]] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
 back in one resident cloud (one launch).  With --voxel V the map is then thinned to one point per V-sized cell
 (DevicePointCloud.voxel_downsample: still on the device) and the last frame is aligned against the thinned map with Icp,
-frame to map.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the
-points ([N, 3] f32)."""
+frame to map.  With --online the thinned map is built the way a live caller would, frame by frame into a persistent
+DeviceVoxelMap (insert per frame, one extract at the end) instead of merge + voxel_downsample of everything: no merged
+cloud exists at any time, and the lines it prints are the same.  --check-batch runs the batch path as well, only to
+assert that the two maps are the same bits.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import os
 import sys
@@ -16,15 +18,22 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from align3d_amd import (Context, DevicePointCloud, Icp, IcpBatch, IcpParams, RangeImageBuilder,  # noqa: E402
-                         SlamTbDataset, Transform, TrajectoryBuilder)
+from align3d_amd import (Context, DevicePointCloud, DeviceVoxelMap, Icp, IcpBatch, IcpParams,  # noqa: E402
+                         RangeImageBuilder, SlamTbDataset, Transform, TrajectoryBuilder)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("dataset", nargs="?", default=os.path.join(ROOT, "tests", "golden", "rgbd", "sample1"))
 ap.add_argument("--max-frames", type=int, default=None)
 ap.add_argument("--voxel", type=float, default=None, help="thin the map to one point per cell of this size (metres)")
+ap.add_argument("--online", action="store_true", help="with --voxel: build the thinned map by inserting frame by frame")
+ap.add_argument("--check-batch", action="store_true",
+                help="with --online: also run merge + voxel_downsample and assert that the online map is the same bits")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file")
 args = ap.parse_args()
+if args.online and not args.voxel:
+    ap.error("--online needs --voxel")
+if args.check_batch and not args.online:
+    ap.error("--check-batch needs --online")
 
 ctx = Context(0)
 ds = SlamTbDataset.load(args.dataset)
@@ -45,12 +54,36 @@ for k, (now_to_previous, st) in enumerate(zip(poses, status)):
     else:
         traj.accumulate(now_to_previous, float(k + 1))
     camera_to_world.append(traj.current_camera_to_world())
-world_map = DevicePointCloud.merge(clouds, camera_to_world)  # the last step: all frames in one coordinate system
-if args.voxel:
-    full = world_map
-    world_map = full.voxel_downsample(args.voxel)
-    print(f"voxel {args.voxel}: {full.len()} points -> {world_map.len()}")
+
+
+def thinned_by_batch():
+    """(points offered, thinned map): all frames in one coordinate system, then one point per cell."""
+    full = DevicePointCloud.merge(clouds, camera_to_world)
+    thin = full.voxel_downsample(args.voxel)
+    offered = full.len()
     full.free()
+    return offered, thin
+
+
+if args.online:
+    online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None)
+    for cloud, pose in zip(clouds, camera_to_world):  # what a live caller does as each frame arrives
+        online.insert(cloud, pose)
+    offered, world_map = online.total(), online.extract()
+    online.free()
+    if args.check_batch:  # the batch path, for this comparison only
+        _, batch_map = thinned_by_batch()
+        same = batch_map.len() == world_map.len() and all(
+            a is None and b is None or np.array_equal(a.view(np.uint32), b.view(np.uint32))
+            for a, b in zip(batch_map.download(), world_map.download()))
+        assert same, "the online map differs from merge + voxel_downsample"
+        batch_map.free()
+elif args.voxel:
+    offered, world_map = thinned_by_batch()
+else:
+    world_map = DevicePointCloud.merge(clouds, camera_to_world)  # the last step: all frames in one coordinate system
+if args.voxel:
+    print(f"voxel {args.voxel}: {offered} points -> {world_map.len()}")
     # frame to map: the last frame, brought to the world by its odometry pose, against the thinned map; what Icp
     # returns is the correction the map asks of that pose
     last = camera_to_world[-1] * clouds[-1]

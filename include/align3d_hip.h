@@ -535,6 +535,59 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
                                                     float* const* d_out_normals, uint32_t* const* d_out_index,
                                                     const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped);
 
+/* A persistent voxel map: the hash table of the downsample above kept between calls, so that resident clouds go in frame
+ * by frame (a3d_voxel_map_insert) instead of merge + downsample of the whole map per frame.  The contract:
+ *   After any sequence of inserts, the map's contents equal a3d_point_clouds_merge_device(all inserted clouds under their
+ *   poses, in insertion order) followed by a3d_point_clouds_voxel_downsample_device(voxel_size, origin): points, normals,
+ *   order and winner indices, however the inserts were grouped into calls and whatever the table's size history was.
+ * Sequence numbers: point i of cloud j of a call gets seq = total + sum(len[0..j)) + i, where total is the number of points
+ * ever offered to the map; dropped points (the downsample's drop rule) consume a number too, so seq is the point's index
+ * in the merged cloud, and the winner of a cell minimises bits(dist) << 32 | seq over everything inserted so far.
+ * Reservation: the table is open-addressing with a power-of-two slot count; before it launches, an insert of L points
+ * makes sure slots >= 2 * (cells + L) and otherwise moves the map into the next sufficient power of two (one growth).  The
+ * table is allocated by the first insert that offers a point, at max(that rule, 2 * reserve_cells, 64) slots, which is no
+ * growth.  Device memory: 16 + 12 (+ 12 with normals) bytes per slot, from the context's block pool.
+ * Limits: total + L must stay below 2^32 - 2^21 (one tile span), else A3D_INVALID_PARAMETER and nothing changes;
+ * renumbering a long-lived map is NOT built.  Neither are removal or ageing of cells, colours, multi-GPU maps.
+ * Every call is host-synchronous (one wait, at its end) and ordered on the context's stream; a map belongs to its context
+ * and must be freed before it. */
+typedef struct a3d_voxel_map a3d_voxel_map;
+typedef struct a3d_voxel_map_stats {
+  uint64_t cells;         /* occupied cells */
+  uint64_t slots;         /* slots of the table (0 before the first point) */
+  uint64_t total;         /* points ever offered, dropped ones included: the next sequence number */
+  uint64_t dropped_total; /* of those, dropped by the drop rule */
+  uint64_t growths;       /* times the table was moved into a larger one */
+} a3d_voxel_map_stats;
+
+/* A new, empty map of pitch voxel_size anchored at origin (NULL = (0,0,0)); with_normals != 0: the map keeps a normal per
+ * cell and every inserted cloud must have normals.  reserve_cells (0 allowed, < 2^32): cells the first table has room for
+ * without growing.  Decided on the host, nothing is launched or allocated on the device: a NULL ctx or out, a voxel_size
+ * that is not finite or <= 0, a non-finite origin are A3D_INVALID_PARAMETER. */
+a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
+                             uint64_t reserve_cells, a3d_voxel_map** out);
+/* Inserts n resident clouds (device pointers on the map's context) under poses_host[i] (NULL = as they are, bit for bit;
+ * otherwise Transform::transform_vector / transform_normal as a3d_point_clouds_merge_device).  out_dropped (NULL ok): [n],
+ * the dropped points of each cloud; out_cells (NULL ok): the map's occupied cells afterwards.
+ * Decided on the host before anything is launched, and then nothing is inserted from the whole call: n == 0 is A3D_OK and
+ * touches nothing; a NULL map or d_clouds, a cloud of 2^32 points or more, NULL points of a non-empty cloud and the limit
+ * above are A3D_INVALID_PARAMETER; a non-empty cloud without normals offered to a map with normals is A3D_MISSING_FIELD.
+ * A cloud with len == 0 may have null pointers.  A3D_HIP_ERROR if the table ever filled up (it cannot). */
+a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
+                                uint64_t n, uint64_t* out_dropped, uint64_t* out_cells);
+/* Writes the occupied cells' rows in ascending seq — the order the downsample gives on the merged cloud, the same bits on
+ * every run — into d_out_points (room for `capacity` points), d_out_normals (NULL ok; non-NULL on a map without normals
+ * -> A3D_MISSING_FIELD) and d_out_index (NULL ok): the seq of each row, u32.  *out_len = cells.  capacity < cells ->
+ * A3D_INVALID_PARAMETER, *out_len = cells, nothing written.  A NULL map, d_out_points or out_len, or outputs whose first
+ * `capacity` rows overlap one another, are A3D_INVALID_PARAMETER.  The map is not changed; inserts may continue.
+ * Scratch memory (context-owned, shared with the calls above): total / 8 bytes of bitmap and total / 16 of prefixes. */
+a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint32_t* d_out_index,
+                                 uint64_t capacity, uint64_t* out_len);
+a3d_status a3d_voxel_map_get_stats(const a3d_voxel_map* map, a3d_voxel_map_stats* out);
+/* Empties the map and keeps its allocation: cells, total and dropped_total are 0 again (sequence numbers restart). */
+a3d_status a3d_voxel_map_clear(a3d_voxel_map* map);
+void a3d_voxel_map_free(a3d_voxel_map* map);
+
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
 /* R3dTree::new(&points): `points` [n][3] f32 in host memory are uploaded and the tree is built ON THE DEVICE
