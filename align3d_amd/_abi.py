@@ -144,6 +144,7 @@ SIGNATURES = {
     "a3d_context_synchronize": (_ST, [_P]),
     "a3d_context_stream": (_P, [_P]),
     "a3d_context_device": (C.c_int32, [_P]),
+    "a3d_context_num_cus": (C.c_int32, [_P]),
     "a3d_timer_start": (_ST, [_P]),
     "a3d_timer_stop": (_ST, [_P, C.POINTER(C.c_float)]),
     "a3d_malloc": (_ST, [_P, C.c_size_t, _PP]),

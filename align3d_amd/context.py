@@ -46,6 +46,10 @@ class Context:
         """The HIP device the context sits on (a3d_context_device)."""
         return int(self.lib.a3d_context_device(self.handle))
 
+    def num_cus(self):
+        """The compute units of that device (a3d_context_num_cus): what the launch geometries are sized by."""
+        return int(self.lib.a3d_context_num_cus(self.handle))
+
     def synchronize(self):
         _abi.check(self.lib.a3d_context_synchronize(self.handle))
 

@@ -610,8 +610,11 @@ __device__ __forceinline__ void head_sum_and_advance(uint32_t state_bits, const 
           sum1 += (double)__uint_as_float((unsigned)(v[k] >> 32));
         }
       }
-      // what is left (at most 256 tiles for this launch geometry) in ONE round of loads: up to 32 in flight per thread,
-      // masked — a lone pair's 150-200 tiles took four dependent rounds of eight; tile order as before, so the same bits
+      // what is left in ONE round of loads: up to 32 in flight per thread, masked — a lone pair's 150-200 tiles took four
+      // dependent rounds of eight; tile order as before, so the same bits.  The loop above ends with t + 248 >= tiles, so
+      // the 32 slots t, t + 8, ..., t + 248 reach every tile of this slice that is left, whatever the tile count: the
+      // product geometry gives at most 256 tiles (one block per CU) and never enters the loop twice, the diagnostics
+      // knobs A3D_PCLB_BLOCK / A3D_PCLB_BLOCKS_PER_CU give over 1 000 (several loop rounds and a masked tail).
       if (t + 56 < tiles) {
         unsigned long long v[32];
 #pragma unroll

@@ -179,6 +179,9 @@ void* a3d_context_stream(a3d_context* ctx);
 /* The HIP device the context was created on (-1 for a null context): what a rank of a multi-process job checks against
  * its LOCAL_RANK before it does any work (bench.py). */
 int32_t a3d_context_device(a3d_context* ctx);
+/* The compute units of that device (0 for a null context): the number the launch geometries are sized by (one block per
+ * CU for Icp and IcpBatch), which a test needs to say how many blocks a pass is cut into. */
+int32_t a3d_context_num_cus(a3d_context* ctx);
 
 /* hipEvent pair on the context stream: start, ..., stop -> elapsed milliseconds (stop synchronises). */
 a3d_status a3d_timer_start(a3d_context* ctx);
