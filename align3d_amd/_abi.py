@@ -198,6 +198,11 @@ SIGNATURES = {
         [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
     "a3d_voxel_map_extract": (_ST, [_P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "a3d_voxel_map_retain": (
+        _ST,
+        [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+         C.POINTER(C.c_uint64)],
+    ),
     "a3d_voxel_map_get_stats": (_ST, [_P, C.POINTER(VoxelMapStatsC)]),
     "a3d_voxel_map_clear": (_ST, [_P]),
     "a3d_voxel_map_free": (None, [_P]),

@@ -28,6 +28,17 @@
 // order depends on which colliding key claimed first, i.e. on timing): a bitmap of `total` bits in scratch, set per
 // occupied slot (32-bit atomicOr), counted per tile, turned into one exclusive prefix per 64-bit word, and a last pass over
 // the slots writes each row to prefix(word of seq) + popcount(lower bits of the word).
+//
+// Retain rebuilds the table from the cells that pass a rule (seq >= min_seq, row inside a box) and numbers the survivors
+// 0 ... k-1 in their old order; afterwards the map is a new map into which the surviving rows went as one cloud without
+// a pose.  That holds because a slot's row is the very f32 point its key and bits(dist) were computed from: the key and
+// the distance half of `best` are kept, and only the seq half is replaced by the survivor's rank.  Five launches,
+// whatever the sizes: the extract's mark pass with the rule, its count and prefix passes unchanged, a thread per mark
+// (callers' sequence numbers translated to the new numbering; `total` is translated too, which gives k), and a pass
+// over the old slots that claims every survivor's key in a NEW table (the growth rehash with a renumbered `best`).  The
+// new table's slot count follows from k, which the host learns only at the call's one wait: the block is sized for
+// every old cell, the rebuild derives slots and the arrays' places from k on the device, and the host derives the same
+// after the wait.  The old table is only read, so a failure of any kind leaves the map as it was.
 #include <cmath>
 #include <vector>
 
@@ -216,16 +227,46 @@ __global__ void __launch_bounds__(VM_THREADS)
   if ((threadIdx.x & 63u) == 0 && n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
 }
 
-// Extract 1: bit seq of the bitmap for every occupied slot (32-bit halves of the 64-bit words, little endian).
-__global__ void __launch_bounds__(VM_THREADS)
-    voxel_map_mark_kernel(const VoxelSlot* __restrict__ table, unsigned long long slots, uint32_t* __restrict__ bitmap32,
-                          unsigned long long total) {
+// The survival rule of a retain: seq >= min_seq and lo <= row <= hi per axis, plain f32 compares on the stored bits (no
+// box: -inf / +inf, which every stored row passes: a kept point is finite).
+struct RetainRule {
+  uint32_t min_seq;  // min(min_seq, total)
+  float lo[3], hi[3];
+};
+
+// The body of both mark passes.  RETAIN: only the slots that pass the rule.
+template <bool RETAIN>
+__device__ __forceinline__ void mark_slots(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
+                                           unsigned long long slots, uint32_t* __restrict__ bitmap32,
+                                           unsigned long long total, const RetainRule& rule) {
   for (unsigned long long s = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; s < slots;
        s += (unsigned long long)gridDim.x * VM_THREADS) {
     if (table[s].key == VX_EMPTY) continue;
     const uint32_t seq = (uint32_t)table[s].best;
+    if (RETAIN) {
+      if (seq < rule.min_seq) continue;
+      const f32x3 p = *(const f32x3_u*)(points + 3 * (size_t)s);
+      if (!(p.x >= rule.lo[0] && p.x <= rule.hi[0] && p.y >= rule.lo[1] && p.y <= rule.hi[1] && p.z >= rule.lo[2] &&
+            p.z <= rule.hi[2]))
+        continue;
+    }
     if (seq < total) atomicOr(&bitmap32[seq >> 5], 1u << (seq & 31u));
   }
+}
+
+// Extract 1: bit seq of the bitmap for every occupied slot (32-bit halves of the 64-bit words, little endian).
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_mark_kernel(const VoxelSlot* __restrict__ table, unsigned long long slots, uint32_t* __restrict__ bitmap32,
+                          unsigned long long total) {
+  mark_slots<false>(table, nullptr, slots, bitmap32, total, RetainRule{});
+}
+
+// Retain 1: bit seq of the bitmap for every occupied slot that survives.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_mark_retained_kernel(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
+                                   unsigned long long slots, uint32_t* __restrict__ bitmap32, unsigned long long total,
+                                   RetainRule rule) {
+  mark_slots<true>(table, points, slots, bitmap32, total, rule);
 }
 
 // Extract 2: tile_counts[tile] = set bits of the tile's words (a tile: chunks_per_tile * VM_THREADS 64-bit words).
@@ -309,6 +350,92 @@ __global__ void __launch_bounds__(VM_THREADS)
     if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)s);
     if (out_index) out_index[dst] = seq;
   }
+}
+
+// The set bits below bit `m` of the bitmap, m <= total.  m = total with total a multiple of 64 names the word one past
+// the last: it is answered from the last word.
+__device__ __forceinline__ unsigned long long rank_below(const unsigned long long* __restrict__ bitmap,
+                                                         const uint32_t* __restrict__ word_prefix, uint32_t n_words,
+                                                         unsigned long long m) {
+  const bool past = (m >> 6) >= n_words;
+  const unsigned long long w = past ? n_words - 1 : m >> 6;
+  const unsigned long long below = past ? ~0ull : (1ull << (m & 63u)) - 1ull;
+  return (unsigned long long)word_prefix[w] + (unsigned long long)__builtin_popcountll(bitmap[w] & below);
+}
+
+// Retain 4: out[i] = survivors whose old seq is below marks[i], a thread per mark.  The host appends `total` as the last
+// mark: its answer is k, the number of survivors, which retain 5 reads from out[n - 1].
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_marks_kernel(const unsigned long long* __restrict__ bitmap, const uint32_t* __restrict__ word_prefix,
+                           uint32_t n_words, unsigned long long total, const unsigned long long* __restrict__ marks,
+                           unsigned long long n, unsigned long long* __restrict__ out) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; i < n;
+       i += (unsigned long long)gridDim.x * VM_THREADS)
+    out[i] = rank_below(bitmap, word_prefix, n_words, min(marks[i], total));
+}
+
+// A table of `slots` slots inside a block: slots | point rows | normal rows, as ensure_slots lays them out.
+struct TableLayout {
+  size_t points_at, normals_at, end;
+};
+__host__ __device__ __forceinline__ TableLayout table_layout(unsigned long long slots, bool with_normals) {
+  const size_t table_bytes = ((size_t)slots * sizeof(VoxelSlot) + 255) & ~(size_t)255;
+  const size_t row_bytes = ((size_t)slots * 12 + 255) & ~(size_t)255;
+  return TableLayout{table_bytes, table_bytes + row_bytes, table_bytes + row_bytes * (with_normals ? 2 : 1)};
+}
+// The slots of a map of k > 0 retained cells: the smallest power of two >= max(2 k, min_slots), min_slots the power of two
+// of an empty map (max(2 * reserve_cells, 64)).  Host and device evaluate it alike.
+__host__ __device__ __forceinline__ unsigned long long retained_slots(unsigned long long k, unsigned long long min_slots) {
+  unsigned long long slots = min_slots;
+  while (slots < 2 * k) slots <<= 1;
+  return slots;
+}
+
+// Retain 5: every surviving slot of the old table (its bit is set: a seq belongs to one slot) into the new one under
+// its rank among the survivors, the new seq; the distance half of `best` stays.  The new table's size follows from k,
+// which only the device knows yet: the block has room for max_slots (the size for every old cell) and its first
+// max_slots slots are VX_EMPTY.  Counts the new table's cells.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_rebuild_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                             const float* __restrict__ old_normals, unsigned long long old_slots,
+                             const unsigned long long* __restrict__ bitmap, const uint32_t* __restrict__ word_prefix,
+                             unsigned long long total, const unsigned long long* __restrict__ k_word, char* new_base,
+                             unsigned long long min_slots, unsigned long long max_slots, uint32_t with_normals,
+                             unsigned long long* __restrict__ cell_count, unsigned long long* __restrict__ fault) {
+  const unsigned long long k = *k_word;
+  if (2 * k > max_slots) {  // (cannot happen: k <= the old cells; a bound on every store below)
+    if (threadIdx.x == 0) atomicMax(fault, 1ull);
+    return;
+  }
+  const unsigned long long slots = retained_slots(k, min_slots);  // <= max_slots
+  const TableLayout lay = table_layout(slots, with_normals != 0);
+  const MapTable m{(VoxelSlot*)new_base, (float*)(new_base + lay.points_at),
+                   with_normals ? (float*)(new_base + lay.normals_at) : nullptr, slots - 1, cell_count};
+  uint32_t n_claimed = 0;
+  for (unsigned long long o = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; o < old_slots;
+       o += (unsigned long long)gridDim.x * VM_THREADS) {
+    const unsigned long long key = old_table[o].key;
+    if (key == VX_EMPTY) continue;
+    const unsigned long long best = old_table[o].best;
+    const uint32_t seq = (uint32_t)best;
+    if (seq >= total) continue;  // (cannot happen, as in the extract)
+    const unsigned long long bits = bitmap[seq >> 6];
+    if (!(bits >> (seq & 63u) & 1ull)) continue;  // removed
+    const unsigned long long new_seq =
+        (unsigned long long)word_prefix[seq >> 6] + (unsigned long long)__builtin_popcountll(bits & ((1ull << (seq & 63u)) - 1ull));
+    unsigned long long s;
+    bool claimed = false;
+    if (new_seq >= k || !claim_slot(m.table, m.mask, key, &s, &claimed) || !claimed) {  // (keys are unique: a fresh claim)
+      atomicMax(fault, 1ull);
+      continue;
+    }
+    ++n_claimed;
+    m.table[s].best = (best & 0xFFFFFFFF00000000ull) | new_seq;
+    *(f32x3_u*)(m.points + 3 * (size_t)s) = *(const f32x3_u*)(old_points + 3 * (size_t)o);
+    if (m.normals) *(f32x3_u*)(m.normals + 3 * (size_t)s) = *(const f32x3_u*)(old_normals + 3 * (size_t)o);
+  }
+  n_claimed = wave_sum(n_claimed);
+  if ((threadIdx.x & 63u) == 0 && n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
 }
 
 uint32_t slot_blocks(uint64_t slots) {
@@ -405,7 +532,7 @@ a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* 
                 "a3d_voxel_map_insert: the map has normals and a cloud has none (nothing was inserted)");
     // (a sum of < 2^32 terms below 2^32 cannot wrap 64 bits; the limit below bounds it)
     A3D_REQUIRE(map->total + incoming + c.len + VM_SEQ_MARGIN < (1ull << 32), A3D_INVALID_PARAMETER,
-                "a3d_voxel_map_insert: the map would pass 2^32 - 2^21 offered points (renumbering is not built)");
+                "a3d_voxel_map_insert: the map would pass 2^32 - 2^21 offered points (a3d_voxel_map_retain renumbers it)");
     MapJob j{};
     j.points = c.points, j.normals = map->with_normals ? c.normals : nullptr;
     j.len = (uint32_t)c.len;
@@ -524,6 +651,130 @@ a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float*
   A3D_HIP_TRY(hipGetLastError());
   // host-synchronous: the caller may read or free the outputs right after
   A3D_HIP_TRY(hipStreamSynchronize(s));
+  return A3D_OK;
+}
+
+a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], const float box_max[3], uint64_t min_seq,
+                                const uint64_t* marks, uint64_t n_marks, uint64_t* out_marks, uint64_t* out_removed) {
+  A3D_REQUIRE(map, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE((box_min == nullptr) == (box_max == nullptr), A3D_INVALID_PARAMETER,
+              "a3d_voxel_map_retain: box_min and box_max are both NULL or both given");
+  A3D_REQUIRE(n_marks == 0 || (marks && out_marks), A3D_INVALID_PARAMETER, "a3d_voxel_map_retain: marks without an array");
+  A3D_REQUIRE(n_marks < (1ull << 32), A3D_INVALID_PARAMETER, "a3d_voxel_map_retain: 2^32 marks or more");
+  RetainRule rule{};
+  for (int a = 0; a < 3; ++a) {
+    rule.lo[a] = box_min ? box_min[a] : -INFINITY, rule.hi[a] = box_max ? box_max[a] : INFINITY;
+    A3D_REQUIRE(!std::isnan(rule.lo[a]) && !std::isnan(rule.hi[a]), A3D_INVALID_PARAMETER,
+                "a3d_voxel_map_retain: a bound of the box is NaN");
+  }
+  if (!map->block || map->cells == 0) {  // nothing to keep: the map is as new
+    A3D_TRY(a3d_voxel_map_clear(map));
+    for (uint64_t i = 0; i < n_marks; ++i) out_marks[i] = 0;
+    if (out_removed) *out_removed = 0;
+    return A3D_OK;
+  }
+  const uint64_t total = map->total;  // >= 1: a cell holds the seq of an offered point
+  rule.min_seq = (uint32_t)std::min<uint64_t>(min_seq, total);
+  a3d_context* ctx = map->ctx;
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  // scratch, as the extract: one count per tile | the bitmap | one prefix per word; then the marks (with `total` appended:
+  // its translation is k), their translations and the fault word
+  const uint64_t n_words = (total + 63) / 64, n_all = n_marks + 1;
+  uint64_t tiles = 0;
+  uint32_t first_tile = 0, chunks_per_tile = 0;
+  A3D_TRY(plan_tiles(n_words, VM_THREADS, VM_MAX_TILES, &tiles, &first_tile, &chunks_per_tile));
+  const size_t counts_bytes = pad256(tiles * 4), bitmap_bytes = pad256(n_words * 8), prefix_bytes = pad256(n_words * 4);
+  const size_t marks_bytes = pad256(n_all * 8), out_bytes = pad256((n_all + 1) * 8);
+  void* region = nullptr;
+  A3D_TRY(ctx_scratch(ctx, 3, counts_bytes + bitmap_bytes + prefix_bytes + marks_bytes + out_bytes, &region));
+  uint32_t* d_tile_counts = (uint32_t*)region;
+  unsigned long long* d_bitmap = (unsigned long long*)((char*)region + counts_bytes);
+  uint32_t* d_prefix = (uint32_t*)((char*)region + counts_bytes + bitmap_bytes);
+  unsigned long long* d_marks = (unsigned long long*)((char*)region + counts_bytes + bitmap_bytes + prefix_bytes);
+  unsigned long long* d_out = (unsigned long long*)((char*)d_marks + marks_bytes);  // [n_all] translations, then the fault word
+  unsigned long long* d_fault = d_out + n_all;
+  // the new table: room for every old cell (k is known on the device only until the wait); its cell count at the end
+  uint64_t min_slots = 64;
+  while (min_slots < 2 * map->reserve_cells) min_slots <<= 1;
+  const uint64_t max_slots = retained_slots(map->cells, min_slots);
+  const size_t bytes = table_layout(max_slots, map->with_normals).end + 256;
+  void* block = nullptr;
+  size_t block_bytes = 0;
+  A3D_TRY(ctx_block_alloc(ctx, bytes, &block, &block_bytes));
+  char* base = (char*)block;
+  unsigned long long* d_cell_count = (unsigned long long*)(base + bytes - 256);
+  std::vector<unsigned long long> h_marks(marks, marks + n_marks), h_out(n_all + 1);
+  h_marks.push_back(total);
+  hipStream_t s = ctx->stream;
+  const dim3 over_slots(slot_blocks(map->slots)), over_words((uint32_t)tiles), block_dim(VM_THREADS);
+  const dim3 over_marks((uint32_t)std::min<uint64_t>((n_all + VM_THREADS - 1) / VM_THREADS, VM_MAX_SLOT_BLOCKS));
+  hipError_t e = hipMemsetAsync(d_bitmap, 0, bitmap_bytes, s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_fault, 0, 8, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_marks, h_marks.data(), n_all * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(base, 0xFF, max_slots * sizeof(VoxelSlot), s);  // every key VX_EMPTY
+  if (e == hipSuccess) e = hipMemsetAsync(d_cell_count, 0, 8, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(voxel_map_mark_retained_kernel, over_slots, block_dim, 0, s, (const VoxelSlot*)map->table,
+                       (const float*)map->points, (unsigned long long)map->slots, (uint32_t*)d_bitmap,
+                       (unsigned long long)total, rule);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(voxel_map_count_kernel, over_words, block_dim, 0, s, (const unsigned long long*)d_bitmap,
+                       (uint32_t)n_words, chunks_per_tile, d_tile_counts);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(voxel_map_prefix_kernel, over_words, block_dim, 0, s, (const unsigned long long*)d_bitmap,
+                       (uint32_t)n_words, chunks_per_tile, (const uint32_t*)d_tile_counts, d_prefix);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(voxel_map_marks_kernel, over_marks, block_dim, 0, s, (const unsigned long long*)d_bitmap,
+                       (const uint32_t*)d_prefix, (uint32_t)n_words, (unsigned long long)total,
+                       (const unsigned long long*)d_marks, (unsigned long long)n_all, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(voxel_map_rebuild_kernel, over_slots, block_dim, 0, s, (const VoxelSlot*)map->table,
+                       (const float*)map->points, (const float*)map->normals, (unsigned long long)map->slots,
+                       (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix, (unsigned long long)total,
+                       (const unsigned long long*)(d_out + n_marks), base, (unsigned long long)min_slots,
+                       (unsigned long long)max_slots, map->with_normals ? 1u : 0u, d_cell_count, d_fault);
+    e = hipGetLastError();
+  }
+  unsigned long long counted = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, (n_all + 1) * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&counted, d_cell_count, 8, hipMemcpyDeviceToHost, s);
+  // host-synchronous, the one wait of the call
+  const hipError_t waited = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = waited;
+  const unsigned long long k = h_out[n_marks];
+  if (e != hipSuccess || h_out[n_all] != 0 || counted != k || k > map->cells) {  // the old table, untouched, stays the map's
+    ctx_block_release(ctx, block, block_bytes);
+    if (e != hipSuccess)
+      set_error("a3d_voxel_map_retain: rebuilding the table failed: %s", hipGetErrorString(e));
+    else
+      set_error("a3d_voxel_map_retain: the rebuilt table does not hold the survivors (the map is unchanged)");
+    return A3D_HIP_ERROR;
+  }
+  const uint64_t removed = map->cells - k;
+  if (k == 0) {  // as a3d_voxel_map_clear: the allocation and its slots stay
+    ctx_block_release(ctx, block, block_bytes);
+    A3D_TRY(a3d_voxel_map_clear(map));
+  }
+  for (uint64_t i = 0; i < n_marks; ++i) out_marks[i] = h_out[i];
+  if (out_removed) *out_removed = removed;
+  if (k == 0) return A3D_OK;
+  ctx_block_release(ctx, map->block, map->block_bytes);  // (nothing enqueued reads it any more)
+  const uint64_t slots = retained_slots(k, min_slots);
+  const TableLayout lay = table_layout(slots, map->with_normals);
+  map->block = block, map->block_bytes = block_bytes, map->slots = slots;
+  map->table = (VoxelSlot*)base;
+  map->points = (float*)(base + lay.points_at);
+  map->normals = map->with_normals ? (float*)(base + lay.normals_at) : nullptr;
+  map->cell_count = d_cell_count;
+  map->cells = map->total = k, map->dropped_total = 0;
   return A3D_OK;
 }
 

@@ -602,6 +602,49 @@ class DeviceVoxelMap:
     def total(self):
         return self.stats()["total"]
 
+    def retain(self, box=None, min_seq=0, marks=None):
+        """Keeps the cells whose winner has sequence number >= min_seq and, with box = (min3, max3), whose stored point
+        lies inside the closed box, and numbers them 0 ... k-1 in their old order: the map is then a new map into which
+        the surviving rows went as one cloud (a3d_voxel_map_retain), total() is k and the table has shrunk to fit.
+        Returns the number of removed cells, or (removed, new_marks) when `marks` (sequence numbers, e.g. total() at frame
+        boundaries) is given: new_marks[i], a numpy uint64 array, is the survivors below marks[i], the same boundary in
+        the new numbering."""
+        lo = hi = None
+        if box is not None:
+            try:
+                lo, hi = box
+            except (TypeError, ValueError):
+                raise _abi.InvalidParameter("DeviceVoxelMap.retain: the box is (min3, max3)") from None
+            bounds = []
+            for b in (lo, hi):
+                b = np.ascontiguousarray(b, np.float32).reshape(-1)
+                if b.size != 3:
+                    raise _abi.InvalidParameter("DeviceVoxelMap.retain: a corner of the box has three coordinates")
+                bounds.append((C.c_float * 3)(*b.tolist()))
+            lo, hi = bounds
+        min_seq = int(min_seq)
+        if not 0 <= min_seq < 1 << 64:
+            raise _abi.InvalidParameter("DeviceVoxelMap.retain: min_seq is a sequence number (0 <= min_seq < 2^64)")
+        old = new = None
+        n = 0
+        if marks is not None:
+            m = np.asarray(marks)
+            if m.ndim != 1 or (m.size and (m.dtype.kind not in "iu" or (m.dtype.kind == "i" and (m < 0).any()))):
+                raise _abi.InvalidParameter("DeviceVoxelMap.retain: marks is a 1-d array of sequence numbers")
+            m = np.ascontiguousarray(m, np.uint64)
+            n = m.size
+            out = np.zeros(n, np.uint64)
+            if n:
+                old, new = m.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64))
+        removed = C.c_uint64()
+        _abi.check(self.ctx.lib.a3d_voxel_map_retain(self.handle, lo, hi, min_seq, old, n, new, C.byref(removed)),
+                   "a3d_voxel_map_retain")
+        return int(removed.value) if marks is None else (int(removed.value), out)
+
+    def compact(self):
+        """retain() with nothing to remove: renumbers the cells 0 ... cells-1 and shrinks the table to fit."""
+        return self.retain()
+
     def clear(self):
         """Empties the map and keeps its allocation; sequence numbers restart at 0."""
         _abi.check(self.ctx.lib.a3d_voxel_map_clear(self.handle), "a3d_voxel_map_clear")

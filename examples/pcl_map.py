@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A map from a recorded sequence without leaving the device:
-    python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N] [--voxel V [--online [--check-batch]]] [--out map.npy]
+    python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
+        [--voxel V [--online [--check-batch | --window-box R | --window-frames W]]] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -9,8 +10,13 @@ back in one resident cloud (one launch).  With --voxel V the map is then thinned
 frame to map.  With --online the thinned map is built the way a live caller would, frame by frame into a persistent
 DeviceVoxelMap (insert per frame, one extract at the end) instead of merge + voxel_downsample of everything: no merged
 cloud exists at any time, and the lines it prints are the same.  --check-batch runs the batch path as well, only to
-assert that the two maps are the same bits.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+assert that the two maps are the same bits.  --window-box R and --window-frames W keep the online map LOCAL, the way
+an odometry loop that runs for hours must: after each insert DeviceVoxelMap.retain drops the cells outside the box of
+half-side R (metres) around the current camera position, or the cells whose point is older than the last W frames
+(frame boundaries are recorded as total() and carried through every retain by its `marks`).  A retain also renumbers the
+cells, so total(), printed per frame beside the cell count, stays bounded instead of running towards 2^32.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
+import collections
 import os
 import sys
 
@@ -28,12 +34,23 @@ ap.add_argument("--voxel", type=float, default=None, help="thin the map to one p
 ap.add_argument("--online", action="store_true", help="with --voxel: build the thinned map by inserting frame by frame")
 ap.add_argument("--check-batch", action="store_true",
                 help="with --online: also run merge + voxel_downsample and assert that the online map is the same bits")
+ap.add_argument("--window-box", type=float, default=None, metavar="R",
+                help="with --online: after each insert keep only the cells within R metres (per axis) of the camera")
+ap.add_argument("--window-frames", type=int, default=None, metavar="W",
+                help="with --online: after each insert keep only the cells whose point came with the last W frames")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file")
 args = ap.parse_args()
 if args.online and not args.voxel:
     ap.error("--online needs --voxel")
 if args.check_batch and not args.online:
     ap.error("--check-batch needs --online")
+windowed = args.window_box is not None or args.window_frames is not None
+if windowed and not args.online:
+    ap.error("--window-box and --window-frames need --online")
+if windowed and args.check_batch:
+    ap.error("--check-batch compares whole maps: not with --window-box or --window-frames")
+if args.window_frames is not None and args.window_frames < 1:
+    ap.error("--window-frames keeps at least one frame")
 
 ctx = Context(0)
 ds = SlamTbDataset.load(args.dataset)
@@ -67,9 +84,26 @@ def thinned_by_batch():
 
 if args.online:
     online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None)
-    for cloud, pose in zip(clouds, camera_to_world):  # what a live caller does as each frame arrives
+    offered = 0
+    starts = collections.deque()  # --window-frames: the first sequence number of each kept frame, in the map's numbering
+    for k, (cloud, pose) in enumerate(zip(clouds, camera_to_world)):  # what a live caller does as each frame arrives
+        if args.window_frames is not None:
+            starts.append(online.total())
         online.insert(cloud, pose)
-    offered, world_map = online.total(), online.extract()
+        offered += cloud.len()
+        if args.window_box is not None:
+            centre = pose.translation()
+            _, marks = online.retain(box=(centre - np.float32(args.window_box), centre + np.float32(args.window_box)),
+                                     marks=np.asarray(starts, np.uint64))
+            starts = collections.deque(marks.tolist())
+        if args.window_frames is not None:
+            while len(starts) > args.window_frames:
+                starts.popleft()
+            _, marks = online.retain(min_seq=starts[0], marks=np.asarray(starts, np.uint64))  # starts[0] becomes 0
+            starts = collections.deque(marks.tolist())
+        if windowed:
+            print(f"frame {k}: {online.cells()} cells, total {online.total()} (offered so far: {offered})")
+    world_map = online.extract()
     online.free()
     if args.check_batch:  # the batch path, for this comparison only
         _, batch_map = thinned_by_batch()

@@ -551,7 +551,8 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
  * table is allocated by the first insert that offers a point, at max(that rule, 2 * reserve_cells, 64) slots, which is no
  * growth.  Device memory: 16 + 12 (+ 12 with normals) bytes per slot, from the context's block pool.
  * Limits: total + L must stay below 2^32 - 2^21 (one tile span), else A3D_INVALID_PARAMETER and nothing changes;
- * renumbering a long-lived map is NOT built.  Neither are removal or ageing of cells, colours, multi-GPU maps.
+ * a3d_voxel_map_retain renumbers a long-lived map, and removes cells by place and by age.  Colours and multi-GPU maps are
+ * NOT built.
  * Every call is host-synchronous (one wait, at its end) and ordered on the context's stream; a map belongs to its context
  * and must be freed before it. */
 typedef struct a3d_voxel_map a3d_voxel_map;
@@ -586,6 +587,32 @@ a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* 
  * Scratch memory (context-owned, shared with the calls above): total / 8 bytes of bitmap and total / 16 of prefixes. */
 a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint32_t* d_out_index,
                                  uint64_t capacity, uint64_t* out_len);
+/* Rebuilds the map from the cells that survive and numbers them anew.  A cell survives iff its winner's seq >= min_seq
+ * and, if a box is given, its stored row p has box_min[k] <= p[k] <= box_max[k] for k = 0, 1, 2: plain f32 comparisons
+ * on the stored bits (the cell centre plays no part).  box_min and box_max are both NULL (no box) or both given; infinite
+ * bounds are allowed (a one-sided box); box_min[k] > box_max[k] keeps nothing; min_seq >= total removes everything; no
+ * box and min_seq == 0 is a pure compaction.  The contract:
+ *   Let the survivors be the k rows of a3d_voxel_map_extract that pass the rule, in extract order.  After the call the map
+ *   is indistinguishable from a new map of the same voxel_size, origin, with_normals and reserve_cells into which those k
+ *   rows, points and normals, were inserted as ONE cloud without a pose.
+ * (A cell's stored row is the very f32 point its key and bits(dist) were computed from, so offering it again without a pose
+ * gives the same key and the same distance.)  So: extract returns the k rows bit for bit with indices 0 ... k-1;
+ * get_stats gives cells = total = k and dropped_total = 0; growths is unchanged (a retain is no growth); for k > 0, slots
+ * is the smallest power of two >= max(2 k, 2 * reserve_cells, 64); every later insert, extract and retain gives exactly
+ * what it would give on that new map, and the next point offered gets seq k: the 2^32 - 2^21 limit recedes with every
+ * retain.  For k == 0 the call has the effect of a3d_voxel_map_clear: the allocation is kept and slots is what it was.
+ * Marks: a caller that ages by frame records `total` at frame boundaries, and the renumbering invalidates those records.
+ * out_marks[i] (i < n_marks) = the number of survivors whose OLD seq is < marks[i]: the same boundary in the new numbering;
+ * a mark >= the old total gives k.  marks NULL with n_marks == 0 is fine.  *out_removed (NULL ok) = cells before - k.
+ * Decided on the host before anything is launched: a NULL map, one of box_min / box_max NULL alone, a NaN bound, marks or
+ * out_marks NULL with n_marks > 0 (or n_marks >= 2^32) are A3D_INVALID_PARAMETER.  On a map that holds no table yet:
+ * A3D_OK, removed 0, every out_mark 0.  On ANY failure, one of the device included (A3D_HIP_ERROR), the map is unchanged:
+ * the old table is only read, and stays the map's if the new one cannot be allocated or built.
+ * Five launches whatever cells and slots are.  Scratch memory as the extract: total / 8 bytes of bitmap and total / 16 of
+ * prefixes (and 16 bytes per mark).  Device memory: the new table's block is sized for the cells BEFORE the call (k is
+ * known only at the call's one wait; the table inside it has the slots stated above): memory follows one retain later. */
+a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], const float box_max[3], uint64_t min_seq,
+                                const uint64_t* marks, uint64_t n_marks, uint64_t* out_marks, uint64_t* out_removed);
 a3d_status a3d_voxel_map_get_stats(const a3d_voxel_map* map, a3d_voxel_map_stats* out);
 /* Empties the map and keeps its allocation: cells, total and dropped_total are 0 again (sequence numbers restart). */
 a3d_status a3d_voxel_map_clear(a3d_voxel_map* map);
