@@ -206,6 +206,16 @@ SIGNATURES = {
     "a3d_voxel_map_get_stats": (_ST, [_P, C.POINTER(VoxelMapStatsC)]),
     "a3d_voxel_map_clear": (_ST, [_P]),
     "a3d_voxel_map_free": (None, [_P]),
+    "a3d_voxel_map_nearest_device": (_ST, [_P, _P, C.c_uint64, C.POINTER(PoseC), _P, _P]),
+    "a3d_voxel_map_icp_align_device": (
+        _ST,
+        [_P, C.POINTER(IcpParamsC), C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.POINTER(PoseC)],
+    ),
+    "a3d_voxel_map_icp_accumulate_device": (
+        _ST,
+        [_P, C.POINTER(IcpParamsC), C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.POINTER(GnStateC)],
+    ),
+    "a3d_voxel_map_icp_last_device_ms": (_ST, [_P, C.POINTER(C.c_float)]),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

@@ -1,5 +1,6 @@
 // The per-point body of Icp::align (src/icp/pcl_icp.rs:68-92), shared by the one-pair kernel (kdtree.hip) and the
-// batch kernel (pcl_icp_batch.hip) so that both compute the same bits per point.
+// batch kernel (pcl_icp_batch.hip) so that both compute the same bits per point; its tail behind the association is
+// shared with the voxel map's frame-to-map loop (voxel_map_icp.hip) as well.
 #pragma once
 #include "icp_engine.hpp"
 #include "kdtree.hpp"
@@ -10,6 +11,22 @@ struct PclGates {
   float max_distance_sqr;
   float dot_reject_max;  // reject iff -1 <= sn.tn <= dot_reject_max  (== acos(sn.tn).abs() > max_normal_angle)
 };
+
+// What follows the association (src/icp/pcl_icp.rs:74-91): the two gates, the residual and the Jacobian of the
+// point-to-plane cost, one Gauss-Newton step.  `live`: the thread holds a source point and it found a row.  p, sn: the
+// source point and normal under the pose; tp, tn: the associated row and its normal; d2: their squared distance as the
+// association computed it.  One definition for the kd-tree loop below and the voxel map's (voxel_map_icp.hip).
+__device__ __forceinline__ void pcl_point_tail(bool live, const V3& p, const V3& sn, const V3& tp, const V3& tn, float d2,
+                                               const PclGates& gates, float (&acc)[GN_ACC]) {
+  const float c = dot(sn, tn);
+  const bool keep = live && !(d2 > gates.max_distance_sqr) && !(c >= -1.0f && c <= gates.dot_reject_max);
+  if (keep) {
+    const float rr = dot(tp - p, tn);
+    const V3 tw = cross(p, tn);
+    const float J[6] = {tn.x, tn.y, tn.z, tw.x, tw.y, tw.z};
+    gn_step(acc, rr, J);
+  }
+}
 
 // The body of Icp::align's point loop (src/icp/pcl_icp.rs:68-92); grid-stride.
 template <int BLOCK>
@@ -33,16 +50,7 @@ __device__ __forceinline__ void pcl_point_loop(const KdSplits& sp, const float4*
     // the winner's record and its normal: one 16-byte gather each (the point's line was just scanned)
     const float4 win = leaves[slot], tn4 = leaf_normals[slot];
     const V3 sn = transform_normal(T, V3{nv.x, nv.y, nv.z});
-    const V3 tn{tn4.x, tn4.y, tn4.z};
-    const float c = dot(sn, tn);
-    const bool keep = i < m && !(d2 > gates.max_distance_sqr) && !(c >= -1.0f && c <= gates.dot_reject_max);
-    if (keep) {
-      const V3 tp{win.x, win.y, win.z};
-      const float rr = dot(tp - p, tn);
-      const V3 tw = cross(p, tn);
-      const float J[6] = {tn.x, tn.y, tn.z, tw.x, tw.y, tw.z};
-      gn_step(acc, rr, J);
-    }
+    pcl_point_tail(i < m, p, sn, V3{win.x, win.y, win.z}, V3{tn4.x, tn4.y, tn4.z}, d2, gates, acc);
   }
 }
 

@@ -32,7 +32,8 @@
 // Retain rebuilds the table from the cells that pass a rule (seq >= min_seq, row inside a box) and numbers the survivors
 // 0 ... k-1 in their old order; afterwards the map is a new map into which the surviving rows went as one cloud without
 // a pose.  That holds because a slot's row is the very f32 point its key and bits(dist) were computed from: the key and
-// the distance half of `best` are kept, and only the seq half is replaced by the survivor's rank.  Five launches,
+// the distance half of `best` are kept, and only the seq half is replaced by the survivor's rank.  (Reading the map as a
+// spatial index — nearest row, frame-to-map ICP — lives in voxel_map_icp.hip; the map's struct in voxel_map.hpp.)  Five launches,
 // whatever the sizes: the extract's mark pass with the rule, its count and prefix passes unchanged, a thread per mark
 // (callers' sequence numbers translated to the new numbering; `total` is translated too, which gives k), and a pass
 // over the old slots that claims every survivor's key in a NEW table (the growth rehash with a renumbered `best`).  The
@@ -42,25 +43,9 @@
 #include <cmath>
 #include <vector>
 
-#include "voxel_grid.hpp"
+#include "voxel_map.hpp"
 
 using namespace a3d;
-
-struct a3d_voxel_map {
-  a3d_context* ctx = nullptr;
-  VoxelGrid grid{};
-  bool with_normals = false;
-  uint64_t reserve_cells = 0;
-  // the device block of the current table (null until the first insert that holds a point)
-  void* block = nullptr;
-  size_t block_bytes = 0;
-  uint64_t slots = 0;
-  VoxelSlot* table = nullptr;
-  float* points = nullptr;
-  float* normals = nullptr;
-  unsigned long long* cell_count = nullptr;
-  uint64_t cells = 0, total = 0, dropped_total = 0, growths = 0;
-};
 
 namespace {
 
@@ -799,6 +784,7 @@ a3d_status a3d_voxel_map_clear(a3d_voxel_map* map) {
 void a3d_voxel_map_free(a3d_voxel_map* map) {
   if (!map) return;
   if (map->block) ctx_block_release(map->ctx, map->block, map->block_bytes);
+  voxel_map_icp_release(map);
   delete map;
 }
 

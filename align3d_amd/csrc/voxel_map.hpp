@@ -1,0 +1,32 @@
+// The persistent voxel map as its two translation units see it: voxel_map.hip (insert, extract, retain: everything
+// that changes the table) and voxel_map_icp.hip (nearest and frame-to-map ICP: the table is only read).
+#pragma once
+#include "voxel_grid.hpp"
+
+struct a3d_voxel_map {
+  a3d_context* ctx = nullptr;
+  a3d::VoxelGrid grid{};
+  bool with_normals = false;
+  uint64_t reserve_cells = 0;
+  // the device block of the current table (null until the first insert that holds a point)
+  void* block = nullptr;
+  size_t block_bytes = 0;
+  uint64_t slots = 0;
+  a3d::VoxelSlot* table = nullptr;
+  float* points = nullptr;
+  float* normals = nullptr;
+  unsigned long long* cell_count = nullptr;
+  uint64_t cells = 0, total = 0, dropped_total = 0, growths = 0;
+  // the working buffers of the frame-to-map ICP (voxel_map_icp.hip): one block of the context's, taken by the first
+  // align or accumulate and released with the map
+  void* icp_block = nullptr;
+  size_t icp_block_bytes = 0;
+  uint32_t icp_blocks = 0;  // block partials it has room for
+  hipEvent_t icp_ev0 = nullptr, icp_ev1 = nullptr;  // bracket the iteration launches of the last align
+  float icp_last_device_ms = 0.f;
+};
+
+namespace a3d {
+// Releases the ICP working buffers of a map that is being freed (voxel_map_icp.hip).
+void voxel_map_icp_release(a3d_voxel_map* map);
+}  // namespace a3d

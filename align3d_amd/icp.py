@@ -645,6 +645,74 @@ class DeviceVoxelMap:
         """retain() with nothing to remove: renumbers the cells 0 ... cells-1 and shrinks the table to fit."""
         return self.retain()
 
+    def _resident_source(self, cloud, what):
+        if not isinstance(cloud, DevicePointCloud):
+            raise TypeError(f"DeviceVoxelMap.{what} takes a DevicePointCloud (got {type(cloud).__name__}); there is no host fallback")
+        if cloud.ctx is not self.ctx:
+            raise _abi.InvalidParameter(f"DeviceVoxelMap.{what}: the cloud must live on the map's context")
+        return cloud
+
+    def nearest(self, queries, transform=None):
+        """The map's association (a3d_voxel_map_nearest_device) for every point of `queries`, a DevicePointCloud of the
+        map's context or an [m, 3] float32 array (uploaded for the call), moved by `transform` first (None: as they
+        are).  Returns host arrays (seq uint32, dist2 float32): the sequence number of the nearest stored row among the
+        27 cells around the query and the squared distance to it; 0xFFFFFFFF and +inf where there is none.  It is the
+        exact nearest row wherever that row lies within about one cell of the query, and not R3dTree.nearest."""
+        ctx = self.ctx
+        own = None
+        if isinstance(queries, DevicePointCloud):
+            d_q, m = self._resident_source(queries, "nearest").d_points, queries.n
+        else:
+            q = np.ascontiguousarray(queries, np.float32)
+            if q.ndim != 2 or q.shape[1] != 3:
+                raise _abi.InvalidParameter("DeviceVoxelMap.nearest: queries is a DevicePointCloud or an [m, 3] array")
+            m = len(q)
+            d_q = own = ctx.to_device(q) if m else None
+        seq, dist2 = np.empty(m, np.uint32), np.empty(m, np.float32)
+        if m == 0:
+            return seq, dist2
+        pose = None if transform is None else C.byref(transform.to_c())
+        d_seq = d_dist = None
+        try:
+            d_seq, d_dist = ctx.malloc(m * 4), ctx.malloc(m * 4)
+            _abi.check(ctx.lib.a3d_voxel_map_nearest_device(self.handle, d_q, m, pose, d_seq, d_dist),
+                       "a3d_voxel_map_nearest_device")
+            ctx.to_host(d_seq, seq), ctx.to_host(d_dist, dist2)
+        finally:
+            for p in (own, d_seq, d_dist):
+                if p is not None:
+                    ctx.free(p)
+        return seq, dist2
+
+    def align(self, source, params, initial=None):
+        """Frame-to-map point-to-plane ICP (a3d_voxel_map_icp_align_device): Icp.align's loop with the map's association
+        in place of the kd-tree, started from `initial` (None: Transform.eye()).  Returns the Transform that maps
+        `source` as given into the map's frame; no extract, no tree build, and the map is not changed.  Map and source
+        need normals."""
+        v = self._resident_source(source, "align").view()
+        p = params.to_c()
+        init = None if initial is None else C.byref(initial.to_c())
+        out = _abi.PoseC()
+        _abi.check(self.ctx.lib.a3d_voxel_map_icp_align_device(self.handle, C.byref(p), C.byref(v), init, C.byref(out)),
+                   "a3d_voxel_map_icp_align_device")
+        return Transform.from_c(out)
+
+    def accumulate(self, source, params, transform):
+        """One pass of align's per-point loop under `transform` (test hook, as Icp.accumulate): {H, g, ssq, count}."""
+        v = self._resident_source(source, "accumulate").view()
+        p = params.to_c()
+        t = transform.to_c()
+        g = _abi.GnStateC()
+        _abi.check(self.ctx.lib.a3d_voxel_map_icp_accumulate_device(self.handle, C.byref(p), C.byref(v), C.byref(t),
+                                                                    C.byref(g)), "a3d_voxel_map_icp_accumulate_device")
+        return g.as_dict()
+
+    def last_device_ms(self):
+        """Device time (ms) of the iteration launches of the most recent align."""
+        ms = C.c_float()
+        _abi.check(self.ctx.lib.a3d_voxel_map_icp_last_device_ms(self.handle, C.byref(ms)))
+        return ms.value
+
     def clear(self):
         """Empties the map and keeps its allocation; sequence numbers restart at 0."""
         _abi.check(self.ctx.lib.a3d_voxel_map_clear(self.handle), "a3d_voxel_map_clear")

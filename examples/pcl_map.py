@@ -9,7 +9,10 @@ back in one resident cloud (one launch).  With --voxel V the map is then thinned
 (DevicePointCloud.voxel_downsample: still on the device) and the last frame is aligned against the thinned map with Icp,
 frame to map.  With --online the thinned map is built the way a live caller would, frame by frame into a persistent
 DeviceVoxelMap (insert per frame, one extract at the end) instead of merge + voxel_downsample of everything: no merged
-cloud exists at any time, and the lines it prints are the same.  --check-batch runs the batch path as well, only to
+cloud exists at any time, and the lines it prints are the same; the last frame is then corrected against the live map
+itself (DeviceVoxelMap.align from its odometry pose: no extract, no kd-tree build, the frame in its own coordinates), and
+the correction printed is that alignment relative to the odometry pose (the map's association is not the kd-tree's, so
+its figures differ from the batch path's).  --check-batch runs the batch path as well, only to
 assert that the two maps are the same bits.  --window-box R and --window-frames W keep the online map LOCAL, the way
 an odometry loop that runs for hours must: after each insert DeviceVoxelMap.retain drops the cells outside the box of
 half-side R (metres) around the current camera position, or the cells whose point is older than the last W frames
@@ -103,6 +106,10 @@ if args.online:
             starts = collections.deque(marks.tolist())
         if windowed:
             print(f"frame {k}: {online.cells()} cells, total {online.total()} (offered so far: {offered})")
+    # frame to map against the LIVE map: no extract, no kd-tree, and the frame stays in its own coordinates: the map's
+    # association (DeviceVoxelMap.nearest) takes the tree's place and the alignment starts from the odometry pose
+    aligned = online.align(clouds[-1], IcpParams.default(), initial=camera_to_world[-1])
+    correction = aligned * camera_to_world[-1].inverse()
     world_map = online.extract()
     online.free()
     if args.check_batch:  # the batch path, for this comparison only
@@ -118,14 +125,15 @@ else:
     world_map = DevicePointCloud.merge(clouds, camera_to_world)  # the last step: all frames in one coordinate system
 if args.voxel:
     print(f"voxel {args.voxel}: {offered} points -> {world_map.len()}")
-    # frame to map: the last frame, brought to the world by its odometry pose, against the thinned map; what Icp
-    # returns is the correction the map asks of that pose
-    last = camera_to_world[-1] * clouds[-1]
-    icp = Icp(ctx, IcpParams.default(), world_map)
-    correction = icp.align(last)
+    if not args.online:
+        # frame to map: the last frame, brought to the world by its odometry pose, against the thinned map; what Icp
+        # returns is the correction the map asks of that pose
+        last = camera_to_world[-1] * clouds[-1]
+        icp = Icp(ctx, IcpParams.default(), world_map)
+        correction = icp.align(last)
+        icp.free(), last.free()
     print(f"last frame against the thinned map: correction angle {correction.angle():.3e} rad, "
           f"translation {float(np.linalg.norm(correction.t)):.3e}")
-    icp.free(), last.free()
 points, _ = world_map.download()
 finite = points[np.isfinite(points).all(axis=1)]
 print(f"{len(clouds)} frames, map of {world_map.len()} points" + (" with normals" if world_map.d_normals is not None else ""))

@@ -551,8 +551,9 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
  * table is allocated by the first insert that offers a point, at max(that rule, 2 * reserve_cells, 64) slots, which is no
  * growth.  Device memory: 16 + 12 (+ 12 with normals) bytes per slot, from the context's block pool.
  * Limits: total + L must stay below 2^32 - 2^21 (one tile span), else A3D_INVALID_PARAMETER and nothing changes;
- * a3d_voxel_map_retain renumbers a long-lived map, and removes cells by place and by age.  Colours and multi-GPU maps are
- * NOT built.
+ * a3d_voxel_map_retain renumbers a long-lived map, and removes cells by place and by age.  The map is also a spatial index:
+ * a3d_voxel_map_nearest_device and a3d_voxel_map_icp_align_device (below) read it without an extract or a kd-tree build.
+ * Colours and multi-GPU maps are NOT built.
  * Every call is host-synchronous (one wait, at its end) and ordered on the context's stream; a map belongs to its context
  * and must be freed before it. */
 typedef struct a3d_voxel_map a3d_voxel_map;
@@ -617,6 +618,55 @@ a3d_status a3d_voxel_map_get_stats(const a3d_voxel_map* map, a3d_voxel_map_stats
 /* Empties the map and keeps its allocation: cells, total and dropped_total are 0 again (sequence numbers restart). */
 a3d_status a3d_voxel_map_clear(a3d_voxel_map* map);
 void a3d_voxel_map_free(a3d_voxel_map* map);
+
+/* Aligning against the map.  The association rule, the definition everything below is tested against:
+ *   For a query point q, after its optional pose (Transform::transform_vector, as a3d_voxel_map_insert applies it):
+ *   c_k = floorf((q_k - o_k) / v) as above; if q fails the drop rule (a c_k not finite or outside [-2^20, 2^20)) it has
+ *   no correspondence.  The candidates are the stored rows of the occupied cells c + d, d in {-1, 0, 1}^3.  A neighbour
+ *   whose coordinate leaves [-2^20, 2^20) on any axis is skipped; that is decided per axis, before the key is packed: a
+ *   borrow or carry never reaches another axis's field of the key.  For a candidate row r, in f32 with every operation
+ *   rounded on its own: d = q - r, d2 = (d_x * d_x + d_y * d_y) + d_z * d_z.  The winner minimises
+ *   bits(d2) << 32 | seq, the word form the map already uses (d2 is never negative or NaN here).  The result therefore
+ *   does not depend on slot order, table size, growth history or timing.  If no candidate exists the result is seq
+ *   0xFFFFFFFF and d2 +inf.
+ * In plain words: the exact nearest stored row wherever that row lies within about one cell of q.  The claim is rigorous
+ * for distances <= 0.75 v when |q - o| / v < 2^12, because the rounding of the cell coordinate is then far below a
+ * quarter cell; farther rows are simply not found.  This is NOT the reference's R3dTree::nearest, which scans a single
+ * leaf and is approximate: there is no parity with Icp over a3d_voxel_map_extract's cloud, only the rule above.
+ * Search radii above one cell, several sources per call, colour terms and a point-to-point cost are NOT built.
+ * All entries are host-synchronous and ordered on the context's stream like the other map calls; the map is never
+ * modified, so inserts and retains may follow.  A map whose table has more than 2^32 slots (over 120 GiB) is refused with
+ * A3D_INVALID_PARAMETER by all of them: slot indices are 32-bit in these kernels. */
+
+/* The association for m resident queries: d_queries [m][3] f32, pose_host NULL = the queries as they are, bit for bit;
+ * d_out_seq [m] u32 and d_out_dist2 [m] f32.  m == 0 is A3D_OK and touches nothing; a map without a table (nothing
+ * inserted yet) fills the outputs with "none".  Decided on the host before any launch: a NULL map, or with m > 0 a NULL
+ * d_queries, d_out_seq or d_out_dist2, m >= 2^31, and outputs that overlap each other or the queries are
+ * A3D_INVALID_PARAMETER. */
+a3d_status a3d_voxel_map_nearest_device(a3d_voxel_map* map, const float* d_queries, uint64_t m, const a3d_pose* pose_host,
+                                        uint32_t* d_out_seq, float* d_out_dist2);
+/* Frame-to-map ICP: Icp::align's loop (src/icp/pcl_icp.rs:59-106) with the association above in place of the kd-tree,
+ * started from initial_host (NULL = Transform::eye()) instead of eye(): the returned pose maps the source AS GIVEN into
+ * the map's frame, the caller does not transform the cloud first.  The gates (max_distance squared against d2, the strict
+ * normal-angle gate), the residual, the Jacobian, the weight, max_iterations (0 returns the initial pose bit for bit), the
+ * best-pose rule and the solve-failure status are exactly a3d_pcl_icp_align_device's: A3D_SOLVE_FAILED when no point
+ * passes, with the pose reached so far in out_pose.  d_source: DEVICE pointers on the map's context, read during the call.
+ * The launch geometry follows the source length and the device only, never the table's slot count: the sums of an
+ * iteration depend on the map's contents alone.  The working buffers (two states, two partial sets, the out pose; a few
+ * hundred bytes per CU) belong to the map: allocated on first use, freed with it.
+ * Decided on the host before any launch, in this order: a NULL map, params, d_source, d_source->points or out_pose
+ * -> A3D_INVALID_PARAMETER; a source with len == 0 or len >= 2^31 -> A3D_INVALID_PARAMETER; a map without normals ->
+ * A3D_MISSING_FIELD; a source without normals -> A3D_MISSING_FIELD. */
+a3d_status a3d_voxel_map_icp_align_device(a3d_voxel_map* map, const a3d_icp_params* params,
+                                          const a3d_point_cloud_view* d_source, const a3d_pose* initial_host,
+                                          a3d_pose* out_pose);
+/* One pass of that per-point loop under `pose` (NULL = eye), summed in f64 as a3d_pcl_icp_accumulate: test hook.  The
+ * same refusals. */
+a3d_status a3d_voxel_map_icp_accumulate_device(a3d_voxel_map* map, const a3d_icp_params* params,
+                                               const a3d_point_cloud_view* d_source, const a3d_pose* pose,
+                                               a3d_gn_state* out_state);
+/* Instrumentation: device time (ms) of the iteration launches of the most recent a3d_voxel_map_icp_align_device. */
+a3d_status a3d_voxel_map_icp_last_device_ms(a3d_voxel_map* map, float* out_ms);
 
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
