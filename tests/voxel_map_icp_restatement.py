@@ -93,15 +93,21 @@ class MapRestatement:
     def point_terms(self, src_points, src_normals, pose, params):
         """(residuals [k] f32, jacobians [k, 6] f32) of the source points that pass both gates under `pose` (a PoseC), in
         source order: the body of src/icp/pcl_icp.rs:68-91."""
+        return self.point_terms_kept(src_points, src_normals, pose, params)[:2]
+
+    def point_terms_kept(self, src_points, src_normals, pose, params):
+        """point_terms and, third, the source indices [k] (ascending) of the points that passed."""
         p = O.transform_points(pose, src_points)
         sn = transform_normals(pose, src_normals)
         _, d2, row = self.nearest(p)
         max_d2 = np.float32(params.max_distance) * np.float32(params.max_distance)
         keep = (row >= 0) & ~(d2 > max_d2)
+        kept = np.flatnonzero(keep)
         p, sn, row = p[keep], sn[keep], row[keep]
         tp, tn = self.rows[row], self.normals[row]
         dot = (sn[:, 0] * tn[:, 0] + sn[:, 1] * tn[:, 1]) + sn[:, 2] * tn[:, 2]
         keep = ~O.acos_gate_rejects(dot, params.max_normal_angle, strict=True) if len(dot) else np.zeros(0, bool)
+        kept = kept[keep]
         p, tp, tn = p[keep], tp[keep], tn[keep]
         d = tp - p
         r = (d[:, 0] * tn[:, 0] + d[:, 1] * tn[:, 1]) + d[:, 2] * tn[:, 2]
@@ -109,7 +115,7 @@ class MapRestatement:
                        p[:, 0] * tn[:, 1] - p[:, 1] * tn[:, 0]], axis=1)
         J = np.ascontiguousarray(np.concatenate([tn, tw], axis=1), np.float32)
         assert r.dtype == np.float32 and J.shape == (len(r), 6)
-        return np.ascontiguousarray(r), J
+        return np.ascontiguousarray(r), J, kept
 
     def gn_state(self, src_points, src_normals, pose, params):
         """The GaussNewton<6> state after the point loop, by orc_gn_steps (f32 running sums, as the reference)."""
@@ -143,6 +149,83 @@ class MapRestatement:
             if residual < best_residual:
                 best_residual, best = residual, optim
         return A3D_OK, best
+
+
+class SparseMapRestatement(MapRestatement):
+    """The map after `pieces` = [(seq0, points, normals)] went in, piece k's point i under sequence number seq0 + i, and
+    every number between the pieces was consumed by a point that the map drops (all NaN: it changes no cell).  The
+    merged input of such a map has up to 2^32 rows and is never formed: the map is voxel_downsample_cloud of the real
+    points alone, each local index translated to its true sequence number.  The translation is strictly increasing, so
+    every "the lower number wins" decision is the one the merged input would give.  `seq` is uint32 as everywhere;
+    `local` keeps the indices into the concatenated real points.  nearest / accumulate / align work unchanged."""
+
+    def __init__(self, pieces, voxel_size, origin=None):
+        pieces = [(int(s), np.ascontiguousarray(p, np.float32).reshape(-1, 3), n) for s, p, n in pieces]
+        true = np.concatenate([np.uint64(s) + np.arange(len(p), dtype=np.uint64) for s, p, _ in pieces])
+        assert (true[1:] > true[:-1]).all() and (len(true) == 0 or int(true[-1]) < 1 << 32)  # the pieces do not overlap
+        self.points_in = np.concatenate([p for _, p, _ in pieces])
+        with_normals = all(n is not None for _, _, n in pieces)
+        self.normals_in = np.concatenate([np.ascontiguousarray(n, np.float32).reshape(-1, 3) for _, _, n in pieces]) if with_normals else None
+        self.true_seq = true  # of every real point offered, kept or not
+        super().__init__(self.points_in, self.normals_in, voxel_size, origin)
+        self.local = self.seq
+        self.seq = true[self.local].astype(np.uint32)
+        self.cells = {key: (int(self.seq[row]), row) for key, (_, row) in self.cells.items()}
+
+
+def retained(model, min_seq=0, box=None, marks=(), total=None):
+    """a3d_voxel_map_retain on a restated map (MapRestatement or SparseMapRestatement) whose `total` points were offered
+    (None: one past its last row's number).  Returns (survivors, removed, new_marks, k): `survivors` is the
+    MapRestatement of the rows with seq >= min_seq that lie inside the closed box = (min3, max3), numbered 0 ... k-1 in
+    their old order; new_marks[i] = the survivors whose old number is below marks[i], marks above `total` counting as
+    `total`."""
+    seq = model.seq.astype(np.uint64)
+    total = (int(seq[-1]) + 1 if len(seq) else 0) if total is None else int(total)
+    assert len(seq) == 0 or int(seq.max()) < total
+    keep = seq >= np.uint64(min(int(min_seq), total))
+    if box is not None:
+        lo, hi = np.asarray(box[0], np.float32), np.asarray(box[1], np.float32)
+        keep &= ((model.rows >= lo) & (model.rows <= hi)).all(axis=1)
+    old = seq[keep]
+    new_marks = [int((old < np.uint64(min(int(m), total))).sum()) for m in marks]
+    k = int(keep.sum())
+    survivors = MapRestatement(model.rows[keep], None if model.normals is None else model.normals[keep], model.voxel, model.origin)
+    assert len(survivors.rows) == k and np.array_equal(survivors.seq, np.arange(k))  # one row per cell: all of them stay
+    return survivors, int(len(seq) - k), new_marks, k
+
+
+class PeriodicSource:
+    """`model` as a long source of `m` points sees it, where the long source is a short one repeated: the methods are
+    handed ONE period of P points, and point i of the long source is point i % P of that period.  Association and
+    per-point terms are computed for the one period and indexed; the sums, the iteration and the loop are
+    MapRestatement's own, taken over all m points."""
+
+    def __init__(self, model, m):
+        self.model, self.m = model, int(m)
+
+    def _index(self, period):
+        assert 0 < period
+        return np.arange(self.m, dtype=np.int64) % period
+
+    def nearest(self, queries, pose=None):
+        seq, d2, row = self.model.nearest(queries, pose)
+        i = self._index(len(seq))
+        return seq[i], d2[i], row[i]
+
+    def point_terms_kept(self, src_points, src_normals, pose, params):
+        r, J, kept = self.model.point_terms_kept(src_points, src_normals, pose, params)
+        period = len(np.ascontiguousarray(src_points, np.float32).reshape(-1, 3))
+        place = np.full(period, -1, np.int64)  # of a period's point among the period's terms
+        place[kept] = np.arange(len(kept))
+        at = place[self._index(period)]
+        long_kept = np.flatnonzero(at >= 0)
+        at = at[long_kept]
+        return np.ascontiguousarray(r[at]), np.ascontiguousarray(J[at]), long_kept
+
+    point_terms = MapRestatement.point_terms
+    gn_state = MapRestatement.gn_state
+    accumulate = MapRestatement.accumulate
+    align = MapRestatement.align
 
 
 def brute_force(rows, seq, queries):
