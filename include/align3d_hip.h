@@ -314,7 +314,9 @@ a3d_status a3d_compute_normals(a3d_context* ctx, const float* points, const uint
 /* ---- ImageIcp (src/icp/image_icp.rs:19-165) ---------------------------------------------- */
 
 /* ImageIcp::new(params, target) + initial_transform + align(source): all iterations run on the
- * device; returns best_transform.  init_pose NULL = Transform::eye(). */
+ * device; returns best_transform.  init_pose NULL = Transform::eye().  Target and source may differ in size and
+ * intrinsics: the loop runs over the source's pixels, and only the target's intrinsics and size enter the projection
+ * and its bounds test (image_icp.rs:107-109). */
 a3d_status a3d_image_icp_align(a3d_context* ctx, const a3d_icp_params* params,
                                const a3d_device_image* target, const a3d_device_image* source,
                                const a3d_pose* init_pose, a3d_pose* out_pose);
@@ -396,7 +398,8 @@ a3d_status a3d_multiscale_new(a3d_context* ctx, const a3d_icp_params* params, ui
                               const a3d_device_image* const* target_pyramid, uint64_t n_levels,
                               a3d_multiscale** out);
 /* MultiscaleAlign::align(&source_pyramid): coarsest level first, each level starts from the
- * previous level's result; a shorter source pyramid truncates like izip! (multiscale.rs:54-64). */
+ * previous level's result; a shorter source pyramid truncates like izip! (multiscale.rs:54-64).  A source level may
+ * differ from its target level in size and intrinsics; only the target's enter the projection (image_icp.rs:107-109). */
 a3d_status a3d_multiscale_align(a3d_multiscale* ms, const a3d_device_image* const* source_pyramid,
                                 uint64_t n_source_levels, a3d_pose* out_pose);
 /* The same with the source pyramid as the reference holds it: `&[RangeImage]` in HOST memory (src/icp/multiscale.rs:51).
@@ -410,7 +413,9 @@ a3d_status a3d_multiscale_align_host(a3d_multiscale* ms, const a3d_range_image_v
 a3d_status a3d_multiscale_free(a3d_multiscale* ms);
 
 /* P independent MultiscaleAlign::new(params, target_p).align(source_p) jobs run as one launch
- * sequence (grid = pairs x tiles).  target/source are [n_pairs][n_levels] row-major handle tables. */
+ * sequence (grid = pairs x tiles).  target/source are [n_pairs][n_levels] row-major handle tables.  Sizes and
+ * intrinsics may differ between pairs and, inside a pair, between target and source: only the target's enter the
+ * projection (image_icp.rs:107-109); the source's own width and back-projection constants serve its pixel loop. */
 a3d_status a3d_multiscale_batch_new(a3d_context* ctx, const a3d_icp_params* params,
                                     uint64_t n_params, uint64_t n_pairs, uint64_t n_levels,
                                     const a3d_device_image* const* target_pyramids,
