@@ -182,10 +182,24 @@ SIGNATURES = {
     "a3d_range_image_to_point_cloud": (_ST, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "a3d_range_image_to_point_clouds": (_ST, [_PP, C.c_uint64, _PP, _PP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "a3d_range_image_has_normals": (_ST, [_P, C.POINTER(C.c_int32)]),
+    "a3d_range_image_has_colors": (_ST, [_P, C.POINTER(C.c_int32)]),
+    "a3d_range_image_to_point_clouds_rgb": (
+        _ST,
+        [_PP, C.c_uint64, _PP, _PP, _PP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    ),
     "a3d_point_clouds_transform_device": (_ST, [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, _PP, _PP]),
     "a3d_point_clouds_merge_device": (
         _ST,
         [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)],
+    ),
+    "a3d_point_clouds_merge_rgb_device": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), _PP, C.POINTER(PoseC), C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)],
+    ),
+    "a3d_point_clouds_voxel_downsample_rgb_device": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), _PP, C.c_uint64, C.c_float, C.POINTER(C.c_float), _PP, _PP, _PP, _PP,
+         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
     "a3d_point_clouds_voxel_downsample_device": (
         _ST,
@@ -198,6 +212,12 @@ SIGNATURES = {
         [_P, C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
     "a3d_voxel_map_extract": (_ST, [_P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "a3d_voxel_map_new_rgb": (_ST, [_P, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_uint64, _PP]),
+    "a3d_voxel_map_insert_rgb": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), _PP, C.POINTER(PoseC), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    ),
+    "a3d_voxel_map_extract_rgb": (_ST, [_P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "a3d_voxel_map_retain": (
         _ST,
         [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),

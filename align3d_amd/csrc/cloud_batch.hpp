@@ -39,6 +39,20 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 __device__ __forceinline__ uint32_t lane_rank(uint64_t ballot) {  // set lanes below this one
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
 }
+
+// A colour row of a cloud: [3] u8 at byte 3 * index of a buffer that may itself start at any byte (the merge puts a
+// cloud's first colour wherever the clouds before it end), so a row has no alignment at all.  It moves as three byte
+// loads and three byte stores: right for every residue of the address mod 4, and the last store of a buffer ends on the
+// buffer's last byte (a dword store over a row would write one byte past it).  r | g << 8 | b << 16 is the packed form
+// the voxel map keeps by slot.
+__device__ __forceinline__ uint32_t load_color(const uint8_t* colors, size_t index) {
+  const uint8_t* c = colors + 3 * index;
+  return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
+}
+__device__ __forceinline__ void store_color(uint8_t* colors, size_t index, uint32_t rgb) {
+  uint8_t* c = colors + 3 * index;
+  c[0] = (uint8_t)rgb, c[1] = (uint8_t)(rgb >> 8), c[2] = (uint8_t)(rgb >> 16);
+}
 #endif  // __HIPCC__
 
 struct ByteRange {

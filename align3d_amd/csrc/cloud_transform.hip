@@ -3,7 +3,9 @@
 // coordinate system).  Per point k of cloud i: out_points[k] = transform_vector(pose_i, points[k]) and, with normals,
 // out_normals[k] = transform_normal(pose_i, normals[k]) — the devmath.hpp functions the ICP kernels call, so the value is
 // the reference's f32 bit for bit (no contraction).  A job without a pose copies verbatim: no arithmetic, so NaN
-// payloads, -0 and infinities survive.
+// payloads, -0 and infinities survive.  A merge may also carry the clouds' colours ([len][3] u8): a pose does not touch
+// them, they are copied, and cloud i's first row lands at byte 3 * sum(len[0..i)) of the output, at any residue mod 4
+// (store_color, cloud_batch.hpp).
 //
 // One launch over every tile of every cloud of a batch (the job table of cloud_batch.hpp).  A tile is
 // XF_THREADS * PPT consecutive points; in round r thread t takes point tile_base + r * XF_THREADS + t, so a wave touches
@@ -29,11 +31,13 @@ struct XformJob {
   const float* normals;  // read only when out_normals is set
   float* out_points;
   float* out_normals;  // null: no normals are written
+  const uint8_t* colors;  // read only when out_colors is set
+  uint8_t* out_colors;    // null: no colours are written (the merge's alone: a transform's result copies its buffer)
   uint32_t len, first_tile, has_pose, pad;
   Pose pose;
   uint32_t pad2;
 };
-static_assert(sizeof(XformJob) == 80, "XformJob layout");
+static_assert(sizeof(XformJob) == 96, "XformJob layout");
 
 // The arrays' pointers come out of the job table, where the compiler only knows them as generic addresses (flat_load /
 // flat_store); they are device memory, and saying so gives global_load_dwordx3 / global_store_dwordx3.
@@ -78,6 +82,23 @@ __global__ void __launch_bounds__(XF_THREADS) cloud_transform_kernel(const Xform
     if (k < len) {
       *(XF_GLOBAL f32x3_u*)(out_points + 3 * (size_t)k) = p[r];
       if (out_normals) *(XF_GLOBAL f32x3_u*)(out_normals + 3 * (size_t)k) = n[r];
+    }
+  }
+  if (j.out_colors) {  // (uniform over the block; the colour output overlaps no input)
+    const XF_GLOBAL uint8_t* colors = (const XF_GLOBAL uint8_t*)j.colors;
+    XF_GLOBAL uint8_t* out_colors = (XF_GLOBAL uint8_t*)j.out_colors;
+    uint8_t c[PPT][3];
+#pragma unroll
+    for (uint32_t r = 0; r < PPT; ++r) {
+      const uint32_t k = k0 + r * XF_THREADS;
+      if (k < len)
+        for (uint32_t b = 0; b < 3; ++b) c[r][b] = colors[3 * (size_t)k + b];
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < PPT; ++r) {
+      const uint32_t k = k0 + r * XF_THREADS;
+      if (k < len)
+        for (uint32_t b = 0; b < 3; ++b) out_colors[3 * (size_t)k + b] = c[r][b];
     }
   }
 }
@@ -160,9 +181,10 @@ a3d_status a3d_point_clouds_transform_device(a3d_context* ctx, const a3d_point_c
   return run_jobs(ctx, jobs, points_per_thread_setting());
 }
 
-a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
-                                         uint64_t n, float* d_out_points, float* d_out_normals, uint64_t capacity,
-                                         uint64_t* out_len) {
+a3d_status a3d_point_clouds_merge_rgb_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                             const uint8_t* const* d_colors, const a3d_pose* poses_host, uint64_t n,
+                                             float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
+                                             uint64_t capacity, uint64_t* out_len) {
   if (n == 0) {
     if (out_len) *out_len = 0;
     return A3D_OK;
@@ -170,7 +192,7 @@ a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud
   A3D_REQUIRE(ctx && d_clouds && d_out_points && out_len, A3D_INVALID_PARAMETER, "null argument");
   std::vector<XformJob> jobs;
   std::vector<ByteRange> ranges;
-  jobs.reserve(n), ranges.reserve(2 * n + 2);
+  jobs.reserve(n), ranges.reserve(3 * n + 3);
   uint64_t total = 0;
   for (uint64_t i = 0; i < n; ++i) {
     const a3d_point_cloud_view& c = d_clouds[i];
@@ -178,15 +200,19 @@ a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud
     A3D_REQUIRE(c.len < (1ull << 31), A3D_INVALID_PARAMETER, "a cloud of 2^31 points or more");
     A3D_REQUIRE(c.points, A3D_INVALID_PARAMETER, "null points pointer");
     A3D_REQUIRE(!d_out_normals || c.normals, A3D_MISSING_FIELD, "a cloud of the merge has no normals");
+    const uint8_t* colors = d_out_colors && d_colors ? d_colors[i] : nullptr;
+    A3D_REQUIRE(!d_out_colors || colors, A3D_MISSING_FIELD, "a cloud of the merge has no colours");
     XformJob j{};
     j.points = c.points, j.normals = d_out_normals ? c.normals : nullptr;
     j.out_points = d_out_points + 3 * total, j.out_normals = d_out_normals ? d_out_normals + 3 * total : nullptr;
+    j.colors = colors, j.out_colors = d_out_colors ? d_out_colors + 3 * total : nullptr;
     j.len = (uint32_t)c.len;
     if (poses_host) j.has_pose = 1, j.pose = pose_from_c(&poses_host[i]);
     jobs.push_back(j);
     const uintptr_t bytes = (uintptr_t)c.len * 12;
     ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + bytes, false});
     if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + bytes, false});
+    if (j.colors) ranges.push_back({(uintptr_t)j.colors, (uintptr_t)j.colors + (uintptr_t)c.len * 3, false});
     total += c.len;
   }
   if (capacity < total) {
@@ -197,11 +223,19 @@ a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud
   }
   ranges.push_back({(uintptr_t)d_out_points, (uintptr_t)d_out_points + total * 12, true});
   if (d_out_normals) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + total * 12, true});
+  if (d_out_colors) ranges.push_back({(uintptr_t)d_out_colors, (uintptr_t)d_out_colors + total * 3, true});
   A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_merge_device: the output overlaps an input (or its own normals)");
+              "a3d_point_clouds_merge_device: the output overlaps an input (or its own normals or colours)");
   A3D_TRY(run_jobs(ctx, jobs, points_per_thread_setting()));
   *out_len = total;
   return A3D_OK;
+}
+
+a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
+                                         uint64_t n, float* d_out_points, float* d_out_normals, uint64_t capacity,
+                                         uint64_t* out_len) {
+  return a3d_point_clouds_merge_rgb_device(ctx, d_clouds, nullptr, poses_host, n, d_out_points, d_out_normals, nullptr,
+                                           capacity, out_len);
 }
 
 }  // extern "C"

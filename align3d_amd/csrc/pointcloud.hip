@@ -1,7 +1,9 @@
 // PointCloud::from(&RangeImage) (src/range_image/structure.rs:375-406) on resident images: an order-preserving
 // compaction.  A pixel is kept iff mask != 0 (structure.rs:381: not the mask == 1 of get_point), kept pixels come out in
 // row-major order, points and normals are copied verbatim (no arithmetic: NaN payloads, -0 and inf survive), and an image
-// without normals gives a cloud without normals (the reference's Option, structure.rs:384-390).
+// without normals gives a cloud without normals (the reference's Option, structure.rs:384-390).  Colours ([h][w][3] u8)
+// pass the same mask (structure.rs:392-398) when the caller asks for them: three bytes per kept pixel, moved by the
+// thread that moves the point (store_color, cloud_batch.hpp).
 //
 // Two launches over every tile of every image of a batch (the job table of cloud_batch.hpp), no block waiting on another:
 //  1. cloud_count_kernel: each block counts the kept pixels of its tile (reads the mask only) and adds them to its
@@ -32,6 +34,8 @@ struct CloudJob {
   const uint16_t* depth16;  // non-null: points_from_depth (common.hpp), the points are rebuilt from this plane
   float* out_points;
   float* out_normals;
+  const uint8_t* colors;  // null: no colours are written
+  uint8_t* out_colors;
   uint64_t capacity;
   uint32_t npx, width, first_tile, n_tiles, chunks_per_tile, pad;
   float bp_fx, bp_fy, bp_cx, bp_cy, depth_scale, pad2;
@@ -90,6 +94,8 @@ __global__ void __launch_bounds__(CLOUD_THREADS)
   const float* __restrict__ normals = j.normals;
   float* __restrict__ out_points = j.out_points;
   float* __restrict__ out_normals = j.out_normals;
+  const uint8_t* __restrict__ colors = j.colors;
+  uint8_t* __restrict__ out_colors = j.out_colors;
   const uint64_t capacity = j.capacity;
   const uint32_t npx = j.npx, width = j.width, span = j.chunks_per_tile * CLOUD_CHUNK;
   const uint32_t px_end = min(npx, t * span + span);
@@ -142,6 +148,7 @@ __global__ void __launch_bounds__(CLOUD_THREADS)
       }
       *(f32x3_u*)(out_points + 3 * dst) = pt;
       if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)p);
+      if (out_colors) store_color(out_colors, dst, load_color(colors, p));
     }
   }
 }
@@ -156,8 +163,15 @@ a3d_status a3d_range_image_has_normals(const a3d_device_image* image, int32_t* o
   return A3D_OK;
 }
 
-a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images, uint64_t n, float* const* d_points,
-                                           float* const* d_normals, const uint64_t* capacities, uint64_t* out_lens) {
+a3d_status a3d_range_image_has_colors(const a3d_device_image* image, int32_t* out_has_colors) {
+  A3D_REQUIRE(image && out_has_colors, A3D_INVALID_PARAMETER, "null argument");
+  *out_has_colors = image->colors ? 1 : 0;
+  return A3D_OK;
+}
+
+a3d_status a3d_range_image_to_point_clouds_rgb(const a3d_device_image* const* images, uint64_t n, float* const* d_points,
+                                               float* const* d_normals, uint8_t* const* d_colors,
+                                               const uint64_t* capacities, uint64_t* out_lens) {
   if (n == 0) return A3D_OK;
   A3D_REQUIRE(images && d_points && capacities && out_lens, A3D_INVALID_PARAMETER, "null argument");
   a3d_context* ctx = images[0] ? images[0]->ctx : nullptr;
@@ -169,6 +183,8 @@ a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images
     A3D_REQUIRE(im->ctx == ctx, A3D_INVALID_PARAMETER, "a3d_range_image_to_point_clouds: the images must share a context");
     float* out_normals = d_normals ? d_normals[i] : nullptr;
     A3D_REQUIRE(!out_normals || im->has_normals, A3D_MISSING_FIELD, "image has no normals");
+    uint8_t* out_colors = d_colors ? d_colors[i] : nullptr;
+    A3D_REQUIRE(!out_colors || im->colors, A3D_MISSING_FIELD, "image has no colours");
     CloudJob& j = jobs[i];
     j = CloudJob{};
     const uint64_t npx = (uint64_t)im->width * im->height;
@@ -176,6 +192,7 @@ a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images
     j.points = im->points, j.mask = im->mask;
     j.normals = out_normals ? im->normals : nullptr;
     j.out_points = d_points[i], j.out_normals = out_normals;
+    j.colors = out_colors ? im->colors : nullptr, j.out_colors = out_colors;
     j.capacity = capacities[i];
     j.npx = (uint32_t)npx, j.width = im->width;
     A3D_TRY(plan_tiles(npx, CLOUD_CHUNK, CLOUD_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
@@ -208,6 +225,11 @@ a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images
   A3D_REQUIRE(!over, A3D_INVALID_PARAMETER,
               "a3d_range_image_to_point_clouds: a capacity is smaller than its image's point count (nothing was written)");
   return A3D_OK;
+}
+
+a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images, uint64_t n, float* const* d_points,
+                                           float* const* d_normals, const uint64_t* capacities, uint64_t* out_lens) {
+  return a3d_range_image_to_point_clouds_rgb(images, n, d_points, d_normals, nullptr, capacities, out_lens);
 }
 
 a3d_status a3d_range_image_to_point_cloud(const a3d_device_image* image, float* d_points, float* d_normals,

@@ -23,7 +23,9 @@
 //  3. voxel_compact_kernel: each block sums its cloud's earlier tile counts for its offset (cloud_write_kernel's form: at
 //     most VX_MAX_TILES tiles per cloud), ranks its winners from the stored ballots and writes point, normal and index at
 //     offset + rank: input order.  It writes nothing if any cloud of the batch has more winners than its capacity, so
-//     the host needs one wait, after everything, to read the counts back.
+//     the host needs one wait, after everything, to read the counts back.  A cloud's colours ([len][3] u8), when the
+//     caller passes them, follow the winner in this pass: three bytes beside the point (store_color, cloud_batch.hpp).
+//     They play no part in passes 1 and 2.
 #include <cmath>
 #include <vector>
 
@@ -53,8 +55,10 @@ struct VoxelJob {
   unsigned long long slot_mask;
   unsigned long long capacity;
   uint32_t len, first_tile, chunks_per_tile, pad;
+  const uint8_t* colors;  // read only when out_colors is set
+  uint8_t* out_colors;    // null: no colours are written
 };
-static_assert(sizeof(VoxelJob) == 88, "VoxelJob layout");
+static_assert(sizeof(VoxelJob) == 104, "VoxelJob layout");
 
 // Pass 1.  dropped[job] += dropped points (zeroed by the host upload); *fault is set if a table were ever full (it cannot
 // be: it has at least two slots per point).
@@ -170,6 +174,8 @@ __global__ void __launch_bounds__(VX_THREADS)
   float* __restrict__ out_points = j.out_points;
   float* __restrict__ out_normals = j.out_normals;
   uint32_t* __restrict__ out_index = j.out_index;
+  const uint8_t* __restrict__ colors = j.colors;
+  uint8_t* __restrict__ out_colors = j.out_colors;
   const unsigned long long capacity = j.capacity;
   const uint32_t len = j.len, span = j.chunks_per_tile * VX_CHUNK, n_groups = (len + 63u) >> 6;
   const uint32_t p0 = t * span, p_end = min(len, p0 + span);
@@ -206,6 +212,7 @@ __global__ void __launch_bounds__(VX_THREADS)
       *(f32x3_u*)(out_points + 3 * dst) = *(const f32x3_u*)(points + 3 * (size_t)p);
       if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)p);
       if (out_index) out_index[dst] = p;
+      if (out_colors) store_color(out_colors, dst, load_color(colors, p));
     }
   }
 }
@@ -214,10 +221,12 @@ __global__ void __launch_bounds__(VX_THREADS)
 
 extern "C" {
 
-a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
-                                                    float voxel_size, const float origin[3], float* const* d_out_points,
-                                                    float* const* d_out_normals, uint32_t* const* d_out_index,
-                                                    const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped) {
+a3d_status a3d_point_clouds_voxel_downsample_rgb_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                                        const uint8_t* const* d_colors, uint64_t n, float voxel_size,
+                                                        const float origin[3], float* const* d_out_points,
+                                                        float* const* d_out_normals, uint8_t* const* d_out_colors,
+                                                        uint32_t* const* d_out_index, const uint64_t* capacities,
+                                                        uint64_t* out_lens, uint64_t* out_dropped) {
   if (n == 0) return A3D_OK;
   A3D_REQUIRE(ctx && d_clouds && d_out_points && capacities && out_lens, A3D_INVALID_PARAMETER, "null argument");
   A3D_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.f, A3D_INVALID_PARAMETER,
@@ -231,7 +240,7 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
   std::vector<VoxelJob> jobs;
   std::vector<uint64_t> cloud_of_job;
   std::vector<ByteRange> ranges;
-  jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(5 * n);
+  jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(7 * n);
   uint64_t tiles = 0;
   size_t flag_bytes = 0, table_bytes = 0;  // offsets of a job's arrays inside their parts of the scratch region, for now
   for (uint64_t i = 0; i < n; ++i) {
@@ -241,10 +250,14 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
     A3D_REQUIRE(c.points && d_out_points[i], A3D_INVALID_PARAMETER, "null points or output pointer");
     float* out_normals = d_out_normals ? d_out_normals[i] : nullptr;
     A3D_REQUIRE(!out_normals || c.normals, A3D_MISSING_FIELD, "cloud has no normals");
+    uint8_t* out_colors = d_out_colors ? d_out_colors[i] : nullptr;
+    const uint8_t* colors = out_colors && d_colors ? d_colors[i] : nullptr;
+    A3D_REQUIRE(!out_colors || colors, A3D_MISSING_FIELD, "cloud has no colours");
     VoxelJob j{};
     j.points = c.points, j.normals = out_normals ? c.normals : nullptr;
     j.out_points = d_out_points[i], j.out_normals = out_normals;
     j.out_index = d_out_index ? d_out_index[i] : nullptr;
+    j.colors = colors, j.out_colors = out_colors;
     j.capacity = capacities[i];
     j.len = (uint32_t)c.len;
     A3D_TRY(plan_tiles(c.len, VX_CHUNK, VX_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
@@ -261,10 +274,12 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
     const uintptr_t in_bytes = (uintptr_t)c.len * 12, kept = (uintptr_t)std::min<uint64_t>(c.len, j.capacity);
     ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + in_bytes, false});
     if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + in_bytes, false});
+    if (j.colors) ranges.push_back({(uintptr_t)j.colors, (uintptr_t)j.colors + (uintptr_t)c.len * 3, false});
     if (kept) {
       ranges.push_back({(uintptr_t)j.out_points, (uintptr_t)j.out_points + kept * 12, true});
       if (out_normals) ranges.push_back({(uintptr_t)out_normals, (uintptr_t)out_normals + kept * 12, true});
       if (j.out_index) ranges.push_back({(uintptr_t)j.out_index, (uintptr_t)j.out_index + kept * 4, true});
+      if (out_colors) ranges.push_back({(uintptr_t)out_colors, (uintptr_t)out_colors + kept * 3, true});
     }
   }
   A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
@@ -315,6 +330,14 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
               "a3d_point_clouds_voxel_downsample_device: a capacity is smaller than its cloud's kept points (nothing was "
               "written)");
   return A3D_OK;
+}
+
+a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
+                                                    float voxel_size, const float origin[3], float* const* d_out_points,
+                                                    float* const* d_out_normals, uint32_t* const* d_out_index,
+                                                    const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped) {
+  return a3d_point_clouds_voxel_downsample_rgb_device(ctx, d_clouds, nullptr, n, voxel_size, origin, d_out_points,
+                                                      d_out_normals, nullptr, d_out_index, capacities, out_lens, out_dropped);
 }
 
 }  // extern "C"

@@ -7,9 +7,12 @@
 // seq = total + sum(len[0..j)) + i, where total counts every point ever offered, dropped ones included.
 //
 // State (one device block per table size, from the context's block pool): slots x VoxelSlot {key, best} | slots x 3 f32
-// points | slots x 3 f32 normals (maps with normals) | one 64-bit count of occupied slots.  The payload is held BY SLOT in
-// arrays of its own: a probe touches 16-byte slots only, and a winner's row has a fixed home that a later, better point
-// simply overwrites, so there is no free list and nothing to compact between calls.
+// points | slots x 3 f32 normals (maps with normals) | slots x u32 colours (maps with colours) | one 64-bit count of
+// occupied slots.  The payload is held BY SLOT in arrays of its own: a probe touches 16-byte slots only, and a winner's
+// row has a fixed home that a later, better point simply overwrites, so there is no free list and nothing to compact
+// between calls.  A colour is a payload like the normal: it never enters a key, a distance or a pose.  By slot it is
+// packed r | g << 8 | b << 16 into one aligned dword (a winner's colour is one 4-byte store, a move of the table one
+// 4-byte copy); a cloud's rows are [3] u8 without alignment, so the commit pass packs and the extract's last pass unpacks.
 //
 // Insert, two launches over every tile of every cloud of the call (the job table of cloud_batch.hpp), no block waits on
 // another block, no LDS:
@@ -64,13 +67,15 @@ struct MapJob {
   uint32_t len, first_tile, chunks_per_tile, has_pose;
   uint32_t seq0;  // sequence number of the cloud's point 0
   Pose pose;
+  const uint8_t* colors;  // [len][3] u8, read only by maps with colours
 };
-static_assert(sizeof(MapJob) == 64, "MapJob layout");
+static_assert(sizeof(MapJob) == 72, "MapJob layout");
 
 struct MapTable {
   VoxelSlot* table;
   float* points;   // [slots][3]
   float* normals;  // [slots][3] or null
+  uint32_t* colors;  // [slots] packed, or null
   unsigned long long mask;  // slots - 1
   unsigned long long* cell_count;
 };
@@ -184,14 +189,15 @@ __global__ void __launch_bounds__(VM_THREADS)
       }
       *(f32x3_u*)(m.normals + 3 * (size_t)s) = nv;
     }
+    if (m.colors) m.colors[s] = load_color(j.colors, p);
   }
 }
 
 // Growth: every occupied slot of the old table into the new one (key, best, row); counts the new table's cells.
 __global__ void __launch_bounds__(VM_THREADS)
     voxel_map_rehash_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
-                            const float* __restrict__ old_normals, unsigned long long old_slots, MapTable m,
-                            unsigned long long* __restrict__ fault) {
+                            const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                            unsigned long long old_slots, MapTable m, unsigned long long* __restrict__ fault) {
   uint32_t n_claimed = 0;
   for (unsigned long long o = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; o < old_slots;
        o += (unsigned long long)gridDim.x * VM_THREADS) {
@@ -207,6 +213,7 @@ __global__ void __launch_bounds__(VM_THREADS)
     m.table[s].best = old_table[o].best;
     *(f32x3_u*)(m.points + 3 * (size_t)s) = *(const f32x3_u*)(old_points + 3 * (size_t)o);
     if (m.normals) *(f32x3_u*)(m.normals + 3 * (size_t)s) = *(const f32x3_u*)(old_normals + 3 * (size_t)o);
+    if (m.colors) m.colors[s] = old_colors[o];
   }
   n_claimed = wave_sum(n_claimed);
   if ((threadIdx.x & 63u) == 0 && n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
@@ -318,10 +325,11 @@ __global__ void __launch_bounds__(VM_THREADS)
 // Extract 4: every occupied slot's row to its rank among the set bits: ascending seq.
 __global__ void __launch_bounds__(VM_THREADS)
     voxel_map_write_kernel(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
-                           const float* __restrict__ normals, unsigned long long slots,
-                           const unsigned long long* __restrict__ bitmap, const uint32_t* __restrict__ word_prefix,
-                           unsigned long long total, unsigned long long rows, float* __restrict__ out_points,
-                           float* __restrict__ out_normals, uint32_t* __restrict__ out_index) {
+                           const float* __restrict__ normals, const uint32_t* __restrict__ colors,
+                           unsigned long long slots, const unsigned long long* __restrict__ bitmap,
+                           const uint32_t* __restrict__ word_prefix, unsigned long long total, unsigned long long rows,
+                           float* __restrict__ out_points, float* __restrict__ out_normals, uint32_t* __restrict__ out_index,
+                           uint8_t* __restrict__ out_colors) {
   for (unsigned long long s = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; s < slots;
        s += (unsigned long long)gridDim.x * VM_THREADS) {
     if (table[s].key == VX_EMPTY) continue;
@@ -334,6 +342,7 @@ __global__ void __launch_bounds__(VM_THREADS)
     *(f32x3_u*)(out_points + 3 * dst) = *(const f32x3_u*)(points + 3 * (size_t)s);
     if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)s);
     if (out_index) out_index[dst] = seq;
+    if (out_colors) store_color(out_colors, dst, colors[s]);  // (dst < rows: the last byte written is 3 * rows - 1)
   }
 }
 
@@ -359,14 +368,17 @@ __global__ void __launch_bounds__(VM_THREADS)
     out[i] = rank_below(bitmap, word_prefix, n_words, min(marks[i], total));
 }
 
-// A table of `slots` slots inside a block: slots | point rows | normal rows, as ensure_slots lays them out.
+// A table of `slots` slots inside a block: slots | point rows | normal rows | packed colours, as ensure_slots lays them
+// out (a plane the map does not keep takes no room: the next one starts where it would).
 struct TableLayout {
-  size_t points_at, normals_at, end;
+  size_t points_at, normals_at, colors_at, end;
 };
-__host__ __device__ __forceinline__ TableLayout table_layout(unsigned long long slots, bool with_normals) {
+__host__ __device__ __forceinline__ TableLayout table_layout(unsigned long long slots, bool with_normals, bool with_colors) {
   const size_t table_bytes = ((size_t)slots * sizeof(VoxelSlot) + 255) & ~(size_t)255;
   const size_t row_bytes = ((size_t)slots * 12 + 255) & ~(size_t)255;
-  return TableLayout{table_bytes, table_bytes + row_bytes, table_bytes + row_bytes * (with_normals ? 2 : 1)};
+  const size_t color_bytes = ((size_t)slots * 4 + 255) & ~(size_t)255;
+  const size_t colors_at = table_bytes + row_bytes * (with_normals ? 2 : 1);
+  return TableLayout{table_bytes, table_bytes + row_bytes, colors_at, colors_at + (with_colors ? color_bytes : 0)};
 }
 // The slots of a map of k > 0 retained cells: the smallest power of two >= max(2 k, min_slots), min_slots the power of two
 // of an empty map (max(2 * reserve_cells, 64)).  Host and device evaluate it alike.
@@ -382,10 +394,11 @@ __host__ __device__ __forceinline__ unsigned long long retained_slots(unsigned l
 // max_slots slots are VX_EMPTY.  Counts the new table's cells.
 __global__ void __launch_bounds__(VM_THREADS)
     voxel_map_rebuild_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
-                             const float* __restrict__ old_normals, unsigned long long old_slots,
-                             const unsigned long long* __restrict__ bitmap, const uint32_t* __restrict__ word_prefix,
-                             unsigned long long total, const unsigned long long* __restrict__ k_word, char* new_base,
-                             unsigned long long min_slots, unsigned long long max_slots, uint32_t with_normals,
+                             const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                             unsigned long long old_slots, const unsigned long long* __restrict__ bitmap,
+                             const uint32_t* __restrict__ word_prefix, unsigned long long total,
+                             const unsigned long long* __restrict__ k_word, char* new_base, unsigned long long min_slots,
+                             unsigned long long max_slots, uint32_t with_normals, uint32_t with_colors,
                              unsigned long long* __restrict__ cell_count, unsigned long long* __restrict__ fault) {
   const unsigned long long k = *k_word;
   if (2 * k > max_slots) {  // (cannot happen: k <= the old cells; a bound on every store below)
@@ -393,9 +406,10 @@ __global__ void __launch_bounds__(VM_THREADS)
     return;
   }
   const unsigned long long slots = retained_slots(k, min_slots);  // <= max_slots
-  const TableLayout lay = table_layout(slots, with_normals != 0);
+  const TableLayout lay = table_layout(slots, with_normals != 0, with_colors != 0);
   const MapTable m{(VoxelSlot*)new_base, (float*)(new_base + lay.points_at),
-                   with_normals ? (float*)(new_base + lay.normals_at) : nullptr, slots - 1, cell_count};
+                   with_normals ? (float*)(new_base + lay.normals_at) : nullptr,
+                   with_colors ? (uint32_t*)(new_base + lay.colors_at) : nullptr, slots - 1, cell_count};
   uint32_t n_claimed = 0;
   for (unsigned long long o = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; o < old_slots;
        o += (unsigned long long)gridDim.x * VM_THREADS) {
@@ -418,6 +432,7 @@ __global__ void __launch_bounds__(VM_THREADS)
     m.table[s].best = (best & 0xFFFFFFFF00000000ull) | new_seq;
     *(f32x3_u*)(m.points + 3 * (size_t)s) = *(const f32x3_u*)(old_points + 3 * (size_t)o);
     if (m.normals) *(f32x3_u*)(m.normals + 3 * (size_t)s) = *(const f32x3_u*)(old_normals + 3 * (size_t)o);
+    if (m.colors) m.colors[s] = old_colors[o];
   }
   n_claimed = wave_sum(n_claimed);
   if ((threadIdx.x & 63u) == 0 && n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
@@ -428,7 +443,7 @@ uint32_t slot_blocks(uint64_t slots) {
 }
 
 MapTable table_of(const a3d_voxel_map* m) {
-  return MapTable{m->table, m->points, m->normals, m->slots - 1, m->cell_count};
+  return MapTable{m->table, m->points, m->normals, m->colors, m->slots - 1, m->cell_count};
 }
 
 // Makes sure the table has at least 2 * (cells + incoming) slots; `fault` is the call's guard word in scratch.
@@ -438,8 +453,8 @@ a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long*
   uint64_t slots = 64;
   while (slots < need || slots < 2 * m->reserve_cells) slots <<= 1;
   a3d_context* ctx = m->ctx;
-  const size_t table_bytes = pad256(slots * sizeof(VoxelSlot)), row_bytes = pad256(slots * 12);
-  const size_t bytes = table_bytes + row_bytes * (m->with_normals ? 2 : 1) + 256;
+  const TableLayout lay = table_layout(slots, m->with_normals, m->with_colors);
+  const size_t bytes = lay.end + 256;
   void* block = nullptr;
   size_t block_bytes = 0;
   A3D_TRY(ctx_block_alloc(ctx, bytes, &block, &block_bytes));
@@ -447,8 +462,9 @@ a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long*
   a3d_voxel_map old = *m;
   m->block = block, m->block_bytes = block_bytes, m->slots = slots;
   m->table = (VoxelSlot*)base;
-  m->points = (float*)(base + table_bytes);
-  m->normals = m->with_normals ? (float*)(base + table_bytes + row_bytes) : nullptr;
+  m->points = (float*)(base + lay.points_at);
+  m->normals = m->with_normals ? (float*)(base + lay.normals_at) : nullptr;
+  m->colors = m->with_colors ? (uint32_t*)(base + lay.colors_at) : nullptr;
   m->cell_count = (unsigned long long*)(base + bytes - 256);
   hipStream_t s = ctx->stream;
   hipError_t e = hipMemsetAsync(m->table, 0xFF, slots * sizeof(VoxelSlot), s);  // every key VX_EMPTY, every best word ~0
@@ -456,7 +472,7 @@ a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long*
   if (e == hipSuccess && old.block && old.cells) {
     hipLaunchKernelGGL(voxel_map_rehash_kernel, dim3(slot_blocks(old.slots)), dim3(VM_THREADS), 0, s,
                        (const VoxelSlot*)old.table, (const float*)old.points, (const float*)old.normals,
-                       (unsigned long long)old.slots, table_of(m), d_fault);
+                       (const uint32_t*)old.colors, (unsigned long long)old.slots, table_of(m), d_fault);
     e = hipGetLastError();
   }
   if (e != hipSuccess) {  // the old table stays the map's
@@ -482,8 +498,8 @@ bool stored_slot_setting() {
 
 extern "C" {
 
-a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
-                             uint64_t reserve_cells, a3d_voxel_map** out) {
+a3d_status a3d_voxel_map_new_rgb(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
+                                 int with_colors, uint64_t reserve_cells, a3d_voxel_map** out) {
   A3D_REQUIRE(ctx && out, A3D_INVALID_PARAMETER, "null argument");
   A3D_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.f, A3D_INVALID_PARAMETER,
               "a3d_voxel_map_new: the voxel size must be finite and positive");
@@ -495,13 +511,19 @@ a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float ori
   }
   A3D_REQUIRE(reserve_cells < (1ull << 32), A3D_INVALID_PARAMETER, "a3d_voxel_map_new: a reservation of 2^32 cells or more");
   a3d_voxel_map* m = new a3d_voxel_map();
-  m->ctx = ctx, m->grid = grid, m->with_normals = with_normals != 0, m->reserve_cells = reserve_cells;
+  m->ctx = ctx, m->grid = grid, m->with_normals = with_normals != 0, m->with_colors = with_colors != 0;
+  m->reserve_cells = reserve_cells;
   *out = m;  // the table is allocated by the first insert that holds a point
   return A3D_OK;
 }
 
-a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
-                                uint64_t n, uint64_t* out_dropped, uint64_t* out_cells) {
+a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
+                             uint64_t reserve_cells, a3d_voxel_map** out) {
+  return a3d_voxel_map_new_rgb(ctx, voxel_size, origin, with_normals, 0, reserve_cells, out);
+}
+
+a3d_status a3d_voxel_map_insert_rgb(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const uint8_t* const* d_colors,
+                                    const a3d_pose* poses_host, uint64_t n, uint64_t* out_dropped, uint64_t* out_cells) {
   if (n == 0) return A3D_OK;
   A3D_REQUIRE(map && d_clouds, A3D_INVALID_PARAMETER, "null argument");
   std::vector<MapJob> jobs;
@@ -515,11 +537,15 @@ a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* 
     A3D_REQUIRE(c.points, A3D_INVALID_PARAMETER, "null points pointer");
     A3D_REQUIRE(!map->with_normals || c.normals, A3D_MISSING_FIELD,
                 "a3d_voxel_map_insert: the map has normals and a cloud has none (nothing was inserted)");
+    const uint8_t* colors = map->with_colors && d_colors ? d_colors[i] : nullptr;
+    A3D_REQUIRE(!map->with_colors || colors, A3D_MISSING_FIELD,
+                "a3d_voxel_map_insert: the map has colours and a cloud has none (nothing was inserted)");
     // (a sum of < 2^32 terms below 2^32 cannot wrap 64 bits; the limit below bounds it)
     A3D_REQUIRE(map->total + incoming + c.len + VM_SEQ_MARGIN < (1ull << 32), A3D_INVALID_PARAMETER,
                 "a3d_voxel_map_insert: the map would pass 2^32 - 2^21 offered points (a3d_voxel_map_retain renumbers it)");
     MapJob j{};
     j.points = c.points, j.normals = map->with_normals ? c.normals : nullptr;
+    j.colors = colors;
     j.len = (uint32_t)c.len;
     j.seq0 = (uint32_t)(map->total + incoming);
     if (poses_host) j.has_pose = 1, j.pose = pose_from_c(&poses_host[i]);
@@ -583,10 +609,16 @@ a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* 
   return A3D_OK;
 }
 
-a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint32_t* d_out_index,
-                                 uint64_t capacity, uint64_t* out_len) {
+a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
+                                uint64_t n, uint64_t* out_dropped, uint64_t* out_cells) {
+  return a3d_voxel_map_insert_rgb(map, d_clouds, nullptr, poses_host, n, out_dropped, out_cells);
+}
+
+a3d_status a3d_voxel_map_extract_rgb(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
+                                     uint32_t* d_out_index, uint64_t capacity, uint64_t* out_len) {
   A3D_REQUIRE(map && d_out_points && out_len, A3D_INVALID_PARAMETER, "null argument");
   A3D_REQUIRE(!d_out_normals || map->with_normals, A3D_MISSING_FIELD, "a3d_voxel_map_extract: the map has no normals");
+  A3D_REQUIRE(!d_out_colors || map->with_colors, A3D_MISSING_FIELD, "a3d_voxel_map_extract: the map has no colours");
   {  // the outputs as the caller declared them: `capacity` rows each (no map has 2^32 cells)
     const uintptr_t rows = (uintptr_t)std::min<uint64_t>(capacity, 1ull << 32);
     std::vector<ByteRange> ranges;
@@ -594,6 +626,7 @@ a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float*
       ranges.push_back({(uintptr_t)d_out_points, (uintptr_t)d_out_points + rows * 12, true});
       if (d_out_normals) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + rows * 12, true});
       if (d_out_index) ranges.push_back({(uintptr_t)d_out_index, (uintptr_t)d_out_index + rows * 4, true});
+      if (d_out_colors) ranges.push_back({(uintptr_t)d_out_colors, (uintptr_t)d_out_colors + rows * 3, true});
     }
     A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER, "a3d_voxel_map_extract: the outputs overlap one another");
   }
@@ -630,13 +663,18 @@ a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float*
                      chunks_per_tile, (const uint32_t*)d_tile_counts, d_prefix);
   A3D_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(voxel_map_write_kernel, over_slots, block, 0, s, (const VoxelSlot*)map->table, (const float*)map->points,
-                     (const float*)map->normals, (unsigned long long)map->slots, (const unsigned long long*)d_bitmap,
-                     (const uint32_t*)d_prefix, (unsigned long long)map->total, (unsigned long long)map->cells, d_out_points,
-                     d_out_normals, d_out_index);
+                     (const float*)map->normals, (const uint32_t*)map->colors, (unsigned long long)map->slots,
+                     (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix, (unsigned long long)map->total,
+                     (unsigned long long)map->cells, d_out_points, d_out_normals, d_out_index, d_out_colors);
   A3D_HIP_TRY(hipGetLastError());
   // host-synchronous: the caller may read or free the outputs right after
   A3D_HIP_TRY(hipStreamSynchronize(s));
   return A3D_OK;
+}
+
+a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint32_t* d_out_index,
+                                 uint64_t capacity, uint64_t* out_len) {
+  return a3d_voxel_map_extract_rgb(map, d_out_points, d_out_normals, nullptr, d_out_index, capacity, out_len);
 }
 
 a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], const float box_max[3], uint64_t min_seq,
@@ -682,7 +720,7 @@ a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], cons
   uint64_t min_slots = 64;
   while (min_slots < 2 * map->reserve_cells) min_slots <<= 1;
   const uint64_t max_slots = retained_slots(map->cells, min_slots);
-  const size_t bytes = table_layout(max_slots, map->with_normals).end + 256;
+  const size_t bytes = table_layout(max_slots, map->with_normals, map->with_colors).end + 256;
   void* block = nullptr;
   size_t block_bytes = 0;
   A3D_TRY(ctx_block_alloc(ctx, bytes, &block, &block_bytes));
@@ -722,10 +760,11 @@ a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], cons
   }
   if (e == hipSuccess) {
     hipLaunchKernelGGL(voxel_map_rebuild_kernel, over_slots, block_dim, 0, s, (const VoxelSlot*)map->table,
-                       (const float*)map->points, (const float*)map->normals, (unsigned long long)map->slots,
-                       (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix, (unsigned long long)total,
-                       (const unsigned long long*)(d_out + n_marks), base, (unsigned long long)min_slots,
-                       (unsigned long long)max_slots, map->with_normals ? 1u : 0u, d_cell_count, d_fault);
+                       (const float*)map->points, (const float*)map->normals, (const uint32_t*)map->colors,
+                       (unsigned long long)map->slots, (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix,
+                       (unsigned long long)total, (const unsigned long long*)(d_out + n_marks), base,
+                       (unsigned long long)min_slots, (unsigned long long)max_slots, map->with_normals ? 1u : 0u,
+                       map->with_colors ? 1u : 0u, d_cell_count, d_fault);
     e = hipGetLastError();
   }
   unsigned long long counted = 0;
@@ -753,11 +792,12 @@ a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], cons
   if (k == 0) return A3D_OK;
   ctx_block_release(ctx, map->block, map->block_bytes);  // (nothing enqueued reads it any more)
   const uint64_t slots = retained_slots(k, min_slots);
-  const TableLayout lay = table_layout(slots, map->with_normals);
+  const TableLayout lay = table_layout(slots, map->with_normals, map->with_colors);
   map->block = block, map->block_bytes = block_bytes, map->slots = slots;
   map->table = (VoxelSlot*)base;
   map->points = (float*)(base + lay.points_at);
   map->normals = map->with_normals ? (float*)(base + lay.normals_at) : nullptr;
+  map->colors = map->with_colors ? (uint32_t*)(base + lay.colors_at) : nullptr;
   map->cell_count = d_cell_count;
   map->cells = map->total = k, map->dropped_total = 0;
   return A3D_OK;

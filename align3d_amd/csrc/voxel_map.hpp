@@ -6,7 +6,7 @@
 struct a3d_voxel_map {
   a3d_context* ctx = nullptr;
   a3d::VoxelGrid grid{};
-  bool with_normals = false;
+  bool with_normals = false, with_colors = false;
   uint64_t reserve_cells = 0;
   // the device block of the current table (null until the first insert that holds a point)
   void* block = nullptr;
@@ -15,6 +15,7 @@ struct a3d_voxel_map {
   a3d::VoxelSlot* table = nullptr;
   float* points = nullptr;
   float* normals = nullptr;
+  uint32_t* colors = nullptr;  // [slots] r | g << 8 | b << 16, or null
   unsigned long long* cell_count = nullptr;
   uint64_t cells = 0, total = 0, dropped_total = 0, growths = 0;
   // the working buffers of the frame-to-map ICP (voxel_map_icp.hip): one block of the context's, taken by the first

@@ -257,18 +257,24 @@ class MultiscaleAlignBatch:
 
 
 class PointCloud:
-    """PointCloud (src/pointcloud.rs:8-12): points [N,3], optional normals."""
+    """PointCloud (src/pointcloud.rs:8-12): points [N,3], optional normals, optional colours [N,3] u8 (RGB)."""
 
-    def __init__(self, points, normals=None):
+    def __init__(self, points, normals=None, colors=None):
         self.points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        self.colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        if self.colors is not None and len(self.colors) != len(self.points):
+            raise _abi.InvalidParameter(f"PointCloud: {len(self.points)} points but {len(self.colors)} colours")
 
     @staticmethod
     def from_range_image(im):
-        """From<&RangeImage> for PointCloud (src/range_image/structure.rs:375-406): mask != 0, row-major."""
+        """From<&RangeImage> for PointCloud (src/range_image/structure.rs:375-406): mask != 0, row-major; the colours
+        pass the same mask when the image has them (structure.rs:392-398)."""
         m = im.mask.reshape(-1) != 0
         normals = None if im.normals is None else im.normals.reshape(-1, 3)[m]
-        return PointCloud(im.points.reshape(-1, 3)[m], normals)
+        colors = getattr(im, "colors", None)
+        colors = None if colors is None else np.asarray(colors, np.uint8).reshape(-1, 3)[m]
+        return PointCloud(im.points.reshape(-1, 3)[m], normals, colors)
 
     def len(self):
         return len(self.points)
@@ -283,24 +289,40 @@ class PointCloud:
 
 class DevicePointCloud:
     """A PointCloud (src/pointcloud.rs:8-12) resident in HBM: points / normals [len][3] f32 on the context's GPU, for
-    the device-pointer forms a3d_pcl_icp_new_device / a3d_pcl_icp_align_device (no PCIe traffic per call)."""
+    the device-pointer forms a3d_pcl_icp_new_device / a3d_pcl_icp_align_device (no PCIe traffic per call).  Colours, when
+    the cloud has them, are [len][3] u8 in a buffer of their own (d_colors): a payload that merge, voxel_downsample and
+    DeviceVoxelMap carry beside the point it belongs to; no ICP reads them."""
+
+    d_colors = None  # (a cloud assembled field by field has no colours until it is given some)
 
     def __init__(self, ctx, cloud):
         self.ctx = ctx
         self.n = cloud.len()
-        self.d_points = ctx.to_device(cloud.points)
-        self.d_normals = None if cloud.normals is None else ctx.to_device(cloud.normals)
+        self.d_points = self.d_normals = self.d_colors = None
+        try:
+            self.d_points = ctx.to_device(cloud.points)
+            self.d_normals = None if cloud.normals is None else ctx.to_device(cloud.normals)
+            colors = getattr(cloud, "colors", None)
+            if colors is not None:
+                self.d_colors = ctx.to_device(colors) if self.n else ctx.malloc(1)
+        except BaseException:
+            self.free()
+            raise
 
     @staticmethod
-    def from_range_image(device_image):
+    def from_range_image(device_image, colors=False):
         """PointCloud::from(&RangeImage) (src/range_image/structure.rs:375-406) without leaving the device: the kept
         pixels (mask != 0) of a resident image, row-major, bit for bit (a3d_range_image_to_point_cloud).  The cloud has
-        normals iff the image has them; it owns its buffers (`free()`)."""
-        return DevicePointCloud.from_range_images([device_image])[0]
+        normals iff the image has them; it owns its buffers (`free()`).  colors=True also carries the kept pixels'
+        colours (see from_range_images)."""
+        return DevicePointCloud.from_range_images([device_image], colors=colors)[0]
 
     @staticmethod
-    def from_range_images(images):
-        """from_range_image for resident images of one context in one pass (a3d_range_image_to_point_clouds)."""
+    def from_range_images(images, colors=False):
+        """from_range_image for resident images of one context in one pass (a3d_range_image_to_point_clouds).
+        colors=True: every cloud also gets the colours of its kept pixels (a3d_range_image_to_point_clouds_rgb; an image
+        without colours raises A3D_MISSING_FIELD).  The reference always copies the colours; here they are opt-in, so
+        that callers who only align pay neither memory nor time for a field no ICP reads."""
         images = list(images)
         if not images:
             return []
@@ -312,18 +334,28 @@ class DevicePointCloud:
                 h, w = im.shape
                 c = DevicePointCloud.__new__(DevicePointCloud)
                 c.ctx, c.n = ctx, 0
-                c.d_points, c.d_normals = None, None
+                c.d_points, c.d_normals, c.d_colors = None, None, None
                 clouds.append(c)
                 c.d_points = ctx.malloc(w * h * 12)
                 c.d_normals = ctx.malloc(w * h * 12) if im.has_normals() else None
+                c.d_colors = ctx.malloc(w * h * 3) if colors else None
             caps = (C.c_uint64 * n)(*[im.shape[0] * im.shape[1] for im in images])
             lens = (C.c_uint64 * n)()
-            _abi.check(
-                ctx.lib.a3d_range_image_to_point_clouds(_handle_array(images), n,
-                                                        (C.c_void_p * n)(*[c.d_points for c in clouds]),
-                                                        (C.c_void_p * n)(*[c.d_normals for c in clouds]), caps, lens),
-                "a3d_range_image_to_point_clouds",
-            )
+            if colors:
+                _abi.check(
+                    ctx.lib.a3d_range_image_to_point_clouds_rgb(_handle_array(images), n,
+                                                                (C.c_void_p * n)(*[c.d_points for c in clouds]),
+                                                                (C.c_void_p * n)(*[c.d_normals for c in clouds]),
+                                                                DevicePointCloud._colors_array(clouds), caps, lens),
+                    "a3d_range_image_to_point_clouds_rgb",
+                )
+            else:
+                _abi.check(
+                    ctx.lib.a3d_range_image_to_point_clouds(_handle_array(images), n,
+                                                            (C.c_void_p * n)(*[c.d_points for c in clouds]),
+                                                            (C.c_void_p * n)(*[c.d_normals for c in clouds]), caps, lens),
+                    "a3d_range_image_to_point_clouds",
+                )
         except BaseException:
             for c in clouds:
                 c.free()
@@ -333,15 +365,16 @@ class DevicePointCloud:
         return clouds
 
     @staticmethod
-    def _allocate(ctx, n, with_normals):
+    def _allocate(ctx, n, with_normals, with_colors=False):
         """An uninitialised resident cloud of n points (at least one point's worth of memory, so that `d_normals is None`
-        keeps meaning "no normals")."""
+        keeps meaning "no normals", and `d_colors is None` "no colours")."""
         c = DevicePointCloud.__new__(DevicePointCloud)
         c.ctx, c.n = ctx, int(n)
-        c.d_points, c.d_normals = None, None
+        c.d_points, c.d_normals, c.d_colors = None, None, None
         try:
             c.d_points = ctx.malloc(max(1, c.n) * 12)
             c.d_normals = ctx.malloc(max(1, c.n) * 12) if with_normals else None
+            c.d_colors = ctx.malloc(max(1, c.n) * 3) if with_colors else None
         except BaseException:
             c.free()
             raise
@@ -370,9 +403,15 @@ class DevicePointCloud:
         return (_abi.PointCloudViewC * len(clouds))(*[c.view() for c in clouds])
 
     @staticmethod
+    def _colors_array(clouds):
+        """The array of colour pointers parallel to _views(clouds): NULL for a cloud without colours."""
+        return (C.c_void_p * len(clouds))(*[c.d_colors for c in clouds])
+
+    @staticmethod
     def transform_many(clouds, transforms):
         """[transforms[i] * clouds[i]] (&Transform * &PointCloud, src/pointcloud.rs:40-52) as new resident clouds, in ONE
-        call and one launch (a3d_point_clouds_transform_device).  Each result has normals iff its input has them."""
+        call and one launch (a3d_point_clouds_transform_device).  Each result has normals iff its input has them, and a
+        copy of its input's colours (the reference clones them, pointcloud.rs:49: one device-to-device copy each)."""
         if transforms is None:
             raise TypeError("transform_many needs one Transform per cloud")
         clouds = list(clouds)
@@ -382,13 +421,16 @@ class DevicePointCloud:
         n, outs = len(clouds), []
         try:
             for c in clouds:
-                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None))
+                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
             _abi.check(
                 ctx.lib.a3d_point_clouds_transform_device(ctx.handle, DevicePointCloud._views(clouds), poses, n,
                                                           (C.c_void_p * n)(*[o.d_points for o in outs]),
                                                           (C.c_void_p * n)(*[o.d_normals for o in outs])),
                 "a3d_point_clouds_transform_device",
             )
+            for c, o in zip(clouds, outs):
+                if c.d_colors is not None and c.n:
+                    _abi.check(ctx.lib.a3d_memcpy_d2d(ctx.handle, o.d_colors, c.d_colors, c.n * 3), "a3d_memcpy_d2d")
         except BaseException:
             for o in outs:
                 o.free()
@@ -400,7 +442,8 @@ class DevicePointCloud:
         return DevicePointCloud.transform_many([self], [transform])[0]
 
     def transform_(self, transform):
-        """self = transform * self, in place (every point is read before it is written); returns self."""
+        """self = transform * self, in place (every point is read before it is written); returns self.  Colours stay
+        as they are."""
         pose = transform.to_c()
         v = self.view()
         _abi.check(
@@ -412,11 +455,12 @@ class DevicePointCloud:
         return self
 
     @staticmethod
-    def merge(clouds, transforms=None, normals=None):
+    def merge(clouds, transforms=None, normals=None, colors=None):
         """One resident cloud holding transforms[i] * clouds[i] back to back, cloud order then point order
         (a3d_point_clouds_merge_device): frames brought into one coordinate system, a valid target for Icp / IcpBatch.
         transforms=None concatenates bit for bit.  The result has normals when the non-empty clouds all have them and
-        none when none has; a mix raises InvalidParameter unless normals=False asks for points only."""
+        none when none has; a mix raises InvalidParameter unless normals=False asks for points only.  `colors` follows the
+        same rule for the clouds' colours (a3d_point_clouds_merge_rgb_device)."""
         clouds = list(clouds)
         if not clouds:
             raise _abi.InvalidParameter("merge needs at least one cloud (an empty list has no context to allocate on)")
@@ -426,15 +470,29 @@ class DevicePointCloud:
             if len(have) > 1:
                 raise _abi.InvalidParameter("merge: some clouds have normals and some do not (normals=False merges the points only)")
             normals = have.pop()
+        if colors is None:
+            have = {c.d_colors is not None for c in clouds if c.n > 0} or {c.d_colors is not None for c in clouds}
+            if len(have) > 1:
+                raise _abi.InvalidParameter("merge: some clouds have colours and some do not (colors=False merges without them)")
+            colors = have.pop()
         total = sum(c.n for c in clouds)
-        out = DevicePointCloud._allocate(ctx, total, bool(normals))
+        out = DevicePointCloud._allocate(ctx, total, bool(normals), bool(colors))
         try:
             n_out = C.c_uint64()
-            _abi.check(
-                ctx.lib.a3d_point_clouds_merge_device(ctx.handle, DevicePointCloud._views(clouds), poses, len(clouds),
-                                                      out.d_points, out.d_normals, total, C.byref(n_out)),
-                "a3d_point_clouds_merge_device",
-            )
+            if colors:
+                _abi.check(
+                    ctx.lib.a3d_point_clouds_merge_rgb_device(ctx.handle, DevicePointCloud._views(clouds),
+                                                              DevicePointCloud._colors_array(clouds), poses, len(clouds),
+                                                              out.d_points, out.d_normals, out.d_colors, total,
+                                                              C.byref(n_out)),
+                    "a3d_point_clouds_merge_rgb_device",
+                )
+            else:
+                _abi.check(
+                    ctx.lib.a3d_point_clouds_merge_device(ctx.handle, DevicePointCloud._views(clouds), poses, len(clouds),
+                                                          out.d_points, out.d_normals, total, C.byref(n_out)),
+                    "a3d_point_clouds_merge_device",
+                )
         except BaseException:
             out.free()
             raise
@@ -457,17 +515,29 @@ class DevicePointCloud:
         n, outs, d_index = len(clouds), [], []
         try:
             for c in clouds:
-                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None))
+                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
                 if return_index:
                     d_index.append(ctx.malloc(max(1, c.n) * 4))
             lens = (C.c_uint64 * n)()
-            _abi.check(
-                ctx.lib.a3d_point_clouds_voxel_downsample_device(
-                    ctx.handle, DevicePointCloud._views(clouds), n, float(voxel_size), o,
-                    (C.c_void_p * n)(*[x.d_points for x in outs]), (C.c_void_p * n)(*[x.d_normals for x in outs]),
-                    (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens, None),
-                "a3d_point_clouds_voxel_downsample_device",
-            )
+            if any(c.d_colors is not None for c in clouds):
+                _abi.check(
+                    ctx.lib.a3d_point_clouds_voxel_downsample_rgb_device(
+                        ctx.handle, DevicePointCloud._views(clouds), DevicePointCloud._colors_array(clouds), n,
+                        float(voxel_size), o, (C.c_void_p * n)(*[x.d_points for x in outs]),
+                        (C.c_void_p * n)(*[x.d_normals for x in outs]), DevicePointCloud._colors_array(outs),
+                        (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens,
+                        None),
+                    "a3d_point_clouds_voxel_downsample_rgb_device",
+                )
+            else:
+                _abi.check(
+                    ctx.lib.a3d_point_clouds_voxel_downsample_device(
+                        ctx.handle, DevicePointCloud._views(clouds), n, float(voxel_size), o,
+                        (C.c_void_p * n)(*[x.d_points for x in outs]), (C.c_void_p * n)(*[x.d_normals for x in outs]),
+                        (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens,
+                        None),
+                    "a3d_point_clouds_voxel_downsample_device",
+                )
             for x, k in zip(outs, lens):
                 x.n = int(k)
             index = None
@@ -487,13 +557,14 @@ class DevicePointCloud:
     def voxel_downsample_many(clouds, voxel_size, origin=None):
         """[c.voxel_downsample(voxel_size, origin) for c in clouds] as new resident clouds of one context, in ONE call
         whose launch count does not depend on the number of clouds (a3d_point_clouds_voxel_downsample_device).  Each
-        result keeps the buffers sized for its input (len() is the kept count) and has normals iff its input has them."""
+        result keeps the buffers sized for its input (len() is the kept count) and has normals iff its input has them,
+        and colours iff its input has them."""
         return DevicePointCloud._voxel_downsample(clouds, voxel_size, origin, False)[0]
 
     def voxel_downsample(self, voxel_size, origin=None, return_index=False):
         """One point per occupied cell of the grid of pitch `voxel_size` anchored at `origin` (default (0, 0, 0)), as a
         new resident cloud: the input point nearest to the cell's centre (ties: the lowest index), never an average, so
-        the result is a subsequence of this cloud, points and normals bit for bit, and does not depend on the order of
+        the result is a subsequence of this cloud, points, normals and colours bit for bit, and does not depend on the order of
         the points.  Points whose cell is not finite or outside [-2^20, 2^20) per axis (NaN, infinities, far outliers)
         are dropped.  return_index=True returns (cloud, index): `index` is a HOST uint32 array, index[k] = the position
         in this cloud of the result's point k (one 4-byte-per-kept-point download; nothing else leaves the device)."""
@@ -511,6 +582,15 @@ class DevicePointCloud:
         nrm = self.ctx.to_host(self.d_normals, np.empty((self.n, 3), np.float32)) if self.n else np.empty((0, 3), np.float32)
         return pts, nrm
 
+    def has_colors(self):
+        return self.d_colors is not None
+
+    def download_colors(self):
+        """The colours [len, 3] uint8 (RGB) read back to the host, or None for a cloud without colours."""
+        if self.d_colors is None:
+            return None
+        return self.ctx.to_host(self.d_colors, np.empty((self.n, 3), np.uint8)) if self.n else np.empty((0, 3), np.uint8)
+
     def view(self):
         v = _abi.PointCloudViewC()
         v.points = self.d_points
@@ -519,22 +599,24 @@ class DevicePointCloud:
         return v
 
     def free(self):
-        for p in (self.d_points, self.d_normals):
+        for p in (self.d_points, self.d_normals, getattr(self, "d_colors", None)):
             if p is not None and self.ctx.handle:
                 self.ctx.free(p)
-        self.d_points = self.d_normals = None
+        self.d_points = self.d_normals = self.d_colors = None
 
 
 class DeviceVoxelMap:
     """A persistent voxel map in HBM (a3d_voxel_map_*): resident clouds go in frame by frame, and after any sequence of
     inserts extract() is DevicePointCloud.merge(all inserted clouds, their transforms).voxel_downsample(voxel_size,
     origin) bit for bit — points, normals, order and indices — however the inserts were grouped.  normals=True: the map
-    keeps a normal per cell and every inserted cloud must have normals.  reserve_cells: cells the first table holds
-    without growing."""
+    keeps a normal per cell and every inserted cloud must have normals.  colors=True: the same for colours (the winner's
+    colour per cell; extract() then returns a cloud with colours).  reserve_cells: cells the first table holds without
+    growing."""
 
-    def __init__(self, ctx, voxel_size, origin=None, normals=True, reserve_cells=0):
+    def __init__(self, ctx, voxel_size, origin=None, normals=True, reserve_cells=0, colors=False):
         self.ctx = ctx
         self.normals = bool(normals)
+        self.colors = bool(colors)
         self.handle = C.c_void_p()
         o = None
         if origin is not None:
@@ -542,8 +624,12 @@ class DeviceVoxelMap:
             if o.size != 3:
                 raise _abi.InvalidParameter("DeviceVoxelMap: the origin has three coordinates")
             o = (C.c_float * 3)(*o.tolist())
-        _abi.check(ctx.lib.a3d_voxel_map_new(ctx.handle, float(voxel_size), o, int(self.normals), int(reserve_cells),
-                                             C.byref(self.handle)), "a3d_voxel_map_new")
+        if self.colors:
+            _abi.check(ctx.lib.a3d_voxel_map_new_rgb(ctx.handle, float(voxel_size), o, int(self.normals), 1, int(reserve_cells),
+                                                     C.byref(self.handle)), "a3d_voxel_map_new_rgb")
+        else:
+            _abi.check(ctx.lib.a3d_voxel_map_new(ctx.handle, float(voxel_size), o, int(self.normals), int(reserve_cells),
+                                                 C.byref(self.handle)), "a3d_voxel_map_new")
 
     def insert_many(self, clouds, transforms=None):
         """Inserts resident clouds of the map's context, cloud i under transforms[i] (None: as they are), in ONE call;
@@ -557,8 +643,13 @@ class DeviceVoxelMap:
             raise _abi.InvalidParameter("DeviceVoxelMap.insert_many: the clouds must live on the map's context")
         n = len(clouds)
         dropped = (C.c_uint64 * n)()
-        _abi.check(self.ctx.lib.a3d_voxel_map_insert(self.handle, DevicePointCloud._views(clouds), poses, n, dropped, None),
-                   "a3d_voxel_map_insert")
+        if self.colors:
+            _abi.check(self.ctx.lib.a3d_voxel_map_insert_rgb(self.handle, DevicePointCloud._views(clouds),
+                                                             DevicePointCloud._colors_array(clouds), poses, n, dropped, None),
+                       "a3d_voxel_map_insert_rgb")
+        else:
+            _abi.check(self.ctx.lib.a3d_voxel_map_insert(self.handle, DevicePointCloud._views(clouds), poses, n, dropped, None),
+                       "a3d_voxel_map_insert")
         return [int(d) for d in dropped]
 
     def insert(self, cloud, transform=None):
@@ -570,14 +661,18 @@ class DeviceVoxelMap:
         downsampled merged cloud; the same bits on every run).  return_index=True returns (cloud, index): `index` is a
         HOST uint32 array, index[k] = the position of row k in the merged cloud of everything inserted."""
         ctx, cells = self.ctx, self.cells()
-        out = DevicePointCloud._allocate(ctx, cells, self.normals)
+        out = DevicePointCloud._allocate(ctx, cells, self.normals, self.colors)
         d_index = None
         try:
             if return_index:
                 d_index = ctx.malloc(max(1, cells) * 4)
             n_out = C.c_uint64()
-            _abi.check(ctx.lib.a3d_voxel_map_extract(self.handle, out.d_points, out.d_normals, d_index, cells, C.byref(n_out)),
-                       "a3d_voxel_map_extract")
+            if self.colors:
+                _abi.check(ctx.lib.a3d_voxel_map_extract_rgb(self.handle, out.d_points, out.d_normals, out.d_colors, d_index,
+                                                             cells, C.byref(n_out)), "a3d_voxel_map_extract_rgb")
+            else:
+                _abi.check(ctx.lib.a3d_voxel_map_extract(self.handle, out.d_points, out.d_normals, d_index, cells,
+                                                         C.byref(n_out)), "a3d_voxel_map_extract")
             out.n = int(n_out.value)
             index = None
             if return_index:

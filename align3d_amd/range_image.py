@@ -130,6 +130,12 @@ class DeviceRangeImage:
         _abi.check(self.ctx.lib.a3d_range_image_has_normals(self.handle, C.byref(out)))
         return bool(out.value)
 
+    def has_colors(self):
+        """Whether the resident image carries colours (RangeImage::colors is Some)."""
+        out = C.c_int32()
+        _abi.check(self.ctx.lib.a3d_range_image_has_colors(self.handle, C.byref(out)))
+        return bool(out.value)
+
     def download_normals(self):
         out = np.empty(self.shape + (3,), np.float32)
         _abi.check(self.ctx.lib.a3d_range_image_download_normals(self.handle, _abi.ptr(out)))

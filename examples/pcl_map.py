@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
-        [--voxel V [--online [--check-batch | --window-box R | --window-frames W]]] [--out map.npy]
+        [--voxel V [--online [--check-batch | --window-box R | --window-frames W]]] [--colors] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -17,7 +17,10 @@ assert that the two maps are the same bits.  --window-box R and --window-frames 
 an odometry loop that runs for hours must: after each insert DeviceVoxelMap.retain drops the cells outside the box of
 half-side R (metres) around the current camera position, or the cells whose point is older than the last W frames
 (frame boundaries are recorded as total() and carried through every retain by its `marks`).  A retain also renumbers the
-cells, so total(), printed per frame beside the cell count, stays bounded instead of running towards 2^32.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+cells, so total(), printed per frame beside the cell count, stays bounded instead of running towards 2^32.  --colors carries
+every point's RGB colour from the frames through whichever of these paths is selected (merge, voxel_downsample, the online
+map and its retains: a colour follows its point and decides nothing), and --out then also writes <out>_colors.npy ([N, 3]
+u8) beside the points.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -41,7 +44,8 @@ ap.add_argument("--window-box", type=float, default=None, metavar="R",
                 help="with --online: after each insert keep only the cells within R metres (per axis) of the camera")
 ap.add_argument("--window-frames", type=int, default=None, metavar="W",
                 help="with --online: after each insert keep only the cells whose point came with the last W frames")
-ap.add_argument("--out", default=None, help="write the map's points to this .npy file")
+ap.add_argument("--colors", action="store_true", help="carry the frames' RGB colours into the map")
+ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
 args = ap.parse_args()
 if args.online and not args.voxel:
     ap.error("--online needs --voxel")
@@ -62,7 +66,7 @@ cam, _, _, depth_scale = frames[0]
 built = RangeImageBuilder(ctx).pyramid_levels(1).with_intensity(False).build_many(cam, [(f[1], f[2]) for f in frames],
                                                                                   depth_scale)
 images = [pyramid[0] for pyramid in built]
-clouds = DevicePointCloud.from_range_images(images)  # frame k's cloud, resident
+clouds = DevicePointCloud.from_range_images(images, colors=args.colors)  # frame k's cloud, resident
 # pair k: frame k + 1 (source) onto frame k (target)
 batch = IcpBatch(ctx, IcpParams.default(), clouds[:-1])
 poses, status = batch.align(clouds[1:])
@@ -86,7 +90,7 @@ def thinned_by_batch():
 
 
 if args.online:
-    online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None)
+    online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None, colors=args.colors)
     offered = 0
     starts = collections.deque()  # --window-frames: the first sequence number of each kept frame, in the map's numbering
     for k, (cloud, pose) in enumerate(zip(clouds, camera_to_world)):  # what a live caller does as each frame arrives
@@ -118,6 +122,8 @@ if args.online:
             a is None and b is None or np.array_equal(a.view(np.uint32), b.view(np.uint32))
             for a, b in zip(batch_map.download(), world_map.download()))
         assert same, "the online map differs from merge + voxel_downsample"
+        if args.colors:
+            assert np.array_equal(batch_map.download_colors(), world_map.download_colors()), "the maps' colours differ"
         batch_map.free()
 elif args.voxel:
     offered, world_map = thinned_by_batch()
@@ -136,12 +142,17 @@ if args.voxel:
           f"translation {float(np.linalg.norm(correction.t)):.3e}")
 points, _ = world_map.download()
 finite = points[np.isfinite(points).all(axis=1)]
-print(f"{len(clouds)} frames, map of {world_map.len()} points" + (" with normals" if world_map.d_normals is not None else ""))
+print(f"{len(clouds)} frames, map of {world_map.len()} points" + (" with normals" if world_map.d_normals is not None else "")
+      + (" and colours" if world_map.has_colors() else ""))
 if len(finite):
     print("bounding box: min", finite.min(axis=0).tolist(), "max", finite.max(axis=0).tolist())
 if args.out:
     np.save(args.out, points)
     print("wrote", args.out)
+    if args.colors:
+        colors_out = os.path.splitext(args.out)[0] + "_colors.npy"
+        np.save(colors_out, world_map.download_colors())
+        print("wrote", colors_out)
 batch.free()
 for x in [world_map] + clouds + images:
     x.free()

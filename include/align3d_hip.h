@@ -285,6 +285,18 @@ a3d_status a3d_range_image_to_point_clouds(const a3d_device_image* const* images
                                            float* const* d_normals, const uint64_t* capacities, uint64_t* out_lens);
 /* Whether the resident image carries normals (RangeImage::normals is Some): 1 or 0.  No device work. */
 a3d_status a3d_range_image_has_normals(const a3d_device_image* image, int32_t* out_has_normals);
+/* Whether the resident image carries colours (RangeImage::colors is Some: every builder image, and an uploaded one after
+ * a3d_range_image_set_colors): 1 or 0.  No device work. */
+a3d_status a3d_range_image_has_colors(const a3d_device_image* image, int32_t* out_has_colors);
+/* a3d_range_image_to_point_clouds with the colours of the kept pixels (structure.rs:392-398: the same mask as the points).
+ * d_colors: NULL (then this is a3d_range_image_to_point_clouds), or n entries of which each is NULL (no colours written
+ * for that image) or a DEVICE buffer of capacities[i] rows of [3] u8, RGB: row k is the colour of the k-th pixel with
+ * mask != 0 in row-major order, byte for byte; no byte at or past 3 * out_lens[i] is written.  A non-NULL entry for an
+ * image without colours is A3D_MISSING_FIELD, decided for the whole batch before anything is launched, as for normals.
+ * Points, normals, the capacity rule (all or nothing) and the two launches are those of the entry above. */
+a3d_status a3d_range_image_to_point_clouds_rgb(const a3d_device_image* const* images, uint64_t n, float* const* d_points,
+                                               float* const* d_normals, uint8_t* const* d_colors,
+                                               const uint64_t* capacities, uint64_t* out_lens);
 
 /* RangeImage::colors = Some(..) (src/range_image/structure.rs:20-36): host rgb [h][w][3] u8 -> the resident image's
  * colours, in an allocation of their own that is freed with the image.  Host-synchronous.  An image that already has
@@ -514,6 +526,22 @@ a3d_status a3d_point_clouds_transform_device(a3d_context* ctx, const a3d_point_c
 a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
                                          const a3d_pose* poses_host, uint64_t n, float* d_out_points, float* d_out_normals,
                                          uint64_t capacity, uint64_t* out_len);
+/* Colours on resident clouds.  A cloud's colours are [len][3] u8, RGB (the reference's Array1<Vector3<u8>>,
+ * src/pointcloud.rs:8-12), in a DEVICE buffer of their own beside points and normals.  a3d_point_cloud_view does not
+ * carry them: they cross the ABI as an array of n pointers parallel to the views, where a NULL array or a NULL entry
+ * means "this cloud has no colours" (inputs) or "write no colours" (outputs).  A colour is a payload: it never decides
+ * which point is kept, and a pose does not touch it (&Transform * &PointCloud clones the colours, pointcloud.rs:49: copy
+ * the buffer with a3d_memcpy_d2d; there is no transform entry for them).  Colour buffers need no alignment, and no entry
+ * writes a byte past the rows it reports. */
+
+/* a3d_point_clouds_merge_device with colours: the colours of cloud i start at byte 3 * sum(len[0..i)) of d_out_colors
+ * (room for `capacity` rows).  A non-NULL d_out_colors requires colours on every cloud with len > 0 (else
+ * A3D_MISSING_FIELD); with d_out_colors NULL, d_colors is ignored and the call is a3d_point_clouds_merge_device.  The
+ * colour output may overlap no input and no other output (A3D_INVALID_PARAMETER).  One launch. */
+a3d_status a3d_point_clouds_merge_rgb_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                             const uint8_t* const* d_colors, const a3d_pose* poses_host, uint64_t n,
+                                             float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
+                                             uint64_t capacity, uint64_t* out_len);
 
 /* Voxel-grid downsampling of n resident clouds, each exactly as if it were passed alone, in a number of launches that
  * does not depend on n; host-synchronous like the two entries above.  Of the points of a cloud that share a cell of the
@@ -537,11 +565,22 @@ a3d_status a3d_point_clouds_merge_device(a3d_context* ctx, const a3d_point_cloud
  * cloud with len == 0 may have null pointers and yields out_lens[i] = 0.
  * Scratch memory (context-owned, grow-only, shared with the calls above): 16 bytes per slot of each cloud's hash table,
  * whose slot count is the smallest power of two >= 2 * len_i (so 32 to 64 bytes per point), plus len_i / 8 bytes of
- * flags, 4 bytes per 1024 points and 88 bytes per cloud. */
+ * flags, 4 bytes per 1024 points and 104 bytes per cloud. */
 a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
                                                     float voxel_size, const float origin[3], float* const* d_out_points,
                                                     float* const* d_out_normals, uint32_t* const* d_out_index,
                                                     const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped);
+/* The same with colours: the kept rows' colours go out in input order beside their points, d_out_colors[i] having room for
+ * capacities[i] rows of [3] u8.  The normals' rules apply: d_colors and d_out_colors may be NULL or hold NULL entries; a
+ * non-NULL output for a cloud without colours is A3D_MISSING_FIELD; the colour buffers (inputs by 3 * len_i bytes, outputs
+ * by 3 * min(len_i, capacities[i])) are part of the overlap check; nothing is written if any result does not fit.  Points,
+ * normals, indices, counts and the launches are those of the entry above, which is this one with NULL colours. */
+a3d_status a3d_point_clouds_voxel_downsample_rgb_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                                        const uint8_t* const* d_colors, uint64_t n, float voxel_size,
+                                                        const float origin[3], float* const* d_out_points,
+                                                        float* const* d_out_normals, uint8_t* const* d_out_colors,
+                                                        uint32_t* const* d_out_index, const uint64_t* capacities,
+                                                        uint64_t* out_lens, uint64_t* out_dropped);
 
 /* A persistent voxel map: the hash table of the downsample above kept between calls, so that resident clouds go in frame
  * by frame (a3d_voxel_map_insert) instead of merge + downsample of the whole map per frame.  The contract:
@@ -554,11 +593,15 @@ a3d_status a3d_point_clouds_voxel_downsample_device(a3d_context* ctx, const a3d_
  * Reservation: the table is open-addressing with a power-of-two slot count; before it launches, an insert of L points
  * makes sure slots >= 2 * (cells + L) and otherwise moves the map into the next sufficient power of two (one growth).  The
  * table is allocated by the first insert that offers a point, at max(that rule, 2 * reserve_cells, 64) slots, which is no
- * growth.  Device memory: 16 + 12 (+ 12 with normals) bytes per slot, from the context's block pool.
+ * growth.  Device memory: 16 + 12 (+ 12 with normals) (+ 4 with colours) bytes per slot, from the context's block pool.
  * Limits: total + L must stay below 2^32 - 2^21 (one tile span), else A3D_INVALID_PARAMETER and nothing changes;
  * a3d_voxel_map_retain renumbers a long-lived map, and removes cells by place and by age.  The map is also a spatial index:
  * a3d_voxel_map_nearest_device and a3d_voxel_map_icp_align_device (below) read it without an extract or a kd-tree build.
- * Colours and multi-GPU maps are NOT built.
+ * Colours (a3d_voxel_map_new_rgb): a map may keep the winner's colour per cell, and the contract extends word for word:
+ * after any sequence of inserts a3d_voxel_map_extract_rgb equals a3d_point_clouds_merge_rgb_device of everything inserted
+ * followed by a3d_point_clouds_voxel_downsample_rgb_device, colours included.  After a retain the map is a new map into
+ * which the surviving rows, colours too, went as one cloud.  Nearest, align and accumulate never read colours.
+ * Multi-GPU maps are NOT built.
  * Every call is host-synchronous (one wait, at its end) and ordered on the context's stream; a map belongs to its context
  * and must be freed before it. */
 typedef struct a3d_voxel_map a3d_voxel_map;
@@ -576,6 +619,10 @@ typedef struct a3d_voxel_map_stats {
  * that is not finite or <= 0, a non-finite origin are A3D_INVALID_PARAMETER. */
 a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
                              uint64_t reserve_cells, a3d_voxel_map** out);
+/* The same; with_colors != 0: the map keeps a colour per cell and every inserted cloud must have colours.  A map made by
+ * a3d_voxel_map_new has no colours. */
+a3d_status a3d_voxel_map_new_rgb(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
+                                 int with_colors, uint64_t reserve_cells, a3d_voxel_map** out);
 /* Inserts n resident clouds (device pointers on the map's context) under poses_host[i] (NULL = as they are, bit for bit;
  * otherwise Transform::transform_vector / transform_normal as a3d_point_clouds_merge_device).  out_dropped (NULL ok): [n],
  * the dropped points of each cloud; out_cells (NULL ok): the map's occupied cells afterwards.
@@ -585,6 +632,12 @@ a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float ori
  * A cloud with len == 0 may have null pointers.  A3D_HIP_ERROR if the table ever filled up (it cannot). */
 a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const a3d_pose* poses_host,
                                 uint64_t n, uint64_t* out_dropped, uint64_t* out_cells);
+/* The same with the clouds' colours (d_colors: NULL, or n DEVICE pointers to [len][3] u8 of which some may be NULL).  A
+ * non-empty cloud without colours offered to a map with colours is A3D_MISSING_FIELD, decided on the host: nothing from
+ * the call is inserted; so a3d_voxel_map_insert on such a map is refused for any non-empty cloud.  A map without colours
+ * ignores d_colors. */
+a3d_status a3d_voxel_map_insert_rgb(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const uint8_t* const* d_colors,
+                                    const a3d_pose* poses_host, uint64_t n, uint64_t* out_dropped, uint64_t* out_cells);
 /* Writes the occupied cells' rows in ascending seq — the order the downsample gives on the merged cloud, the same bits on
  * every run — into d_out_points (room for `capacity` points), d_out_normals (NULL ok; non-NULL on a map without normals
  * -> A3D_MISSING_FIELD) and d_out_index (NULL ok): the seq of each row, u32.  *out_len = cells.  capacity < cells ->
@@ -593,6 +646,11 @@ a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* 
  * Scratch memory (context-owned, shared with the calls above): total / 8 bytes of bitmap and total / 16 of prefixes. */
 a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint32_t* d_out_index,
                                  uint64_t capacity, uint64_t* out_len);
+/* The same with the rows' colours into d_out_colors (NULL ok; room for `capacity` rows of [3] u8; non-NULL on a map
+ * without colours -> A3D_MISSING_FIELD).  capacity < cells writes nothing.  The colour output takes part in the overlap
+ * check by its first 3 * capacity bytes; bytes at or past 3 * cells are never written. */
+a3d_status a3d_voxel_map_extract_rgb(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
+                                     uint32_t* d_out_index, uint64_t capacity, uint64_t* out_len);
 /* Rebuilds the map from the cells that survive and numbers them anew.  A cell survives iff its winner's seq >= min_seq
  * and, if a box is given, its stored row p has box_min[k] <= p[k] <= box_max[k] for k = 0, 1, 2: plain f32 comparisons
  * on the stored bits (the cell centre plays no part).  box_min and box_max are both NULL (no box) or both given; infinite
@@ -600,7 +658,7 @@ a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float*
  * box and min_seq == 0 is a pure compaction.  The contract:
  *   Let the survivors be the k rows of a3d_voxel_map_extract that pass the rule, in extract order.  After the call the map
  *   is indistinguishable from a new map of the same voxel_size, origin, with_normals and reserve_cells into which those k
- *   rows, points and normals, were inserted as ONE cloud without a pose.
+ *   rows, points, normals and colours, were inserted as ONE cloud without a pose.
  * (A cell's stored row is the very f32 point its key and bits(dist) were computed from, so offering it again without a pose
  * gives the same key and the same distance.)  So: extract returns the k rows bit for bit with indices 0 ... k-1;
  * get_stats gives cells = total = k and dropped_total = 0; growths is unchanged (a retain is no growth); for k > 0, slots
