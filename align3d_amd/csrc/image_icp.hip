@@ -173,15 +173,19 @@ __device__ __forceinline__ SrcPx stage_a(const LevelDesc& d, uint32_t i, bool in
   return s;
 }
 
-struct ProjPx {  // stage B: transformed point, projection, the gathered target record
+struct ProjPx {  // stage B: transformed point, projection, the gathered target record and the intensity-map cell
   V3 p;
   float u, v;
   V3 tp, tn;
   uint8_t tmask;  // consumed in stage C, so that stage B only ISSUES the gathers
   bool live;
-  uint32_t tdepth, trow, tcol;  // D16 & D16_TGT: the gathered u16 depth and its pixel (tp is rebuilt in stage C)
+  uint16_t tdepth;        // D16 & D16_TGT: the gathered u16 depth, widened where it is consumed (stage C)
+  uint32_t trow, tcol;    // ... and its pixel (tp is rebuilt in stage C)
+  float t00, t10, t01, t11;     // the map cell at (u, v), requested here unless CLASSIC (then stage C requests it)
 };
-template <bool ZMASK = false, int D16 = 0>
+// CLASSIC (diagnostics build only, A3D_ICP_STEP_ORDER=classic): the map cell is requested by stage C, after its gates, as
+// it was before the step was reordered (pixel_pass) — the same values either way.
+template <bool ZMASK = false, int D16 = 0, bool CLASSIC = false>
 __device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, const SrcPx& s, float twf, float thf,
                                           const BackProj2& bp = BackProj2{}) {
   ProjPx o;
@@ -211,11 +215,24 @@ __device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, con
     o.tdepth = ld<uint16_t>(d.tgt_depth, tidx * 2u);
     o.trow = row, o.tcol = col;
     o.tn = ld_v3(d.tgt_normals, tidx);
-    return o;
+  } else {
+    o.tp = ld_v3(d.tgt_points, tidx);
+    o.tn = ld_v3(d.tgt_normals, tidx);
+    o.tmask = ZMASK ? (uint8_t)0 : ld<uint8_t>(d.tgt_mask, tidx);
   }
-  o.tp = ld_v3(d.tgt_points, tidx);
-  o.tn = ld_v3(d.tgt_normals, tidx);
-  o.tmask = ZMASK ? (uint8_t)0 : ld<uint8_t>(d.tgt_mask, tidx);
+  if (!CLASSIC) {
+    // The 2 x 2 cell of the intensity map at (u, v), requested beside the gathers: its address needs nothing that they
+    // bring.  In bounds: a live lane has u + 0.5 in (-1, tw) and v + 0.5 in (-1, th), so u < tw - 0.5 and ui <= tw - 1,
+    // likewise vi <= th - 1 (a NaN or a negative u casts to 0), and rows vi, vi + 1, columns ui, ui + 1 lie inside
+    // the (th + 2) x (tw + 2) map — the bound the lanes that pass stage C's gates have always relied on, here for
+    // every lane that is live after the bounds test.  A lane that fails a gate in stage C has read a valid cell that
+    // nothing uses; a lane that is dead here reads texel 0, as a rejected lane always did.
+    const uint32_t mw = d.tw + 2u;
+    const uint32_t ui = f32_as_usize(o.u), vi = f32_as_usize(o.v);
+    const uint32_t mo = o.live ? texel_offset(vi, mw, ui) : 0u;
+    const f32x2 a = ld<f32x2_u>(d.imap, mo), b = ld<f32x2_u>(d.imap, mo + mw * 4u);
+    o.t00 = a.x, o.t10 = a.y, o.t01 = b.x, o.t11 = b.y;
+  }
   return o;
 }
 
@@ -223,12 +240,16 @@ struct MapPx {  // stage C: gates passed, the intensity-map cell
   float t00, t10, t01, t11;
   uint32_t ui, vi;
 };
-template <bool ZMASK = false, int D16 = 0>
+template <bool ZMASK = false, int D16 = 0, bool CLASSIC = false>
 __device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, ProjPx& px, uint32_t mw,
                                          const BackProj2& bp = BackProj2{}) {
   bool tvalid;
   if (D16 & D16_TGT) {  // the gathered depth lands here: the builder's function in its proven form, the same bits
-    const uint32_t td = px.live ? px.tdepth : 0u;  // (a rejected lane's row / column are not a pixel's: no point)
+    // (the depth is widened by an instruction of this stage: a widening left to the compiler is merged across the two
+    // unrolled steps and scheduled into stage B, between its loads, where it waits for the depth of the pixel before)
+    uint32_t wide;
+    asm volatile("v_and_b32 %0, 0xffff, %1" : "=v"(wide) : "v"(px.tdepth));
+    const uint32_t td = px.live ? wide : 0u;  // (a rejected lane's row / column are not a pixel's: no point)
     px.tp = backproject_px_proven(td, (int)px.trow, (int)px.tcol, bp.tgt.cx, bp.tgt.cy, bp.tgt.scale, bp.tgt.dfx, bp.tgt.dfy);
     tvalid = td != 0u;  // (td == 0: (±0, ±0, +0), dead below)
   } else {
@@ -242,7 +263,11 @@ __device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, Pr
             & !(norm_squared(diff) > gt.max_distance_sqr)        // image_icp.rs:114
             & !((pn >= -1.0f) & (pn <= gt.dot_reject_max));
   MapPx m;
-  m.ui = f32_as_usize(px.u), m.vi = f32_as_usize(px.v);
+  m.ui = f32_as_usize(px.u), m.vi = f32_as_usize(px.v);  // (the instruction stage B used: the same bits)
+  if (!CLASSIC) {  // stage B requested the cell: no load here
+    m.t00 = px.t00, m.t10 = px.t10, m.t01 = px.t01, m.t11 = px.t11;
+    return m;
+  }
   const uint32_t o = px.live ? texel_offset(m.vi, mw, m.ui) : 0u;  // (rejected pixels read texel 0)
   const f32x2 a = ld<f32x2_u>(d.imap, o), b = ld<f32x2_u>(d.imap, o + mw * 4u);
   m.t00 = a.x, m.t10 = a.y, m.t01 = b.x, m.t11 = b.y;
@@ -388,8 +413,8 @@ __global__ void __launch_bounds__(256, MERGED ? 5 : 1)
       // leaves the projected pixel k+1 in `nxt` and the source record of pixel k+2 in `s_new`
       auto step = [&](ProjPx& cur, uint8_t cur_i, ProjPx& nxt, uint8_t& nxt_i, const SrcPx& s_next, SrcPx& s_new, int k0) {
         s_new = src_at(k0 + 2, 0);                                  // issue source record k+2
-        const MapPx mp = stage_c(d, gt, cur, mw);                   // gathers(k) land; issue map cell(k)
-        nxt = stage_b(d, T, s_next, twf, thf);                      // issue gathers(k+1)
+        const MapPx mp = stage_c(d, gt, cur, mw);                   // the loads of k land (stage B requested the map cell too)
+        nxt = stage_b(d, T, s_next, twf, thf);                      // issue gathers and map cell(k+1)
         nxt_i = s_next.intensity;
         if (cur.live) accumulate(stage_d(d, gt, cur, mp, cur_i, mw));
       };
@@ -418,9 +443,9 @@ __global__ void __launch_bounds__(256, MERGED ? 5 : 1)
 #pragma unroll
       for (int g = 0; g < G; ++g) s2[g] = src_at(k0 + 2 * G, g);  // issue source records of batch k+2
 #pragma unroll
-      for (int g = 0; g < G; ++g) mp[g] = stage_c(d, gt, cur[g], mw);  // gathers(k) land; issue map cells(k)
+      for (int g = 0; g < G; ++g) mp[g] = stage_c(d, gt, cur[g], mw);  // the loads of k land (stage B requested the map cells too)
 #pragma unroll
-      for (int g = 0; g < G; ++g) {  // source(k+1) landed long ago; issue gathers(k+1)
+      for (int g = 0; g < G; ++g) {  // source(k+1) landed long ago; issue gathers and map cells(k+1)
         nxt[g] = stage_b(d, T, s1[g], twf, thf);
         nxt_int[g] = s1[g].intensity;
       }
@@ -490,12 +515,19 @@ __global__ void __launch_bounds__(256)
 
 // ---- the pixel pass of one block (the reference's loop over its share of the source pixels) -----------------------
 // grid = (tiles, pairs); block = 256.  A thread visits `ppt` source pixels, 256 apart (coalesced), through a
-// three-deep software pipeline: the source record of pixel k+2, the target gathers of pixel k+1 and the map cell of
-// pixel k are in flight while pixel k is accumulated (58 per-thread f32 accumulators, wave reduce-scatter at the end).
+// three-deep software pipeline: the source record of pixel k+2 and every target-side load of pixel k+1 — the gathers
+// AND the intensity-map cell, whose address needs only the projection — are in flight while pixel k is consumed (58
+// per-thread f32 accumulators, wave reduce-scatter at the end).  One step: issue A(k+2); wait for the source record of
+// k+1; B(k+1) with its four (masks read: five) loads back to back; then the step's one stall point, the wait for the
+// loads of k, which were requested a whole step (C(k-1) + D(k-1) + B(k+1), ~320 instructions) earlier; C(k), D(k) and the
+// accumulation.  (Before, C(k) came first and requested the cell of k behind its gates, ~115 instructions ahead of its
+// use, with a second wait per pixel; that order is CLASSIC, kept in the diagnostics build as a cross-check:
+// A3D_ICP_STEP_ORDER=classic.)  The cell travels in ProjPx: 112 VGPRs (116 with the masks read), four waves per SIMD.
 // The pipeline is unrolled by two with the buffers swapping roles, so that the rotation cur <- nxt, s1 <- s2 costs no
-// register copies.  Reading the loop's s_waitcnt's in the ISA is part of maintaining this code: a short-circuit `&&`
-// around a load, a u8 -> f32 conversion next to its load or a 64-bit multiply-add with a don't-care high half each
-// cost a full drain of the pipeline per pixel before they were found.
+// register copies.  Reading the loop's s_waitcnt's in the ISA is part of maintaining this code
+// (profiles/steporder_isa_stats.txt): a short-circuit `&&` around a load, a u8 -> f32 conversion next to its load, a
+// 64-bit multiply-add with a don't-care high half or a u16 -> u32 widening that the compiler moved into stage B each
+// cost a drain of the pipeline per pixel before they were found.
 // The first two source records do not depend on the pose: the callers issue them (pixel_source_at) BEFORE they wait
 // for the pose of the iteration, so those loads are in flight during the head.
 template <bool ZMASK, int D16 = 0>
@@ -503,7 +535,7 @@ __device__ __forceinline__ SrcPx pixel_source_at(const LevelDesc& d, uint32_t ba
   const uint32_t i = base + (uint32_t)k0 * 256u;
   return stage_a<ZMASK, D16>(d, i, (k0 < ppt) && (i < d.src_n));
 }
-template <bool ZMASK, int D16 = 0>
+template <bool ZMASK, int D16 = 0, bool CLASSIC = false>
 __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, const Pose& T, uint32_t base, int ppt,
                                            const SrcPx& s0, SrcPx sa, float (&acc)[GN_PARTIAL]) {
   const uint32_t mw = d.tw + 2;
@@ -512,17 +544,32 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
   if (D16 & D16_SRC) bp.src = make_backproj(d.src_bp);
   if (D16 & D16_TGT) bp.tgt = make_backproj(d.tgt_bp);
   SrcPx sb;
-  ProjPx pa = stage_b<ZMASK, D16>(d, T, s0, twf, thf, bp), pb;
+  ProjPx pa = stage_b<ZMASK, D16, CLASSIC>(d, T, s0, twf, thf, bp), pb;
   uint8_t ia = s0.intensity, ib;
   // one step: `cur` holds the projected pixel k, `s_next` the source record of pixel k+1 (consumed here); leaves the
   // projected pixel k+1 in `nxt` and the source record of pixel k+2 in `s_new`
   auto step = [&](ProjPx& cur, uint8_t cur_i, ProjPx& nxt, uint8_t& nxt_i, const SrcPx& s_next, SrcPx& s_new, int k0) {
     s_new = pixel_source_at<ZMASK, D16>(d, base, ppt, k0 + 2);  // issue source record k+2
+    if constexpr (!CLASSIC) {
+      // (the barriers pin the order A(k+2), B(k+1), C(k): left alone, the scheduler sinks stage B below stage C's wait
+      // to shorten live ranges, and the loads of k+1 are requested only when those of k have landed)
+      __builtin_amdgcn_sched_barrier(0);
+      nxt = stage_b<ZMASK, D16>(d, T, s_next, twf, thf, bp);      // source record k+1 lands; issue gathers and map cell(k+1)
+      nxt_i = s_next.intensity;
+      __builtin_amdgcn_sched_barrier(0);
+      const MapPx mp = stage_c<ZMASK, D16>(d, gt, cur, mw, bp);   // the loads of k land: the step's one wait for them
+      if (cur.live) {
+        const Terms t = stage_d(d, gt, cur, mp, cur_i, mw);
+        gn_step(acc, t.rg, t.Jg);  // the geometric term counts even when the colour term is rejected
+        if (t.color) gn_step(acc + GN_ACC, t.rc, t.Jc);
+      }
+      return;
+    }
     // (DEPTH16: otherwise the source depth load takes the register of the gathered depth of k, is issued after that
     // depth is read, and the step starts with vmcnt(0) instead of keeping the source record in flight)
     if (D16) __builtin_amdgcn_sched_barrier(0);
-    const MapPx mp = stage_c<ZMASK, D16>(d, gt, cur, mw, bp);     // gathers(k) land; issue map cell(k)
-    nxt = stage_b<ZMASK, D16>(d, T, s_next, twf, thf, bp);        // issue gathers(k+1)
+    const MapPx mp = stage_c<ZMASK, D16, true>(d, gt, cur, mw, bp);  // gathers(k) land; issue map cell(k)
+    nxt = stage_b<ZMASK, D16, true>(d, T, s_next, twf, thf, bp);     // issue gathers(k+1)
     nxt_i = s_next.intensity;
     if (cur.live) {
       const Terms t = stage_d(d, gt, cur, mp, cur_i, mw);
@@ -545,7 +592,8 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
 // DEPTH16: level 0 of a batch whose every image carries points_from_depth and passes backproject_proven (devmath.hpp) —
 // the points are rebuilt, in straight-line code (backproject_px_proven), from the u16 depth
 // planes (D16_SIDES: the target's, and the source's unless A3D_ICP_DEPTH16_SRC=0) instead of read.
-template <bool ZMASK, bool DEPTH16>
+// CLASSIC (diagnostics build only): the step order of pixel_pass before B(k+1) moved ahead of C(k), as a cross-check.
+template <bool ZMASK, bool DEPTH16, bool CLASSIC = false>
 __global__ void __launch_bounds__(256, 1)
     image_icp_head_kernel(const LevelDesc* __restrict__ descs, const JobState* __restrict__ states_in,
                           JobState* __restrict__ states_out, Gates gt, const float* __restrict__ partials_in,
@@ -578,7 +626,7 @@ __global__ void __launch_bounds__(256, 1)
   if ((int)s_state[15] == A3D_OK) {  // a failed job stays frozen: its blocks contribute nothing
     auto uni = [&](int k) { return __uint_as_float(__builtin_amdgcn_readfirstlane(s_state[k])); };
     const Pose T{{uni(0), uni(1), uni(2)}, {uni(3), uni(4), uni(5), uni(6)}};
-    pixel_pass<ZMASK, D16>(d, gt, T, base, ppt, s0, s1, acc);
+    pixel_pass<ZMASK, D16, CLASSIC>(d, gt, T, base, ppt, s0, s1, acc);
   }
   A3D_HEAD_STAMP(3);  // pixel pass done
   block_reduce_store<GN_PARTIAL, false>(acc, partials_out + (size_t)pair * job_stride + (size_t)tile * GN_PARTIAL);
@@ -1360,6 +1408,23 @@ a3d_status launch_head_kernel(a3d_multiscale_batch* b, uint32_t level, uint32_t 
   const float* part_in = b->d_partials + (size_t)((seq + 1u) & 1u) * b->partials_half + (size_t)p0 * job_stride;
   float* part_out = b->d_partials + (size_t)(seq & 1u) * b->partials_half + (size_t)p0 * job_stride;
   const LevelDesc* descs = b->d_descs + (size_t)level * P + p0;
+#ifdef A3D_DIAGNOSTICS
+  // A3D_ICP_STEP_ORDER=classic: the pixel loop in its earlier order (the map cell requested by stage C): the same bits
+  const char* oenv = A3D_DIAG_ENV("A3D_ICP_STEP_ORDER");
+  if (oenv && strcmp(oenv, "classic") == 0) {
+    if (b->depth16 && level == 0)
+      hipLaunchKernelGGL((image_icp_head_kernel<true, true, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
+                         st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    else if (b->zmask)
+      hipLaunchKernelGGL((image_icp_head_kernel<true, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
+                         st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    else
+      hipLaunchKernelGGL((image_icp_head_kernel<false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
+                         st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    A3D_HIP_TRY(hipGetLastError());
+    return A3D_OK;
+  }
+#endif
   if (b->depth16 && level == 0)
     hipLaunchKernelGGL((image_icp_head_kernel<true, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
                        st_out, b->gates[level], part_in, part_out, job_stride, prev);

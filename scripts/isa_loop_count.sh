@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 OUT=${TMPDIR:-/tmp}/a3d_isa && mkdir -p $OUT
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize --offload-arch=gfx950 "$@" \
   -Iinclude -S --cuda-device-only align3d_amd/csrc/image_icp.hip -o $OUT/image_icp.s 2>/dev/null
-KERNEL=${KERNEL:-_ZN12_GLOBAL__N_121image_icp_head_kernelILb1ELb0EE}  # (KERNEL=_ZN12_GLOBAL__N_116image_icp_kernelILi1ELb0E: the last-block form)
+KERNEL=${KERNEL:-_ZN12_GLOBAL__N_121image_icp_head_kernelILb1ELb0ELb0EE}  # (KERNEL=_ZN12_GLOBAL__N_116image_icp_kernelILi1ELb0E: the last-block form)
 n=$(grep -n "^${KERNEL}.*:" $OUT/image_icp.s | head -1 | cut -d: -f1)
 awk -v n=$n 'NR>=n' $OUT/image_icp.s | awk '/^\.Lfunc_end/{exit} {print}' > $OUT/kernel.s
 st=$(grep -n "Loop Header: Depth=1" $OUT/kernel.s | head -1 | cut -d: -f1)
