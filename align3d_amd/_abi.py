@@ -236,6 +236,15 @@ SIGNATURES = {
         [_P, C.POINTER(IcpParamsC), C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.POINTER(GnStateC)],
     ),
     "a3d_voxel_map_icp_last_device_ms": (_ST, [_P, C.POINTER(C.c_float)]),
+    "a3d_point_cloud_render_device": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), _P, C.POINTER(PoseC), C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64,
+         C.c_uint64, C.c_float, _P, _PP],
+    ),
+    "a3d_voxel_map_render": (
+        _ST,
+        [_P, C.POINTER(PoseC), C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_float, _P, _PP],
+    ),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

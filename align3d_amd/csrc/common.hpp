@@ -102,9 +102,10 @@ struct a3d_context {
   // tile counts: pointcloud.hip), voxel-grid downsample (the same plus its ballot words and hash tables:
   // voxel_downsample.hip; both laid out by cloud_batch.hpp) and the bare job table of the cloud transform / merge
   // (cloud_transform.hip), [4] the per-image, per-level pointer table of a3d_range_image_pyramids /
-  // a3d_range_image_compute_intensity (pyramid.hip).
-  void* scratch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t scratch_size[5] = {0, 0, 0, 0, 0};
+  // a3d_range_image_compute_intensity (pyramid.hip), [5] the z-buffer of a render and, for the map form, the extracted
+  // cloud behind it (cloud_render.hip; host-synchronous; region 3 is the extract's own at that moment).
+  void* scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t scratch_size[6] = {0, 0, 0, 0, 0, 0};
   // Device blocks handed back by freed kd-trees / Icp objects (ctx_block_release), kept for the next one of about the
   // same size (ctx_block_alloc): Icp::new per frame then costs no hipMalloc / hipFree (each a device-wide
   // synchronisation, ~0.1 ms).  Reuse is stream-ordered: everything on a context runs on its one stream.

@@ -471,6 +471,7 @@ void ctx_destroy_now(a3d_context* ctx) {
   hipFree(ctx->scratch[2]);
   hipFree(ctx->scratch[3]);
   hipFree(ctx->scratch[4]);
+  hipFree(ctx->scratch[5]);
   if (ctx->ev_start) hipEventDestroy(ctx->ev_start);
   if (ctx->ev_stop) hipEventDestroy(ctx->ev_stop);
   for (hipEvent_t e : ctx->kd_ev)

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _abi
 from .icp_params import IcpParams, MsIcpParams
-from .range_image import DeviceRangeImage, RangeImage, upload_pyramid
+from .range_image import CameraIntrinsics, DeviceRangeImage, RangeImage, upload_pyramid
 from .transform import Transform
 
 
@@ -285,6 +285,36 @@ class PointCloud:
         v.normals = _abi.ptr(self.normals)
         v.len = len(self.points)
         return v
+
+
+def _render(ctx, what, camera, camera_to_world, radius, return_index, call, name):
+    """The part DevicePointCloud.render and DeviceVoxelMap.render share: argument types, the pose's inverse, the index
+    plane's buffer and the new image's handle.  call(pose, camera, radius, d_index, out_handle) is the ABI entry."""
+    if not isinstance(camera, CameraIntrinsics):
+        raise TypeError(f"{what} takes a CameraIntrinsics (got {type(camera).__name__})")
+    if camera_to_world is not None and not isinstance(camera_to_world, Transform):
+        raise TypeError(f"{what}: camera_to_world is a Transform or None (got {type(camera_to_world).__name__})")
+    w, h = camera.width, camera.height
+    if w < 0 or h < 0:
+        raise _abi.InvalidParameter(f"{what}: the camera's width and height are the image's size (got {w} x {h})")
+    pose = None if camera_to_world is None else C.byref(camera_to_world.inverse().to_c())
+    handle = C.c_void_p()
+    d_index = None
+    try:
+        if return_index and 0 < w * h < 1 << 31:
+            d_index = ctx.malloc(w * h * 4)
+        _abi.check(call(pose, camera, float(radius), d_index, C.byref(handle)), name)
+        image = DeviceRangeImage(ctx, handle=handle)
+        if not return_index:
+            return image
+        try:
+            return image, ctx.to_host(d_index, np.empty((h, w), np.uint32))
+        except BaseException:
+            image.free()
+            raise
+    finally:
+        if d_index is not None:
+            ctx.free(d_index)
 
 
 class DevicePointCloud:
@@ -571,6 +601,21 @@ class DevicePointCloud:
         outs, index = DevicePointCloud._voxel_downsample([self], voxel_size, origin, return_index)
         return (outs[0], index[0]) if return_index else outs[0]
 
+    def render(self, camera, camera_to_world=None, radius=0.0, return_index=False):
+        """What a pinhole camera sees of this cloud, as a new DeviceRangeImage (a3d_point_cloud_render_device): the
+        inverse of from_range_image, PinholeCamera::project_to_image (src/camera.rs:177-202) over every point.  `camera`
+        is a CameraIntrinsics whose width / height are the image's size; `camera_to_world` has the sense of
+        PinholeCamera::new (its f32 inverse is applied; None: no pose, no arithmetic).  Per pixel the nearest point wins
+        (ties: the lowest index) and the image holds that point in the camera's frame, its normal and its colour when
+        the cloud has them; radius > 0 (metres) lets a point cover the pixels its disc would, at most 17 x 17.  The image
+        goes to pyramid() and MultiscaleAlign like any other.  return_index=True returns (image, index): a HOST uint32
+        [h][w] array of the winning point per pixel, 0xFFFFFFFF where there is none."""
+        v = self.view()
+        return _render(self.ctx, "DevicePointCloud.render", camera, camera_to_world, radius, return_index,
+                       lambda pose, k, r, d_index, out: self.ctx.lib.a3d_point_cloud_render_device(
+                           self.ctx.handle, C.byref(v), self.d_colors, pose, k.fx, k.fy, k.cx, k.cy, k.width, k.height, r,
+                           d_index, out), "a3d_point_cloud_render_device")
+
     def len(self):
         return self.n
 
@@ -807,6 +852,15 @@ class DeviceVoxelMap:
         ms = C.c_float()
         _abi.check(self.ctx.lib.a3d_voxel_map_icp_last_device_ms(self.handle, C.byref(ms)))
         return ms.value
+
+    def render(self, camera, camera_to_world=None, radius=0.0, return_index=False):
+        """DevicePointCloud.render over the live map (a3d_voxel_map_render): bit for bit what extract().render(...) gives,
+        the index plane (extract rows) included, without a cloud of its own: the model image of frame-to-model tracking,
+        with the map's normals and colours when it keeps them.  The map is not changed."""
+        return _render(self.ctx, "DeviceVoxelMap.render", camera, camera_to_world, radius, return_index,
+                       lambda pose, k, r, d_index, out: self.ctx.lib.a3d_voxel_map_render(
+                           self.handle, pose, k.fx, k.fy, k.cx, k.cy, k.width, k.height, r, d_index, out),
+                       "a3d_voxel_map_render")
 
     def clear(self):
         """Empties the map and keeps its allocation; sequence numbers restart at 0."""

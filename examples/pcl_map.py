@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
-        [--voxel V [--online [--check-batch | --window-box R | --window-frames W]]] [--colors] [--out map.npy]
+        [--voxel V [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
+        [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -20,7 +21,12 @@ half-side R (metres) around the current camera position, or the cells whose poin
 cells, so total(), printed per frame beside the cell count, stays bounded instead of running towards 2^32.  --colors carries
 every point's RGB colour from the frames through whichever of these paths is selected (merge, voxel_downsample, the online
 map and its retains: a colour follows its point and decides nothing), and --out then also writes <out>_colors.npy ([N, 3]
-u8) beside the points.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+u8) beside the points.  --render-track (with --online; it carries the colours too) is frame-to-model tracking the way
+KinectFusion does it: before frame k goes in, the live map is rendered (DeviceVoxelMap.render, radius V / 2, the frame's
+intrinsics and size) at the pose the odometry predicts, the corrected pose of frame k - 1 times the pair's alignment;
+pyramid(3) of that image is the target of a MultiscaleAlign, point-to-plane and intensity terms, whose source is the
+frame's own pyramid; the frame is inserted under the corrected pose, and the mean distance of the camera positions from
+the dataset's trajectory is printed with and without the correction.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -30,8 +36,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from align3d_amd import (Context, DevicePointCloud, DeviceVoxelMap, Icp, IcpBatch, IcpParams,  # noqa: E402
-                         RangeImageBuilder, SlamTbDataset, Transform, TrajectoryBuilder)
+from align3d_amd import (A3dError, Context, DevicePointCloud, DeviceVoxelMap, Icp, IcpBatch, IcpParams,  # noqa: E402
+                         MsIcpParams, MultiscaleAlign, RangeImageBuilder, SlamTbDataset, Transform, TrajectoryBuilder)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("dataset", nargs="?", default=os.path.join(ROOT, "tests", "golden", "rgbd", "sample1"))
@@ -44,6 +50,8 @@ ap.add_argument("--window-box", type=float, default=None, metavar="R",
                 help="with --online: after each insert keep only the cells within R metres (per axis) of the camera")
 ap.add_argument("--window-frames", type=int, default=None, metavar="W",
                 help="with --online: after each insert keep only the cells whose point came with the last W frames")
+ap.add_argument("--render-track", action="store_true",
+                help="with --online: correct each frame's pose against a rendering of the live map before it is inserted")
 ap.add_argument("--colors", action="store_true", help="carry the frames' RGB colours into the map")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
 args = ap.parse_args()
@@ -58,14 +66,22 @@ if windowed and args.check_batch:
     ap.error("--check-batch compares whole maps: not with --window-box or --window-frames")
 if args.window_frames is not None and args.window_frames < 1:
     ap.error("--window-frames keeps at least one frame")
+if args.render_track and not args.online:
+    ap.error("--render-track needs --online")
+if args.render_track and args.check_batch:
+    ap.error("--check-batch compares maps built under the same poses: not with --render-track")
+args.colors = args.colors or args.render_track  # (the intensity term reads the map's colours)
 
 ctx = Context(0)
 ds = SlamTbDataset.load(args.dataset)
 frames = [ds.get(i) for i in range(min(ds.len(), args.max_frames or ds.len()))]
 cam, _, _, depth_scale = frames[0]
-built = RangeImageBuilder(ctx).pyramid_levels(1).with_intensity(False).build_many(cam, [(f[1], f[2]) for f in frames],
-                                                                                  depth_scale)
+builder = RangeImageBuilder(ctx).pyramid_levels(1).with_intensity(False)
+if args.render_track:  # the frames are also the sources of the frame-to-model alignment: three levels, with intensities
+    builder = RangeImageBuilder(ctx).pyramid_levels(3)
+built = builder.build_many(cam, [(f[1], f[2]) for f in frames], depth_scale)
 images = [pyramid[0] for pyramid in built]
+coarser = [level for pyramid in built for level in pyramid[1:]]
 clouds = DevicePointCloud.from_range_images(images, colors=args.colors)  # frame k's cloud, resident
 # pair k: frame k + 1 (source) onto frame k (target)
 batch = IcpBatch(ctx, IcpParams.default(), clouds[:-1])
@@ -93,7 +109,21 @@ if args.online:
     online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None, colors=args.colors)
     offered = 0
     starts = collections.deque()  # --window-frames: the first sequence number of each kept frame, in the map's numbering
+    corrected = []  # --render-track: the poses the frames went in under
     for k, (cloud, pose) in enumerate(zip(clouds, camera_to_world)):  # what a live caller does as each frame arrives
+        if args.render_track:
+            if k > 0:
+                pose = corrected[-1] * poses[k - 1] if status[k - 1] == 0 else corrected[-1]  # the odometry's prediction
+                model = online.render(cam, pose, radius=args.voxel / 2).pyramid(3)
+                try:
+                    aligner = MultiscaleAlign.new(ctx, MsIcpParams.default(), model)
+                    pose = pose * aligner.align(built[k])  # (the frame in the rendered camera's frame, then in the world)
+                    aligner.free()
+                except A3dError as e:
+                    print(f"frame {k}: no correction against the rendered map ({e})")
+                for level in model:
+                    level.free()
+            corrected.append(pose)
         if args.window_frames is not None:
             starts.append(online.total())
         online.insert(cloud, pose)
@@ -110,6 +140,14 @@ if args.online:
             starts = collections.deque(marks.tolist())
         if windowed:
             print(f"frame {k}: {online.cells()} cells, total {online.total()} (offered so far: {offered})")
+    if args.render_track:
+        truth = ds.trajectory()
+        if truth is not None:
+            def mean_error(estimate):
+                origin = truth.camera_to_world[0].inverse()
+                return float(np.mean([np.linalg.norm(e.t - (origin * truth.camera_to_world[i]).t) for i, e in enumerate(estimate)]))
+            print(f"mean trajectory error over {len(corrected)} frames: odometry alone {mean_error(camera_to_world):.4e} m, "
+                  f"corrected against the rendered map {mean_error(corrected):.4e} m")
     # frame to map against the LIVE map: no extract, no kd-tree, and the frame stays in its own coordinates: the map's
     # association (DeviceVoxelMap.nearest) takes the tree's place and the alignment starts from the odometry pose
     aligned = online.align(clouds[-1], IcpParams.default(), initial=camera_to_world[-1])
@@ -154,6 +192,6 @@ if args.out:
         np.save(colors_out, world_map.download_colors())
         print("wrote", colors_out)
 batch.free()
-for x in [world_map] + clouds + images:
+for x in [world_map] + clouds + images + coarser:
     x.free()
 ctx.close()

@@ -28,6 +28,8 @@ extern "C" {
 #endif
 
 #define A3D_ABI_VERSION 1
+/* a3d_point_cloud_render_device: the largest half-width, in pixels, of a row's footprint (at most 17 x 17 per row). */
+#define A3D_RENDER_MAX_HALF_WIDTH 8
 
 typedef enum a3d_status {
   A3D_OK = 0,
@@ -730,6 +732,55 @@ a3d_status a3d_voxel_map_icp_accumulate_device(a3d_voxel_map* map, const a3d_icp
                                                a3d_gn_state* out_state);
 /* Instrumentation: device time (ms) of the iteration launches of the most recent a3d_voxel_map_icp_align_device. */
 a3d_status a3d_voxel_map_icp_last_device_ms(a3d_voxel_map* map, float* out_ms);
+
+/* ---- PinholeCamera::project_to_image over a cloud (src/camera.rs:177-202) ------------------ */
+
+/* Renders a resident cloud into the resident RangeImage a pinhole camera would see: the inverse of
+ * a3d_range_image_to_point_cloud, with PinholeCamera::project_to_image (src/camera.rs:177-202) applied to every row.
+ * d_cloud: DEVICE pointers on the context's GPU ([len][3] f32 points, normals or NULL), d_colors: DEVICE [len][3] u8 or
+ * NULL, all read during the call only.  world_to_camera_host: PinholeCamera's world_to_camera (the inverse of the
+ * camera_to_world given to PinholeCamera::new), NULL = none.  fx, fy, cx, cy are cast to f32 once.  The rule, all of it in
+ * f32 with every operation rounded on its own; for each row k, in this order:
+ *   1. p = transform_vector(world_to_camera, points[k]) (src/transform.rs:138-145); without a pose p = points[k] verbatim.
+ *   2. z = p.z; the row is dropped unless z > 0 and z < +inf (a NaN fails both).
+ *   3. u = p.x * fx / z + cx, v = p.y * fy / z + cy (CameraIntrinsics::project, camera.rs:64-70).
+ *   4. ui = round(u), vi = round(v), halves away from zero (f32::round, camera.rs:194); the row is dropped unless
+ *      0 <= ui < width and 0 <= vi < height compared as f32 (camera.rs:196): -0.0 passes, NaN and infinities fail.  This is
+ *      not the (u + 0.5) as i32 of the ICP kernels: u = 0.49999997 lands in column 0 here.
+ *   5. The footprint's half-widths are 0 for radius == 0, else hx = min(floor(radius * fx / z), 8) and
+ *      hy = min(floor(radius * fy / z), 8) (the product is rounded, then divided; 8 = A3D_RENDER_MAX_HALF_WIDTH).
+ *   6. The footprint is columns [ui - hx, ui + hx] x rows [vi - hy, vi + hy] clipped to the image; a row whose centre
+ *      pixel is outside the image is dropped whole (the reference's None).
+ *   7. Every pixel of the footprint is offered the key bits(z) << 32 | k, and a pixel's winner is the MINIMUM key: the
+ *      nearest surface, and on equal z bits the lowest row (z > 0 and finite, so its bits are monotone).
+ * A pixel with winner k gets mask 1, point p of step 1 (the true transformed point, not a pixel-centre back-projection:
+ * with radius > 0 one row may fill many pixels with the same point and normal, a surfel to point-to-plane ICP), normal
+ * transform_normal(world_to_camera, normals[k]) (verbatim without a pose), colour colors[k] byte for byte and index k; a
+ * pixel without a winner gets mask 0, +0 points and normals, colour 0, 0, 0 and index 0xFFFFFFFF.  The result does not
+ * depend on launch geometry, scheduling or how often the call runs.
+ * *out_image: an ordinary image on ctx (a3d_range_image_free) that carries fx, fy, cx, cy as given, has normals iff
+ * d_cloud->normals is not NULL and colours iff d_colors is not NULL (a non-NULL d_colors for a cloud that has none is the
+ * caller's business: the view does not know), and has no intensities and no map: a3d_range_image_compute_intensity /
+ * a3d_range_image_pyramids add them as for an uploaded image with colours.  d_out_index: NULL, or DEVICE [height][width]
+ * u32 for the index plane.  Host-synchronous; three launches whatever the sizes; width * height * 8 bytes of context
+ * scratch for the z-buffer.  len == 0 is A3D_OK with an all-empty image.
+ * Decided on the host before anything is launched or allocated (A3D_INVALID_PARAMETER, *out_image untouched): a NULL ctx,
+ * d_cloud or out_image; width or height 0, or width * height >= 2^31; a non-finite intrinsic, or (float)fx <= 0 or
+ * (float)fy <= 0; a radius that is NaN, infinite or negative; len > 2^32 - 2; NULL points with len > 0; an index plane
+ * that overlaps the cloud.  On any failure *out_image is untouched and no memory is kept. */
+a3d_status a3d_point_cloud_render_device(a3d_context* ctx, const a3d_point_cloud_view* d_cloud, const uint8_t* d_colors,
+                                         const a3d_pose* world_to_camera_host /* NULL: none */,
+                                         double fx, double fy, double cx, double cy, uint64_t width, uint64_t height,
+                                         float radius, uint32_t* d_out_index /* NULL, or DEVICE [h][w] */,
+                                         a3d_device_image** out_image);
+/* PinholeCamera::project_to_image (src/camera.rs:177-202) over the live map: bit for bit, the index plane included,
+ * a3d_point_cloud_render_device applied to what a3d_voxel_map_extract_rgb would return now (the row index is the extract's
+ * row); the image has normals iff the map has them and colours iff the map has them; an empty map gives an all-empty
+ * image.  The extract goes into context scratch inside the call (cells * 27 bytes behind the z-buffer) and the same
+ * kernels run on it.  The same refusals as above with `map` in place of ctx and d_cloud; the map is never changed. */
+a3d_status a3d_voxel_map_render(a3d_voxel_map* map, const a3d_pose* world_to_camera_host, double fx, double fy, double cx,
+                                double cy, uint64_t width, uint64_t height, float radius, uint32_t* d_out_index,
+                                a3d_device_image** out_image);
 
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
