@@ -189,7 +189,8 @@ __global__ void __launch_bounds__(256)
 // ONE u64 (value sum << 24 | count) and a pixel is ONE integer add (in the gather-splat: an LDS add into the owning
 // thread's slot) instead of two f64 atomics; integer adds are exact, so the cell holds exactly the reference's f64 sums.
 constexpr int PACK_SHIFT = 24;
-// When at most 255 pixels can splat into one (row, column) of the grid — sigma_space below ~14 — the count of a cell
+// When at most 255 pixels can splat into one (row, column) of the grid — floor(sigma_space) <= 13, the rule of
+// bilateral_grids_enqueue: 13.999 takes these cells, 14.0 the wide ones — the count of a cell
 // is < 2^8 and its value sum < 255 x 65535 < 2^24: the cell is ONE u32 (value sum << 8 | count), half the bytes to
 // write and to load in the blur.
 template <typename CELL>
@@ -1154,11 +1155,14 @@ a3d_status bilateral_grids_enqueue(a3d_context* ctx, const uint16_t* d_depth, ui
   const size_t extent_bytes = pad256((size_t)lf * columns * sizeof(uint2));
   const size_t head_bytes = scal_only + partial_bytes + flag_bytes + list_bytes + table_bytes + extent_bytes;
   capacity = (capacity + 3) & ~3ull;  // a multiple of four cells: every frame's packed grid starts 16-byte aligned
-  // at most floor(sigma) + 1 image rows (columns) round to one grid row (column): 4-byte cells while a (row, column)
-  // can not receive more than 255 pixels (A3D_BILATERAL_CELLS=wide: always 8-byte cells, a cross-check)
-  const uint32_t reach = (uint32_t)std::min(sigma_space, 1e6) + 2;
+  // at most floor(sigma) + 1 image rows (columns) round to one grid row (column), so a (row, column) receives at most
+  // (floor(sigma) + 1)^2 pixels.  4-byte cells while (floor(sigma_space) + 2)^2 <= 255 (one row and column to spare), i.e.
+  // while floor(sigma_space) <= 13: 13.999 is narrow (196 pixels at most), 14.0 is wide; tests/test_frame_prep_bounds_cpu.py
+  // holds the bounds.  The rule is written as that comparison: the square formed in 32 bits wrapped to 0 at
+  // floor(sigma_space) + 2 == 65536 and chose narrow cells for sigma_space in [65534, 65535), where one (row, column)
+  // takes the whole image.  (A3D_BILATERAL_CELLS=wide: always 8-byte cells, a cross-check)
   const char* cells_mode = A3D_DIAG_ENV("A3D_BILATERAL_CELLS");
-  const bool narrow = reach * reach <= 255 && !(cells_mode && !strcmp(cells_mode, "wide"));
+  const bool narrow = sigma_space < 14.0 && !(cells_mode && !strcmp(cells_mode, "wide"));
   const uint32_t cell_bytes = narrow ? 4 : 8;
   const size_t packed_bytes = pad256((size_t)lf * capacity * cell_bytes);
   void* region = nullptr;

@@ -483,7 +483,8 @@ def test_builder_keeps_its_grid_scratch_clean_between_enqueues():
 
 
 def test_bilateral_wide_cells_for_a_large_sigma_space():
-    """sigma_space >= 15: more than 255 pixels can fall into one grid (row, column), so the packed cells are u64
+    """floor(sigma_space) > 13, i.e. sigma_space >= 14.0 (the rule tests/test_frame_prep_bounds_cpu.py states; 16.0 and 23.5
+    here): more than 255 pixels could fall into one grid (row, column), so the packed cells are u64
     (value sum << 24 | count) and the blur carries f64 throughout — the other instantiation of splat / blur / unsplat.
     The host filter and the frame builder (two enqueues on one context: the grid scratch must come back clean) against
     the oracle, bit for bit; footprints of 16-17 x 16-17 pixels also take several load patches per grid column."""
