@@ -601,6 +601,99 @@ class DevicePointCloud:
         outs, index = DevicePointCloud._voxel_downsample([self], voxel_size, origin, return_index)
         return (outs[0], index[0]) if return_index else outs[0]
 
+    @staticmethod
+    def estimate_normals_many(clouds, radius, viewpoints=None, min_neighbors=3, orient="viewpoint", curvature=False,
+                              counts=False, dropped=False):
+        """estimate_normals for resident clouds of one context in ONE call and one wait, whatever their number
+        (a3d_point_clouds_estimate_normals_device).  viewpoints: None (the origin for every cloud) or one entry per cloud,
+        each None, three coordinates, or a Transform (a camera-to-world pose, whose translation is taken).  Returns the
+        valid-row count of each cloud; with curvature / counts, a tuple (valid, [curvature arrays], [count arrays]) of
+        what was asked for, downloaded to the host; dropped=True appends the per-cloud number of dropped rows (coordinates
+        that are not finite or beyond 2^20 cells) to that tuple."""
+        clouds = list(clouds)
+        extras = bool(curvature) + bool(counts) + bool(dropped)
+        if orient not in ("viewpoint", "normals"):
+            raise _abi.InvalidParameter(f'estimate_normals: orient is "viewpoint" or "normals" (got {orient!r})')
+        if not clouds:
+            return ([],) * (1 + extras) if extras else []
+        clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "estimate_normals")
+        n = len(clouds)
+        eyes = None
+        if viewpoints is not None:
+            viewpoints = list(viewpoints)
+            if len(viewpoints) != n:
+                raise _abi.InvalidParameter(f"estimate_normals: {n} clouds but {len(viewpoints)} viewpoints")
+            e = np.zeros((n, 3), np.float32)
+            for i, v in enumerate(viewpoints):
+                if isinstance(v, Transform):
+                    v = v.t
+                if v is not None:
+                    v = np.ascontiguousarray(v, np.float32).reshape(-1)
+                    if v.size != 3:
+                        raise _abi.InvalidParameter("estimate_normals: a viewpoint has three coordinates")
+                    e[i] = v
+            eyes = (C.c_float * (3 * n))(*e.reshape(-1).tolist())
+        by_normals = orient == "normals"
+        if by_normals and any(c.d_normals is None and c.n for c in clouds):
+            raise _abi.A3dError(_abi.A3D_MISSING_FIELD, 'estimate_normals: orient="normals" on a cloud without normals')
+        fresh, d_curv, d_counts = [], [], []
+        try:
+            for c in clouds:
+                if c.d_normals is None:
+                    c.d_normals = ctx.malloc(max(1, c.n) * 12)
+                    fresh.append(c)
+                if curvature:
+                    d_curv.append(ctx.malloc(max(1, c.n) * 4))
+                if counts:
+                    d_counts.append(ctx.malloc(max(1, c.n) * 4))
+            valid, n_dropped = (C.c_uint64 * n)(), (C.c_uint64 * n)()
+            _abi.check(
+                ctx.lib.a3d_point_clouds_estimate_normals_device(
+                    ctx.handle, DevicePointCloud._views(clouds), n, float(radius), int(min_neighbors), eyes,
+                    1 if by_normals else 0, (C.c_void_p * n)(*[c.d_normals for c in clouds]),
+                    (C.c_void_p * n)(*d_curv) if curvature else None, (C.c_void_p * n)(*d_counts) if counts else None,
+                    valid, n_dropped),
+                "a3d_point_clouds_estimate_normals_device",
+            )
+            out = ([int(v) for v in valid],)
+            if curvature:
+                out += ([ctx.to_host(d, np.empty(c.n, np.float32)) if c.n else np.empty(0, np.float32)
+                         for d, c in zip(d_curv, clouds)],)
+            if counts:
+                out += ([ctx.to_host(d, np.empty(c.n, np.uint32)) if c.n else np.empty(0, np.uint32)
+                         for d, c in zip(d_counts, clouds)],)
+            if dropped:
+                out += ([int(v) for v in n_dropped],)
+        except BaseException:
+            for c in fresh:  # a cloud that had no normals has none after a failed call
+                ctx.free(c.d_normals)
+                c.d_normals = None
+            raise
+        finally:
+            for d in d_curv + d_counts:
+                ctx.free(d)
+        return out if extras else out[0]
+
+    def estimate_normals(self, radius, viewpoint=None, min_neighbors=3, orient="viewpoint", curvature=False, counts=False,
+                         dropped=False):
+        """Gives this cloud normals estimated from its own points (a3d_point_clouds_estimate_normals_device): per point,
+        the direction of least spread of the points within `radius` (the cells of a grid of pitch `radius` around the
+        point's own, then the ball), turned towards `viewpoint` (three coordinates or a camera-to-world Transform; None:
+        the origin).  orient="normals" turns it along the normal the row already has instead, which refreshes the normals
+        of a voxel map's extract without knowing which camera saw each cell.  Allocates d_normals if the cloud has none
+        and overwrites them otherwise.  A row with fewer than min_neighbors (>= 3) neighbours, itself included, with all
+        its neighbours on one spot, or with a coordinate that is not finite or beyond 2^20 cells gets the normal
+        (0, 0, 0).  Such rows stay in the cloud: a zero normal is at pi / 2 from every normal, so every aligner's
+        max_normal_angle gate (below pi / 2) rejects the row, and nothing needs to be compacted.  Returns the number of
+        valid rows; with curvature=True and / or counts=True a tuple (valid, curvature [len] f32, counts [len] uint32) of
+        what was asked for (host arrays: curvature = smallest eigenvalue / trace, counts = neighbours found); dropped=True
+        appends the number of dropped rows."""
+        out = DevicePointCloud.estimate_normals_many([self], radius, None if viewpoint is None else [viewpoint],
+                                                     min_neighbors, orient, curvature, counts, dropped)
+        if not (curvature or counts or dropped):
+            return out[0]
+        return (out[0][0],) + tuple(x[0] for x in out[1:])
+
     def render(self, camera, camera_to_world=None, radius=0.0, return_index=False):
         """What a pinhole camera sees of this cloud, as a new DeviceRangeImage (a3d_point_cloud_render_device): the
         inverse of from_range_image, PinholeCamera::project_to_image (src/camera.rs:177-202) over every point.  `camera`

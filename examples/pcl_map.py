@@ -2,7 +2,7 @@
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
         [--voxel V [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
-        [--out map.npy]
+        [--estimate-normals R] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -26,7 +26,12 @@ KinectFusion does it: before frame k goes in, the live map is rendered (DeviceVo
 intrinsics and size) at the pose the odometry predicts, the corrected pose of frame k - 1 times the pair's alignment;
 pyramid(3) of that image is the target of a MultiscaleAlign, point-to-plane and intensity terms, whose source is the
 frame's own pyramid; the frame is inserted under the corrected pose, and the mean distance of the camera positions from
-the dataset's trajectory is printed with and without the correction.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+the dataset's trajectory is printed with and without the correction.  --estimate-normals R treats the frames as clouds
+from a sensor without a pixel grid: every frame's cloud drops its image normals and takes normals estimated from its own
+points within R metres (DevicePointCloud.estimate_normals_many, the viewpoint at the frame's camera) before anything is
+aligned; with --render-track the model that is rendered is then the map's extract with its normals refreshed from the
+map's own neighbourhood (estimate_normals(3 V, orient="normals"): one raw sensor normal per cell otherwise), and the
+trajectory errors printed are those of this variant.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -53,6 +58,9 @@ ap.add_argument("--window-frames", type=int, default=None, metavar="W",
 ap.add_argument("--render-track", action="store_true",
                 help="with --online: correct each frame's pose against a rendering of the live map before it is inserted")
 ap.add_argument("--colors", action="store_true", help="carry the frames' RGB colours into the map")
+ap.add_argument("--estimate-normals", type=float, default=None, metavar="R",
+                help="replace every frame's image normals by normals estimated from the cloud itself within R metres "
+                     "(with --render-track the rendered model's normals are refreshed too, within 3 V whatever R is)")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
 args = ap.parse_args()
 if args.online and not args.voxel:
@@ -83,6 +91,9 @@ built = builder.build_many(cam, [(f[1], f[2]) for f in frames], depth_scale)
 images = [pyramid[0] for pyramid in built]
 coarser = [level for pyramid in built for level in pyramid[1:]]
 clouds = DevicePointCloud.from_range_images(images, colors=args.colors)  # frame k's cloud, resident
+if args.estimate_normals is not None:  # in each camera's own frame: the viewpoint is the origin
+    valid = DevicePointCloud.estimate_normals_many(clouds, args.estimate_normals)
+    print(f"estimated normals within {args.estimate_normals} m: {sum(valid)} of {sum(c.len() for c in clouds)} rows valid")
 # pair k: frame k + 1 (source) onto frame k (target)
 batch = IcpBatch(ctx, IcpParams.default(), clouds[:-1])
 poses, status = batch.align(clouds[1:])
@@ -114,7 +125,13 @@ if args.online:
         if args.render_track:
             if k > 0:
                 pose = corrected[-1] * poses[k - 1] if status[k - 1] == 0 else corrected[-1]  # the odometry's prediction
-                model = online.render(cam, pose, radius=args.voxel / 2).pyramid(3)
+                if args.estimate_normals is not None:
+                    snapshot = online.extract()  # the model's normals from the model's own neighbourhood
+                    snapshot.estimate_normals(3 * args.voxel, orient="normals")
+                    model = snapshot.render(cam, pose, radius=args.voxel / 2).pyramid(3)
+                    snapshot.free()
+                else:
+                    model = online.render(cam, pose, radius=args.voxel / 2).pyramid(3)
                 try:
                     aligner = MultiscaleAlign.new(ctx, MsIcpParams.default(), model)
                     pose = pose * aligner.align(built[k])  # (the frame in the rendered camera's frame, then in the world)

@@ -584,6 +584,46 @@ a3d_status a3d_point_clouds_voxel_downsample_rgb_device(a3d_context* ctx, const 
                                                         uint32_t* const* d_out_index, const uint64_t* capacities,
                                                         uint64_t* out_lens, uint64_t* out_dropped);
 
+/* Normals of n resident clouds from their own neighbourhoods, each exactly as if it were passed alone, in a number of
+ * launches that does not depend on n; host-synchronous like the entries above.  For clouds that have no pixel grid to take
+ * normals from (a lidar scan, an uploaded cloud, a voxel map's extract).  Per point: the eigenvector of the smallest
+ * eigenvalue of the scatter matrix of its neighbours, oriented towards the cloud's viewpoint.  The rule, every f32
+ * operation rounded on its own, with r2 = radius * radius and s = 32768.0f / radius computed on the host:
+ *   1. grid of pitch radius at the origin (the downsample's cell and key); a point whose key is refused (NaN, infinite,
+ *      outside +-2^20 cells) is DROPPED: nobody's neighbour, normal (0,0,0), count 0, curvature 0;
+ *   2. the neighbours of point i are the kept points j of its cloud (i included) whose cell coordinates each differ from
+ *      i's by at most 1 and whose d = p_j - p_i has (d_x*d_x + d_y*d_y) + d_z*d_z <= r2;
+ *   3. q_k = (int) rintf(d_k * s);  N = sum 1, S_k = sum q_k, M_kl = sum q_k q_l in int64: no order dependence;
+ *   4. A_kl = (double)N * (double)M_kl - (double)S_k * (double)S_l;  mx = max |A_kl|;  the row is VALID iff
+ *      N >= min_neighbors and mx > 0, else normal 0 and curvature 0 (the count is still reported);
+ *      B = (float) ldexp(A, -e) with e the exponent of frexp(mx);
+ *   5. cyclic Jacobi in f32, exactly 6 sweeps over the pairs (0,1), (0,2), (1,2), each skipped iff a_pq == 0:
+ *      theta = (a_qq - a_pp) / (2 a_pq), t = (theta < 0 ? -1 : 1) / (|theta| + sqrtf(theta*theta + 1)),
+ *      c = 1 / sqrtf(t*t + 1), s = t*c;  a_pp -= t*a_pq, a_qq += t*a_pq, a_pq = 0;  a_op' = c*a_op - s*a_oq,
+ *      a_oq' = s*a_op + c*a_oq;  V_kp' = c*V_kp - s*V_kq, V_kq' = s*V_kp + c*V_kq (V starts as the identity);
+ *   6. n = the column of V at the smallest diagonal entry (ties: lowest index), divided by
+ *      sqrtf((n_x*n_x + n_y*n_y) + n_z*n_z);  curvature = lambda_min / ((l_0 + l_1) + l_2), or 0 if that sum is not > 0;
+ *   7. w = viewpoint - p_i (orient_by_normals != 0: the row's existing normal), dot = (n_x*w_x + n_y*w_y) + n_z*w_z,
+ *      n is negated iff dot < 0.
+ * A row with a zero normal takes no part in any alignment (its angle to any normal is pi / 2, which every gate below
+ * pi / 2 rejects), so nothing is compacted.  viewpoints_host: [n][3] f32 in host memory, NULL = the origin for every
+ * cloud.  d_out_normals[i]: [len_i][3]; d_out_curvature and d_out_counts: NULL, or per cloud NULL / [len_i] (counts: N of
+ * step 3).  out_valid[i] = valid rows of cloud i; out_dropped[i] (NULL ok) = dropped rows.
+ * d_out_normals[i] == d_clouds[i].normals (in place) is allowed: a thread reads only its own row's old normal, before it
+ * writes.  Every other overlap of an output with an input or another output is A3D_INVALID_PARAMETER.
+ * Decided on the host before anything is launched (nothing is touched): n == 0 is A3D_OK; a NULL ctx, d_clouds,
+ * d_out_normals or out_valid, a radius that is not finite or <= 0 (or so small that its square is 0 in f32),
+ * min_neighbors < 3, a non-finite viewpoint, a cloud of 2^32 points or more (or within one tile, < 2^21 points, of it),
+ * NULL points or NULL output normals of a non-empty cloud are A3D_INVALID_PARAMETER; orient_by_normals on a non-empty
+ * cloud without normals is A3D_MISSING_FIELD.  A cloud with len == 0 may have null pointers and yields zeros.
+ * Scratch memory (context-owned, grow-only, shared with the calls above): the downsample's hash table (32 to 64 bytes per
+ * point) plus 16 bytes per point for the cell-ordered copy and 96 bytes per cloud. */
+a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
+                                                    float radius, uint32_t min_neighbors, const float* viewpoints_host,
+                                                    int32_t orient_by_normals, float* const* d_out_normals,
+                                                    float* const* d_out_curvature, uint32_t* const* d_out_counts,
+                                                    uint64_t* out_valid, uint64_t* out_dropped);
+
 /* A persistent voxel map: the hash table of the downsample above kept between calls, so that resident clouds go in frame
  * by frame (a3d_voxel_map_insert) instead of merge + downsample of the whole map per frame.  The contract:
  *   After any sequence of inserts, the map's contents equal a3d_point_clouds_merge_device(all inserted clouds under their
