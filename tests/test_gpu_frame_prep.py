@@ -29,8 +29,10 @@ def test_compute_normals_bit_exact(ctx, sample, frame):
 
 def test_compute_normals_batch_bit_exact(ctx):
     """a3d_range_image_compute_normals_batch: many resident images in one launch (more than one 64-image launch here),
-    every image bit for bit the oracle's normals (structure.rs:184-262) — real frames, and a ragged size that is neither
-    a multiple of the 64 x 16 tile nor of a wave."""
+    every image bit for bit the oracle's normals (structure.rs:184-262) — real frames of 640 x 480, a multiple of the
+    64 x 16 tile of the four-pixel form, and five ragged images of 131 x 37, which are 24 235 pixels in their launch and
+    so run the ONE-pixel form (32 x 8 tiles), like the two-image tail launch of the 66.  The four-pixel form at sizes
+    that cut its tiles is in test_gpu_compute_normals_forms.py."""
     from align3d_amd import CameraIntrinsics, RangeImage, compute_normals_batch
 
     frames = [oracle_frame("sample1", k) for k in (0, 1, 4, 5)] + [oracle_frame("sample2", k) for k in (0, 1)]
@@ -400,22 +402,10 @@ def test_compute_normals_wide_dynamic_range_and_signed_zeros(ctx):
     division's range take the plain one), axis-aligned planes (cross products with -0.0 components), zero and huge
     neighbour distances (ratios 0, inf, NaN, exactly 4 and exactly 1/4) — all bit for bit the oracle's."""
     from align3d_amd import CameraIntrinsics, RangeImage
+    from normals_image_cases import wide_range_cases  # (shared with test_gpu_compute_normals_forms.py: every tile shape)
 
-    rng = np.random.default_rng(99)
-    h, w = 48, 80
-    cases = []
-    for scale in (1e-12, 1e-6, 1e-3, 1.0, 1e4, 1e9, 1e12):
-        cases.append((rng.normal(size=(h, w, 3)) * scale).astype(np.float32))
-    yy, xx = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
-    for plane in ((xx, yy, np.zeros_like(xx)), (-xx, yy, np.full_like(xx, 2.0)), (xx, -yy, xx * 0), (yy * 0, xx, -yy)):
-        cases.append(np.stack(plane, axis=-1).astype(np.float32))
-    # neighbour distances in exact ratios 4, 1/4, 1 and with repeated points (0 / 0)
-    steps = np.array([1.0, 2.0, 1.0, 0.5, 0.0, 4.0, 1.0, 1.0], np.float32)
-    xs = np.concatenate([[0.0], np.cumsum(np.tile(steps, w // 8 + 1))])[:w].astype(np.float32)
-    cases.append(np.stack([np.broadcast_to(xs, (h, w)), np.broadcast_to(xs[:h, None], (h, w)) if h <= w else yy, np.ones((h, w), np.float32)], axis=-1).astype(np.float32))
-    for k, pts in enumerate(cases):
-        pts = np.ascontiguousarray(pts)
-        mask = (rng.random((h, w)) > 0.1).astype(np.uint8)
+    for k, (pts, mask) in enumerate(wide_range_cases()):
+        h, w = mask.shape
         ref = O.compute_normals(pts, mask)
         got = RangeImage(pts, mask, CameraIntrinsics(100, 100, w / 2, h / 2, w, h)).compute_normals(ctx).normals
         assert np.array_equal(_bits(got), _bits(ref)), (k, int(np.sum(_bits(got) != _bits(ref))))
