@@ -206,6 +206,11 @@ SIGNATURES = {
         [_P, C.POINTER(PointCloudViewC), C.c_uint64, C.c_float, C.POINTER(C.c_float), _PP, _PP, _PP, C.POINTER(C.c_uint64),
          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
+    "a3d_point_clouds_voxel_mean_device": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), _PP, C.c_uint64, C.c_float, C.POINTER(C.c_float), _PP, _PP, _PP, _PP, _PP,
+         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    ),
     "a3d_point_clouds_estimate_normals_device": (
         _ST,
         [_P, C.POINTER(PointCloudViewC), C.c_uint64, C.c_float, C.c_uint32, C.POINTER(C.c_float), C.c_int32, _PP, _PP, _PP,

@@ -1,0 +1,681 @@
+// Voxel-grid downsampling of resident clouds by cell MEAN: per occupied cell of a grid of pitch v anchored at o, the
+// centroid of the cell's points, the mean of their normals and the mean of their colours.  The sibling
+// (voxel_downsample.hip) keeps one real sample per cell because an f32 mean depends on the summation order; here the
+// offsets are rounded to a lattice and summed in int64 (the answer of cloud_normals.hip), so the mean is a rule stated in
+// arithmetic: the same bits as its numpy restatement and the same bits under any permutation of the rows.
+//
+// The rule.  All f32 operations are rounded on their own (-ffp-contract=off, correctly rounded / and sqrt); f64
+// operations likewise.  Per call: v finite and > 0, a finite origin o (default 0).  Host constants in f32:
+// s = 32768.0f / v and u = v / 32768.0f.
+//  1. Cell.  voxel_key of voxel_grid.hpp, unchanged.  A point it refuses is dropped and counted.
+//  2. Offsets.  ctr_k = (c_k + 0.5f) * v + o_k and d_k = p_k - ctr_k, as voxel_key computes them.
+//     q_k = (int) rintf(d_k * s), ties to even.  Per cell, in int64: N = sum 1 and S_k = sum q_k.  |q_k| stays near 2^14,
+//     so with len < 2^32 nothing can overflow.
+//  3. Mean point.  If N == 1 the cell's only row is copied bit for bit: point, normal and colour.  Otherwise
+//     m_k = (float)((double)S_k / (double)N) and out_k = ctr_k + m_k * u, with ctr taken from the cell's representative
+//     (step 6).
+//  4. Mean normal (only when normals are written, N > 1).  A row's normal is counted iff its three components are finite
+//     and |n_k| <= 2.  r_k = (int) rintf(n_k * 1048576.0f), T_k = sum r_k in int64 over the counted rows (each sum stays
+//     <= 2^53: exact in f64).  L = sqrt((T_x*T_x + T_y*T_y) + T_z*T_z) in f64, out_n_k = L > 0 ? (float)((double)T_k / L)
+//     : 0.  A zero normal stays in the cloud: every aligner's angle gate rejects it, as after estimate_normals.
+//  5. Mean colour (only when colours are written, N > 1).  Per channel C = sum c in u64 and out_c = (2 C + N) / (2 N) in
+//     integer division, which rounds half up.
+//  6. Order, index, count.  A cell's representative is its lowest input index.  Output rows are in ascending order of
+//     representative (first-occurrence order), out_index[row] is that index, out_counts[row] = N as u32.
+//
+// The kernels: a counting sort by cell (the shape of cloud_normals.hip) and a reduction of each cell's contiguous run, so
+// no sum is contended and the scratch beyond the sibling's is 20 bytes per input point (a 16-byte record and a 4-byte row
+// number) plus 96 bytes per 64 points, not ten words per hash slot.  One upload, one fill and six launches over every tile
+// of every cloud of a batch, whatever the batch size (the job table of cloud_batch.hpp); no block waits on another block,
+// and the host waits once, at the end.
+//  1. vmean_count_kernel: a wave combines each run of lanes with the same key (a frame cloud is row-major: neighbouring
+//     lanes often share a cell); the run's first lane claims the slot of the key (load, then 64-bit atomicCAS on key + 1;
+//     the fill is zeros) and adds the run's length to the slot's count (the low half of its second word) and atomicMaxes
+//     ~index into the high half: the complement of the cell's lowest index, so that zero is "none yet".
+//  2. vmean_flag_kernel: a point is its cell's representative iff the slot's high half is ~its index; ballots, tile
+//     counts and row totals exactly as the sibling's pass 2.
+//  3. vmean_place_kernel: a thread per slot; the slot's high half becomes the start of the cell's run in the sorted
+//     records (a block takes its slots' total from the job's cursor with one atomicAdd), the low half stays the count.
+//  4. vmean_scatter_kernel: in input order with the sibling's pass-3 ranking.  A representative writes its record
+//     (x, y, z, index) at the START of its cell's run and its output row number beside it; the others take the positions
+//     start + count - 1 down to start + 1 (one atomicSub per run of lanes with the same key).
+//  5. vmean_reduce_kernel: a thread per record in cell order.  A wave's segmented scan sums the lattice offsets, the
+//     rounded normals and the colours of each run of equal keys.  A cell that lies inside the wave is finished there and
+//     written to its row.  A cell that crosses a wave boundary adds its partial sums to the spill accumulator of the
+//     64-record group in which it starts: at most one cell starts in a group and leaves it, so 12 words per 64 records
+//     are enough, and a cell of N rows adds to them N / 64 times, not N times.
+//  6. vmean_spill_kernel: a thread per accumulator finishes the cells that crossed.
+// Passes 5 and 6 write nothing if any cloud of the batch has more rows than its capacity, and bound every store by it.
+#include <cmath>
+#include <vector>
+
+#include "voxel_grid.hpp"  // VoxelGrid, voxel_key, slot_hash, VoxelSlot: shared with voxel_downsample.hip and voxel_map.hip
+
+using namespace a3d;
+
+namespace {
+
+constexpr uint32_t VM_THREADS = 256;
+constexpr uint32_t VM_WAVES = VM_THREADS / 64;
+constexpr uint32_t VM_ROUNDS = 4;
+constexpr uint32_t VM_CHUNK = VM_ROUNDS * VM_THREADS;  // points per chunk: a multiple of 64
+constexpr uint32_t VM_GROUPS = VM_CHUNK / 64;          // ballot words per chunk
+constexpr uint32_t VM_MAX_TILES = 4096;
+static_assert(VM_GROUPS <= 64, "a wave's lanes hold the chunk's ballot words");
+
+struct VmRecord {  // a kept point in cell order; the first record of a cell's run is its representative
+  float x, y, z;
+  uint32_t index;
+};
+static_assert(sizeof(VmRecord) == 16, "VmRecord layout");
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct VmSpill {  // the sums of the one cell that starts in a group of 64 records and crosses its end (zero-filled)
+  unsigned long long n;
+  long long s[3], t[3];
+  unsigned long long c[3];
+  unsigned long long head;  // the position of the cell's first record + 1; 0 = no such cell
+  unsigned long long pad;
+};
+static_assert(sizeof(VmSpill) == 96, "VmSpill layout");
+
+// One non-empty cloud of a batch as the kernels see it (uploaded per call).
+struct MeanJob {
+  const float* points;
+  const float* normals;   // read only when out_normals is set
+  const uint8_t* colors;  // read only when out_colors is set
+  float* out_points;
+  float* out_normals;    // null: no normals are written
+  uint8_t* out_colors;   // null: no colours are written
+  uint32_t* out_index;   // null: no indices are written
+  uint32_t* out_counts;  // null: no counts are written
+  VoxelSlot* table;      // slot_mask + 1 slots, zeroed before the count: key word 0 = empty, else key + 1
+  unsigned long long* flags;  // (len + 63) / 64 ballot words
+  VmRecord* sorted;           // len records, the first `kept` of them written
+  uint32_t* row_at;           // len row numbers, written at the first position of every run
+  VmSpill* spill;             // (len + 63) / 64 accumulators, zeroed
+  unsigned long long slot_mask;
+  unsigned long long capacity;
+  uint32_t len, first_tile, chunks_per_tile, n_tiles;
+};
+static_assert(sizeof(MeanJob) == 136, "MeanJob layout");
+
+struct MeanParams {
+  float s, u;
+};
+
+// The halves of a slot's second word (little-endian: [0] the count, [1] ~lowest index, later the run's start).
+__device__ __forceinline__ uint32_t* slot_half(VoxelSlot* slot, int h) { return (uint32_t*)&slot->best + h; }
+
+// The slot that holds `tag` (key + 1), or ~0 if the table has none (the walk stops at the first empty slot).
+__device__ __forceinline__ unsigned long long find_slot(const VoxelSlot* __restrict__ table, unsigned long long mask,
+                                                        unsigned long long tag) {
+  unsigned long long s = slot_hash(tag - 1) & mask;
+  for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
+    const unsigned long long k = table[s].key;
+    if (k == tag) return s;
+    if (k == 0) break;
+  }
+  return ~0ull;
+}
+
+// A run is a maximal stretch of lanes of one wave with the same key.  first: this lane starts one.
+__device__ __forceinline__ uint64_t run_heads(unsigned long long key, uint32_t lane, bool* first) {
+  const unsigned long long prev = __shfl_up(key, 1, 64);
+  *first = lane == 0 || prev != key;
+  return __builtin_amdgcn_ballot_w64(*first);
+}
+__device__ __forceinline__ uint32_t run_first_lane(uint64_t heads, uint32_t lane) {  // (lane 0 always starts a run)
+  return 63u - (uint32_t)__builtin_clzll(heads & (~0ull >> (63u - lane)));
+}
+__device__ __forceinline__ uint32_t run_end_lane(uint64_t heads, uint32_t lane) {  // one past the run's last lane
+  const uint64_t above = lane == 63u ? 0ull : heads >> (lane + 1u);
+  return above ? lane + 1u + (uint32_t)__builtin_ctzll(above) : 64u;
+}
+
+// Pass 1.  dropped[job] += dropped points (zeroed by the host upload); *fault is set if a table were ever full (it cannot
+// be: it has at least two slots per point).
+__global__ void __launch_bounds__(VM_THREADS)
+    vmean_count_kernel(const MeanJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid,
+                       unsigned long long* __restrict__ dropped, unsigned long long* __restrict__ fault) {
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MeanJob& j = jobs[ji];
+  const float* __restrict__ points = j.points;
+  VoxelSlot* table = j.table;
+  const unsigned long long mask = j.slot_mask;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (len < 2^32 - span: checked by the host)
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t n_dropped = 0;
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += VM_THREADS) {  // wave-uniform
+    const uint32_t p = base + lane;
+    unsigned long long key = VX_EMPTY;  // no key: a lane past the end or a dropped point
+    if (p < p_end && !voxel_key(*(const f32x3_u*)(points + 3 * (size_t)p), grid, &key, nullptr)) key = VX_EMPTY, ++n_dropped;
+    bool first;
+    const uint64_t heads = run_heads(key, lane, &first);
+    if (first && key != VX_EMPTY) {  // (no lane leaves the trip early: the next one shuffles again)
+      const uint32_t run = run_end_lane(heads, lane) - lane;
+      const unsigned long long tag = key + 1;
+      unsigned long long s = slot_hash(key) & mask;
+      bool placed = false;
+      for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
+        unsigned long long k = VX_LOAD_AGENT(&table[s].key);
+        if (k == 0) k = atomicCAS(&table[s].key, 0ull, tag);
+        if (k == 0 || k == tag) {
+          placed = true;
+          break;
+        }
+      }
+      if (placed) {
+        atomicAdd(slot_half(&table[s], 0), run);
+        // (a stale value can only be smaller than the true one, so the test never skips a needed update)
+        if (VX_LOAD_AGENT(slot_half(&table[s], 1)) < ~p) atomicMax(slot_half(&table[s], 1), ~p);
+      } else {
+        atomicMax(fault, 1ull);
+      }
+    }
+  }
+  n_dropped = wave_sum(n_dropped);
+  if (lane == 0 && n_dropped) atomicAdd(&dropped[ji], (unsigned long long)n_dropped);
+}
+
+// Pass 2: flags[p / 64] bit p % 64 = point p is its cell's representative; tile_counts[tile] = representatives of the
+// tile; lens[job] += the same (zeroed by the host upload).
+__global__ void __launch_bounds__(VM_THREADS)
+    vmean_flag_kernel(const MeanJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, uint32_t* __restrict__ tile_counts,
+                      unsigned long long* __restrict__ lens) {
+  __shared__ uint32_t s_wave[VM_WAVES];
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MeanJob& j = jobs[ji];
+  const float* __restrict__ points = j.points;
+  const VoxelSlot* __restrict__ table = j.table;
+  unsigned long long* __restrict__ flags = j.flags;
+  const unsigned long long mask = j.slot_mask;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t c = 0;  // wave-uniform
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += VM_THREADS) {  // wave-uniform
+    const uint32_t p = base + lane;
+    bool win = false;
+    unsigned long long key;
+    if (p < p_end && voxel_key(*(const f32x3_u*)(points + 3 * (size_t)p), grid, &key, nullptr)) {
+      const unsigned long long s = find_slot(table, mask, key + 1);
+      win = s != ~0ull && (uint32_t)(table[s].best >> 32) == ~p;
+    }
+    const uint64_t ballot = __builtin_amdgcn_ballot_w64(win);
+    if (lane == 0) flags[base >> 6] = ballot;
+    c += (uint32_t)__builtin_popcountll(ballot);
+  }
+  if (lane == 0) s_wave[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t total = 0;
+    for (uint32_t w = 0; w < VM_WAVES; ++w) total += s_wave[w];
+    tile_counts[tile] = total;
+    if (total) atomicAdd(&lens[ji], (unsigned long long)total);
+  }
+}
+
+// Pass 3: every occupied slot's second word = start << 32 | count, the starts handed out from cursor[job] (zeroed by the
+// upload; it ends as the job's kept count).  Tile t of a job takes slots [t * per, (t + 1) * per), per = ceil(slots / tiles).
+// A block walks its slots twice: first every wave sums the counts of its share, then the block takes its run of the
+// cursor with ONE atomicAdd and the waves hand out the starts on the second walk (the slots are in L2 by then).  The
+// cursors of a batch's jobs are neighbours in one or a few cache lines: an atomicAdd per wave and trip, as in
+// cloud_normals.hip, made this pass two thirds of a call on 64 clouds.
+__global__ void __launch_bounds__(VM_THREADS)
+    vmean_place_kernel(const MeanJob* __restrict__ jobs, uint32_t n_jobs, unsigned long long* __restrict__ cursor) {
+  __shared__ unsigned long long s_wave[VM_WAVES];
+  __shared__ unsigned long long s_start;
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MeanJob& j = jobs[ji];
+  VoxelSlot* table = j.table;
+  const unsigned long long slots = j.slot_mask + 1, per = (slots + j.n_tiles - 1) / j.n_tiles;
+  const unsigned long long s0 = (unsigned long long)(tile - j.first_tile) * per, s_end = min(slots, s0 + per);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  unsigned long long mine = 0;  // the counts of this wave's slots (per lane, then summed)
+  for (unsigned long long s = s0 + threadIdx.x; s < s_end; s += VM_THREADS)
+    if (table[s].key != 0) mine += (uint32_t)table[s].best;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  if (lane == 0) s_wave[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long total = 0;
+    for (uint32_t w = 0; w < VM_WAVES; ++w) total += s_wave[w];
+    s_start = total ? atomicAdd(&cursor[ji], total) : 0ull;
+  }
+  __syncthreads();
+  unsigned long long start = s_start;  // of this wave's first cell
+  for (uint32_t w = 0; w < wave; ++w) start += s_wave[w];
+  if (mine == 0) return;  // wave-uniform; no barrier follows
+  for (unsigned long long base = s0 + (threadIdx.x & ~63u); base < s_end; base += VM_THREADS) {  // wave-uniform
+    const unsigned long long s = base + lane;
+    const bool occupied = s < s_end && table[s].key != 0;
+    const uint32_t cnt = occupied ? (uint32_t)table[s].best : 0u;
+    uint32_t incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t up = __shfl_up(incl, o, 64);
+      if (lane >= (uint32_t)o) incl += up;
+    }
+    if (occupied) table[s].best = (start + (incl - cnt)) << 32 | cnt;
+    start += __shfl(incl, 63, 64);
+  }
+}
+
+// Pass 4: kept points into their cells' runs, the representative first, and its row number beside it.
+__global__ void __launch_bounds__(VM_THREADS)
+    vmean_scatter_kernel(const MeanJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid,
+                         const uint32_t* __restrict__ tile_counts, unsigned long long* __restrict__ fault) {
+  __shared__ uint32_t s_base;
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MeanJob& j = jobs[ji];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t t = tile - j.first_tile;
+  if (wave == 0) {
+    uint32_t s = 0;
+    for (uint32_t k = lane; k < t; k += 64) s += tile_counts[j.first_tile + k];
+    s = wave_sum(s);
+    if (lane == 0) s_base = s;
+  }
+  __syncthreads();
+  const float* __restrict__ points = j.points;
+  const unsigned long long* __restrict__ flags = j.flags;
+  VoxelSlot* table = j.table;
+  VmRecord* sorted = j.sorted;
+  uint32_t* row_at = j.row_at;
+  const unsigned long long mask = j.slot_mask;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK, n_groups = (len + 63u) >> 6;
+  const uint32_t p0 = t * span, p_end = min(len, p0 + span);
+  uint32_t base = s_base;  // representatives of the cloud before this chunk
+  for (uint32_t px0 = p0; px0 < p_end; px0 += VM_CHUNK) {  // block-uniform
+    // lane g < VM_GROUPS of every wave holds the ballot word of the chunk's group g; their exclusive prefix gives every
+    // group's offset (voxel_compact_kernel's form)
+    const uint32_t g = (px0 >> 6) + lane;
+    const uint64_t word = lane < VM_GROUPS && g < n_groups ? flags[g] : 0ull;
+    const uint32_t cnt = (uint32_t)__builtin_popcountll(word);
+    uint32_t incl = cnt;
+#pragma unroll
+    for (int o = 1; o < (int)VM_GROUPS; o <<= 1) {
+      const uint32_t up = __shfl_up(incl, o, 64);
+      if (lane >= (uint32_t)o) incl += up;
+    }
+    const uint32_t excl = incl - cnt;
+    uint64_t ballots[VM_ROUNDS];
+    uint32_t offs[VM_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < VM_ROUNDS; ++r) {
+      const int src = (int)(r * VM_WAVES + wave);
+      ballots[r] = (uint64_t)__shfl((unsigned long long)word, src, 64);
+      offs[r] = base + __shfl(excl, src, 64);
+    }
+    base += __shfl(incl, (int)VM_GROUPS - 1, 64);
+#pragma unroll
+    for (uint32_t r = 0; r < VM_ROUNDS; ++r) {  // (every lane of the wave goes through every round: the shuffles below)
+      const uint64_t ballot = ballots[r];
+      const uint32_t p = px0 + r * VM_THREADS + threadIdx.x;
+      const bool rep = (ballot >> lane) & 1ull;
+      f32x3 pt = {0.f, 0.f, 0.f};
+      unsigned long long key = VX_EMPTY;
+      if (p < p_end) {
+        pt = *(const f32x3_u*)(points + 3 * (size_t)p);
+        if (!voxel_key(pt, grid, &key, nullptr)) key = VX_EMPTY;
+      }
+      bool first;
+      const uint64_t heads = run_heads(key, lane, &first);
+      const uint32_t first_lane = run_first_lane(heads, lane), end_lane = run_end_lane(heads, lane);
+      // the lanes of this run that are not the representative, and how many of them are below this lane
+      const uint64_t run_mask = (end_lane == 64u ? ~0ull : (1ull << end_lane) - 1ull) & (~0ull << first_lane);
+      const uint64_t others = run_mask & ~ballot;
+      const uint32_t n_others = (uint32_t)__builtin_popcountll(others);
+      const uint32_t below = (uint32_t)__builtin_popcountll(others & ((1ull << lane) - 1ull));
+      uint32_t start = 0, old = 0;
+      if (first && key != VX_EMPTY) {
+        const unsigned long long s = find_slot(table, mask, key + 1);
+        if (s == ~0ull) {  // (cannot happen: pass 1 placed every kept point)
+          atomicMax(fault, 2ull);
+          start = ~0u;
+        } else {
+          start = (uint32_t)(table[s].best >> 32);  // (nothing writes the high half in this pass)
+          if (n_others) old = atomicSub(slot_half(&table[s], 0), n_others);
+        }
+      }
+      start = __shfl(start, (int)first_lane, 64), old = __shfl(old, (int)first_lane, 64);
+      if (key != VX_EMPTY && start != ~0u) {
+        // the representative at the run's start; the others at start + count - 1 ... start + 1, in any order
+        const unsigned long long pos = rep ? (unsigned long long)start : (unsigned long long)start + old - 1u - below;
+        if (pos >= len || (!rep && old < n_others + 1u)) {  // (cannot happen: the runs partition the kept points; a bound on every store)
+          atomicMax(fault, 3ull);
+        } else {
+          const f32x4 rec = {pt.x, pt.y, pt.z, __uint_as_float(p)};
+          *(f32x4*)(sorted + pos) = rec;
+          if (rep) row_at[pos] = offs[r] + lane_rank(ballot);
+        }
+      }
+    }
+  }
+}
+
+// The sums of a cell, or of the part of one that a wave holds.
+struct VmSums {
+  uint32_t n;
+  long long s[3];
+  int t[3];  // (a wave's 64 rows of |r| <= 2^21 fit; the spill accumulators are 64-bit)
+  uint32_t c[3];
+};
+
+// Steps 3 to 6 for one cell: `rec` is its representative, the sums are the whole cell's.
+__device__ __forceinline__ void vmean_finish(const MeanJob& j, VoxelGrid grid, float u, unsigned long long row, f32x4 rec,
+                                             unsigned long long n, const long long* s, const long long* t,
+                                             const unsigned long long* c) {
+  if (row >= j.capacity) return;  // (cannot happen: the rows are fewer than lens <= capacity; a bound on every store)
+  const uint32_t index = __float_as_uint(rec.w);
+  f32x3 out = {rec.x, rec.y, rec.z};
+  if (n == 1) {
+    *(f32x3_u*)(j.out_points + 3 * row) = out;
+    if (j.out_normals) *(f32x3_u*)(j.out_normals + 3 * row) = *(const f32x3_u*)(j.normals + 3 * (size_t)index);
+    if (j.out_colors) store_color(j.out_colors, row, load_color(j.colors, index));
+  } else {
+    const double dn = (double)n;
+    const float cx = floorf((rec.x - grid.ox) / grid.v), cy = floorf((rec.y - grid.oy) / grid.v),
+                cz = floorf((rec.z - grid.oz) / grid.v);
+    const float mx = (float)((double)s[0] / dn), my = (float)((double)s[1] / dn), mz = (float)((double)s[2] / dn);
+    out.x = ((cx + 0.5f) * grid.v + grid.ox) + mx * u;
+    out.y = ((cy + 0.5f) * grid.v + grid.oy) + my * u;
+    out.z = ((cz + 0.5f) * grid.v + grid.oz) + mz * u;
+    *(f32x3_u*)(j.out_points + 3 * row) = out;
+    if (j.out_normals) {
+      const double tx = (double)t[0], ty = (double)t[1], tz = (double)t[2];
+      const double l = sqrt((tx * tx + ty * ty) + tz * tz);
+      f32x3 nrm = {0.f, 0.f, 0.f};
+      if (l > 0.0) nrm.x = (float)(tx / l), nrm.y = (float)(ty / l), nrm.z = (float)(tz / l);
+      *(f32x3_u*)(j.out_normals + 3 * row) = nrm;
+    }
+    if (j.out_colors) {
+      const uint32_t r = (uint32_t)((2 * c[0] + n) / (2 * n)), g = (uint32_t)((2 * c[1] + n) / (2 * n)),
+                     b = (uint32_t)((2 * c[2] + n) / (2 * n));
+      store_color(j.out_colors, row, r | g << 8 | b << 16);
+    }
+  }
+  if (j.out_index) j.out_index[row] = index;
+  if (j.out_counts) j.out_counts[row] = (uint32_t)n;
+}
+
+// Whether any cloud of the batch has more rows than its capacity (then nothing is written anywhere); wave 0 decides.
+__device__ __forceinline__ bool vmean_any_over(const MeanJob* __restrict__ jobs, uint32_t n_jobs,
+                                               const unsigned long long* __restrict__ lens, uint32_t* s_over) {
+  if (threadIdx.x < 64u) {
+    bool over = false;
+    for (uint32_t k = threadIdx.x; k < n_jobs; k += 64) over |= lens[k] > jobs[k].capacity;
+    const bool any_over = __builtin_amdgcn_ballot_w64(over) != 0ull;
+    if (threadIdx.x == 0) *s_over = any_over ? 1u : 0u;
+  }
+  __syncthreads();
+  return *s_over != 0u;
+}
+
+// Pass 5.
+__global__ void __launch_bounds__(VM_THREADS)
+    vmean_reduce_kernel(const MeanJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, MeanParams prm,
+                        const unsigned long long* __restrict__ cursor, const unsigned long long* __restrict__ lens) {
+  __shared__ uint32_t s_over;
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  if (vmean_any_over(jobs, n_jobs, lens, &s_over)) return;
+  const MeanJob& j = jobs[ji];
+  const VmRecord* __restrict__ sorted = j.sorted;
+  const float* __restrict__ normals = j.out_normals ? j.normals : nullptr;
+  const uint8_t* __restrict__ colors = j.out_colors ? j.colors : nullptr;
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
+  const uint32_t kept = (uint32_t)min(cursor[ji], (unsigned long long)len);
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(kept, p0 + span);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += VM_THREADS) {  // wave-uniform; base is a multiple of 64
+    const uint32_t pos = base + lane;
+    const bool live = pos < p_end;
+    f32x4 rec = {0.f, 0.f, 0.f, 0.f};
+    unsigned long long key = VX_EMPTY;
+    VmSums a{};
+    if (live) {
+      rec = *(const f32x4*)(sorted + pos);
+      const f32x3 pt = {rec.x, rec.y, rec.z};
+      if (!voxel_key(pt, grid, &key, nullptr)) key = VX_EMPTY;  // (a record is a kept point: never refused)
+      const float cx = floorf((pt.x - grid.ox) / grid.v), cy = floorf((pt.y - grid.oy) / grid.v),
+                  cz = floorf((pt.z - grid.oz) / grid.v);
+      const float dx = pt.x - ((cx + 0.5f) * grid.v + grid.ox), dy = pt.y - ((cy + 0.5f) * grid.v + grid.oy),
+                  dz = pt.z - ((cz + 0.5f) * grid.v + grid.oz);
+      a.n = 1;
+      a.s[0] = (int)rintf(dx * prm.s), a.s[1] = (int)rintf(dy * prm.s), a.s[2] = (int)rintf(dz * prm.s);
+      const uint32_t index = __float_as_uint(rec.w);
+      if (normals) {
+        const f32x3 nr = *(const f32x3_u*)(normals + 3 * (size_t)index);
+        // (a NaN fails every comparison)
+        if (fabsf(nr.x) <= 2.f && fabsf(nr.y) <= 2.f && fabsf(nr.z) <= 2.f)
+          a.t[0] = (int)rintf(nr.x * 1048576.0f), a.t[1] = (int)rintf(nr.y * 1048576.0f), a.t[2] = (int)rintf(nr.z * 1048576.0f);
+      }
+      if (colors) {
+        const uint32_t rgb = load_color(colors, index);
+        a.c[0] = rgb & 255u, a.c[1] = (rgb >> 8) & 255u, a.c[2] = (rgb >> 16) & 255u;
+      }
+    }
+    // whether the cell of lane 0 starts before this wave, and whether the cell of lane 63 goes on after it
+    bool open_left = false, open_right = false;
+    if (lane == 0 && pos > 0) {
+      const f32x4 before = *(const f32x4*)(sorted + (pos - 1));
+      const f32x3 pb = {before.x, before.y, before.z};
+      unsigned long long kb = VX_EMPTY;
+      voxel_key(pb, grid, &kb, nullptr);
+      open_left = kb == key;
+    }
+    if (lane == 63 && live && pos + 1u < kept) {
+      const f32x4 after = *(const f32x4*)(sorted + (pos + 1));
+      const f32x3 pa = {after.x, after.y, after.z};
+      unsigned long long ka = VX_EMPTY;
+      voxel_key(pa, grid, &ka, nullptr);
+      open_right = ka == key;
+    }
+    open_left = __builtin_amdgcn_ballot_w64(open_left) != 0ull;
+    bool first;
+    const uint64_t heads = run_heads(key, lane, &first);
+    const uint32_t first_lane = run_first_lane(heads, lane), end_lane = run_end_lane(heads, lane);
+    // inclusive scan inside every run: its last lane ends with the run's sums
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t un = __shfl_up(a.n, o, 64);
+      const long long us0 = __shfl_up(a.s[0], o, 64), us1 = __shfl_up(a.s[1], o, 64), us2 = __shfl_up(a.s[2], o, 64);
+      const int ut0 = __shfl_up(a.t[0], o, 64), ut1 = __shfl_up(a.t[1], o, 64), ut2 = __shfl_up(a.t[2], o, 64);
+      const uint32_t uc0 = __shfl_up(a.c[0], o, 64), uc1 = __shfl_up(a.c[1], o, 64), uc2 = __shfl_up(a.c[2], o, 64);
+      if (lane >= first_lane + (uint32_t)o) {
+        a.n += un;
+        a.s[0] += us0, a.s[1] += us1, a.s[2] += us2;
+        a.t[0] += ut0, a.t[1] += ut1, a.t[2] += ut2;
+        a.c[0] += uc0, a.c[1] += uc1, a.c[2] += uc2;
+      }
+    }
+    // the run's first record, for its last lane
+    f32x4 head;
+    head.x = __shfl(rec.x, (int)first_lane, 64), head.y = __shfl(rec.y, (int)first_lane, 64);
+    head.z = __shfl(rec.z, (int)first_lane, 64), head.w = __shfl(rec.w, (int)first_lane, 64);
+    if (live && end_lane == lane + 1u) {  // the run's last lane (no lane leaves the trip early: the next one shuffles again)
+      const long long s64[3] = {a.s[0], a.s[1], a.s[2]}, t64[3] = {a.t[0], a.t[1], a.t[2]};
+      const unsigned long long c64[3] = {a.c[0], a.c[1], a.c[2]};
+      const bool from_before = first_lane == 0 && open_left;
+      if (!from_before && !open_right) {  // (open_right is lane 63's alone)
+        vmean_finish(j, grid, prm.u, j.row_at[base + first_lane], head, a.n, s64, t64, c64);
+      } else {
+        const unsigned long long slot = find_slot(j.table, j.slot_mask, key + 1);
+        // (a missing slot or a start past the end cannot happen; a bound on the accumulator's index)
+        const uint32_t start = slot == ~0ull ? len : (uint32_t)(j.table[slot].best >> 32);
+        if (start < len) {
+          VmSpill* acc = j.spill + (start >> 6);
+          atomicAdd(&acc->n, (unsigned long long)a.n);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            if (s64[k]) atomicAdd((unsigned long long*)&acc->s[k], (unsigned long long)s64[k]);
+            if (t64[k]) atomicAdd((unsigned long long*)&acc->t[k], (unsigned long long)t64[k]);
+            if (c64[k]) atomicAdd(&acc->c[k], c64[k]);
+          }
+          if (!from_before) acc->head = (unsigned long long)start + 1ull;  // the part that holds the cell's first record
+        }
+      }
+    }
+  }
+}
+
+// Pass 6: a thread per accumulator.
+__global__ void __launch_bounds__(VM_THREADS)
+    vmean_spill_kernel(const MeanJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, MeanParams prm,
+                       const unsigned long long* __restrict__ lens) {
+  __shared__ uint32_t s_over;
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  if (vmean_any_over(jobs, n_jobs, lens, &s_over)) return;
+  const MeanJob& j = jobs[ji];
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK, n_groups = (len + 63u) >> 6;
+  const uint32_t g0 = (tile - j.first_tile) * (span >> 6), g_end = min(n_groups, g0 + (span >> 6));
+  for (uint32_t g = g0 + threadIdx.x; g < g_end; g += VM_THREADS) {
+    const VmSpill acc = j.spill[g];
+    if (acc.head == 0 || acc.head > len) continue;
+    const unsigned long long pos = acc.head - 1;
+    vmean_finish(j, grid, prm.u, j.row_at[pos], *(const f32x4*)(j.sorted + pos), acc.n, acc.s, acc.t, acc.c);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                              const uint8_t* const* d_colors, uint64_t n, float voxel_size,
+                                              const float origin[3], float* const* d_out_points,
+                                              float* const* d_out_normals, uint8_t* const* d_out_colors,
+                                              uint32_t* const* d_out_index, uint32_t* const* d_out_counts,
+                                              const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped) {
+  if (n == 0) return A3D_OK;
+  A3D_REQUIRE(ctx && d_clouds && d_out_points && capacities && out_lens, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.f, A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_voxel_mean_device: the voxel size must be finite and positive");
+  VoxelGrid grid{voxel_size, 0.f, 0.f, 0.f};
+  if (origin) {
+    A3D_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), A3D_INVALID_PARAMETER,
+                "a3d_point_clouds_voxel_mean_device: the origin must be finite");
+    grid.ox = origin[0], grid.oy = origin[1], grid.oz = origin[2];
+  }
+  const MeanParams prm{32768.0f / voxel_size, voxel_size / 32768.0f};
+  std::vector<MeanJob> jobs;
+  std::vector<uint64_t> cloud_of_job;
+  std::vector<ByteRange> ranges;
+  jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(8 * n);
+  uint64_t tiles = 0;
+  // offsets of a job's arrays inside their parts of the scratch region, for now
+  size_t flag_bytes = 0, row_bytes = 0, sorted_bytes = 0, table_bytes = 0, spill_bytes = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const a3d_point_cloud_view& c = d_clouds[i];
+    A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
+    if (c.len == 0) continue;  // yields no points; its pointers may be null
+    A3D_REQUIRE(c.points && d_out_points[i], A3D_INVALID_PARAMETER, "null points or output pointer");
+    float* out_normals = d_out_normals ? d_out_normals[i] : nullptr;
+    A3D_REQUIRE(!out_normals || c.normals, A3D_MISSING_FIELD, "cloud has no normals");
+    uint8_t* out_colors = d_out_colors ? d_out_colors[i] : nullptr;
+    const uint8_t* colors = out_colors && d_colors ? d_colors[i] : nullptr;
+    A3D_REQUIRE(!out_colors || colors, A3D_MISSING_FIELD, "cloud has no colours");
+    MeanJob j{};
+    j.points = c.points, j.normals = out_normals ? c.normals : nullptr, j.colors = colors;
+    j.out_points = d_out_points[i], j.out_normals = out_normals, j.out_colors = out_colors;
+    j.out_index = d_out_index ? d_out_index[i] : nullptr;
+    j.out_counts = d_out_counts ? d_out_counts[i] : nullptr;
+    j.capacity = capacities[i];
+    j.len = (uint32_t)c.len;
+    A3D_TRY(plan_tiles(c.len, VM_CHUNK, VM_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
+    j.n_tiles = (uint32_t)tiles - j.first_tile;
+    // the kernels' 32-bit point positions run up to one tile span past len
+    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * VM_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
+                "a3d_point_clouds_voxel_mean_device: a cloud within one tile of 2^32 points");
+    uint64_t slots = 2;
+    while (slots < 2 * c.len) slots <<= 1;
+    j.slot_mask = slots - 1;
+    const size_t groups = (c.len + 63) / 64;
+    j.flags = (unsigned long long*)flag_bytes, j.row_at = (uint32_t*)row_bytes, j.sorted = (VmRecord*)sorted_bytes;
+    j.table = (VoxelSlot*)table_bytes, j.spill = (VmSpill*)spill_bytes;
+    flag_bytes += pad256(groups * 8), row_bytes += pad256(c.len * 4), sorted_bytes += pad256(c.len * sizeof(VmRecord));
+    table_bytes += slots * sizeof(VoxelSlot), spill_bytes += pad256(groups * sizeof(VmSpill));
+    jobs.push_back(j), cloud_of_job.push_back(i);
+    // what the call may write is the first min(len, capacity) elements of each output
+    const uintptr_t in_bytes = (uintptr_t)c.len * 12, kept = (uintptr_t)std::min<uint64_t>(c.len, j.capacity);
+    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + in_bytes, false});
+    if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + in_bytes, false});
+    if (j.colors) ranges.push_back({(uintptr_t)j.colors, (uintptr_t)j.colors + (uintptr_t)c.len * 3, false});
+    if (kept) {
+      ranges.push_back({(uintptr_t)j.out_points, (uintptr_t)j.out_points + kept * 12, true});
+      if (out_normals) ranges.push_back({(uintptr_t)out_normals, (uintptr_t)out_normals + kept * 12, true});
+      if (j.out_index) ranges.push_back({(uintptr_t)j.out_index, (uintptr_t)j.out_index + kept * 4, true});
+      if (j.out_counts) ranges.push_back({(uintptr_t)j.out_counts, (uintptr_t)j.out_counts + kept * 4, true});
+      if (out_colors) ranges.push_back({(uintptr_t)out_colors, (uintptr_t)out_colors + kept * 3, true});
+    }
+  }
+  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_voxel_mean_device: an output overlaps an input or another output (there is no in-place "
+              "form)");
+  for (uint64_t i = 0; i < n; ++i) out_lens[i] = 0;
+  if (out_dropped)
+    for (uint64_t i = 0; i < n; ++i) out_dropped[i] = 0;
+  if (jobs.empty()) return A3D_OK;
+  const size_t n_jobs = jobs.size();
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  // the words: lens, dropped, cursor, fault; the tail: ballot words | row numbers | records | hash tables | accumulators
+  BatchScratch scratch;
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(MeanJob), 3 * n_jobs + 1, tiles,
+                        flag_bytes + row_bytes + sorted_bytes + table_bytes + spill_bytes, &scratch));
+  char* d_flags = scratch.tail;
+  char* d_rows = d_flags + flag_bytes;
+  char* d_sorted = d_rows + row_bytes;
+  char* d_tables = d_sorted + sorted_bytes;
+  char* d_spill = d_tables + table_bytes;
+  for (MeanJob& j : jobs) {
+    j.flags = (unsigned long long*)(d_flags + (size_t)j.flags);
+    j.row_at = (uint32_t*)(d_rows + (size_t)j.row_at);
+    j.sorted = (VmRecord*)(d_sorted + (size_t)j.sorted);
+    j.table = (VoxelSlot*)(d_tables + (size_t)j.table);
+    j.spill = (VmSpill*)(d_spill + (size_t)j.spill);
+  }
+  const MeanJob* d_jobs = (const MeanJob*)scratch.jobs;
+  unsigned long long* d_lens = scratch.words;
+  unsigned long long* d_dropped = d_lens + n_jobs;
+  unsigned long long* d_cursor = d_lens + 2 * n_jobs;
+  unsigned long long* d_fault = d_lens + 3 * n_jobs;
+  uint32_t* d_tile_counts = scratch.tile_counts;
+  hipStream_t s = ctx->stream;
+  A3D_TRY(batch_upload(scratch, jobs.data(), s));
+  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, table_bytes + spill_bytes, s));  // every slot empty, every accumulator zero
+  const dim3 grid_dim((uint32_t)tiles), block(VM_THREADS);
+  hipLaunchKernelGGL(vmean_count_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, d_dropped, d_fault);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(vmean_flag_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, d_tile_counts, d_lens);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(vmean_place_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, d_cursor);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(vmean_scatter_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid,
+                     (const uint32_t*)d_tile_counts, d_fault);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(vmean_reduce_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, prm,
+                     (const unsigned long long*)d_cursor, (const unsigned long long*)d_lens);
+  A3D_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(vmean_spill_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, prm,
+                     (const unsigned long long*)d_lens);
+  A3D_HIP_TRY(hipGetLastError());
+  std::vector<unsigned long long> words(3 * n_jobs + 1);
+  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_lens, words.size() * 8, hipMemcpyDeviceToHost, s));
+  // host-synchronous: the caller may free inputs and outputs right after
+  A3D_HIP_TRY(hipStreamSynchronize(s));
+  A3D_REQUIRE(words[3 * n_jobs] == 0, A3D_HIP_ERROR, "a3d_point_clouds_voxel_mean_device: a hash table filled up");
+  bool over = false;
+  for (size_t k = 0; k < n_jobs; ++k) {
+    out_lens[cloud_of_job[k]] = words[k];
+    if (out_dropped) out_dropped[cloud_of_job[k]] = words[n_jobs + k];
+    over |= words[k] > jobs[k].capacity;
+  }
+  A3D_REQUIRE(!over, A3D_INVALID_PARAMETER,
+              "a3d_point_clouds_voxel_mean_device: a capacity is smaller than its cloud's rows (nothing was written)");
+  return A3D_OK;
+}
+
+}  // extern "C"

@@ -530,9 +530,17 @@ class DevicePointCloud:
         return out
 
     @staticmethod
-    def _voxel_downsample(clouds, voxel_size, origin, return_index):
-        """([downsampled clouds], [uint32 host index arrays] or None): one a3d_point_clouds_voxel_downsample_device call."""
+    def _voxel_downsample(clouds, voxel_size, origin, return_index, mode="nearest", return_counts=False):
+        """([downsampled clouds], [uint32 host index arrays] or None): one a3d_point_clouds_voxel_downsample_device call;
+        with mode="mean" ([clouds], [index arrays] or None, [uint32 host count arrays] or None): one
+        a3d_point_clouds_voxel_mean_device call."""
+        if mode not in ("nearest", "mean"):
+            raise _abi.InvalidParameter(f"voxel_downsample: mode is 'nearest' or 'mean', not {mode!r}")
+        if return_counts and mode != "mean":
+            raise _abi.InvalidParameter("voxel_downsample: return_counts needs mode='mean' (a nearest-point cell has one row)")
         clouds = list(clouds)
+        if mode == "mean":
+            return DevicePointCloud._voxel_mean(clouds, voxel_size, origin, return_index, return_counts)
         if not clouds:
             return [], ([] if return_index else None)
         clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "voxel_downsample")
@@ -584,22 +592,85 @@ class DevicePointCloud:
         return outs, index
 
     @staticmethod
-    def voxel_downsample_many(clouds, voxel_size, origin=None):
-        """[c.voxel_downsample(voxel_size, origin) for c in clouds] as new resident clouds of one context, in ONE call
-        whose launch count does not depend on the number of clouds (a3d_point_clouds_voxel_downsample_device).  Each
-        result keeps the buffers sized for its input (len() is the kept count) and has normals iff its input has them,
-        and colours iff its input has them."""
-        return DevicePointCloud._voxel_downsample(clouds, voxel_size, origin, False)[0]
+    def _origin3(origin):
+        if origin is None:
+            return None
+        o = np.ascontiguousarray(origin, np.float32).reshape(-1)
+        if o.size != 3:
+            raise _abi.InvalidParameter("voxel_downsample: the origin has three coordinates")
+        return (C.c_float * 3)(*o.tolist())
 
-    def voxel_downsample(self, voxel_size, origin=None, return_index=False):
+    @staticmethod
+    def _voxel_mean(clouds, voxel_size, origin, return_index, return_counts):
+        """The mode="mean" half of _voxel_downsample: one a3d_point_clouds_voxel_mean_device call."""
+        if not clouds:
+            return [], ([] if return_index else None), ([] if return_counts else None)
+        clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "voxel_downsample")
+        o = DevicePointCloud._origin3(origin)
+        n, outs, d_index, d_counts = len(clouds), [], [], []
+        try:
+            for c in clouds:
+                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
+                if return_index:
+                    d_index.append(ctx.malloc(max(1, c.n) * 4))
+                if return_counts:
+                    d_counts.append(ctx.malloc(max(1, c.n) * 4))
+            lens = (C.c_uint64 * n)()
+            colours = any(c.d_colors is not None for c in clouds)
+            _abi.check(
+                ctx.lib.a3d_point_clouds_voxel_mean_device(
+                    ctx.handle, DevicePointCloud._views(clouds), DevicePointCloud._colors_array(clouds) if colours else None,
+                    n, float(voxel_size), o, (C.c_void_p * n)(*[x.d_points for x in outs]),
+                    (C.c_void_p * n)(*[x.d_normals for x in outs]), DevicePointCloud._colors_array(outs) if colours else None,
+                    (C.c_void_p * n)(*d_index) if return_index else None,
+                    (C.c_void_p * n)(*d_counts) if return_counts else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens,
+                    None),
+                "a3d_point_clouds_voxel_mean_device",
+            )
+            for x, k in zip(outs, lens):
+                x.n = int(k)
+
+            def download(buffers):
+                return [ctx.to_host(d, np.empty(x.n, np.uint32)) if x.n else np.empty(0, np.uint32)
+                        for d, x in zip(buffers, outs)]
+
+            index = download(d_index) if return_index else None
+            counts = download(d_counts) if return_counts else None
+        except BaseException:
+            for x in outs:
+                x.free()
+            raise
+        finally:
+            for d in d_index + d_counts:
+                ctx.free(d)
+        return outs, index, counts
+
+    @staticmethod
+    def voxel_downsample_many(clouds, voxel_size, origin=None, mode="nearest"):
+        """[c.voxel_downsample(voxel_size, origin, mode=mode) for c in clouds] as new resident clouds of one context, in
+        ONE call whose launch count does not depend on the number of clouds (a3d_point_clouds_voxel_downsample_device;
+        mode="mean": a3d_point_clouds_voxel_mean_device).  Each result keeps the buffers sized for its input (len() is
+        the kept count) and has normals iff its input has them, and colours iff its input has them."""
+        return DevicePointCloud._voxel_downsample(clouds, voxel_size, origin, False, mode)[0]
+
+    def voxel_downsample(self, voxel_size, origin=None, return_index=False, mode="nearest", return_counts=False):
         """One point per occupied cell of the grid of pitch `voxel_size` anchored at `origin` (default (0, 0, 0)), as a
         new resident cloud: the input point nearest to the cell's centre (ties: the lowest index), never an average, so
         the result is a subsequence of this cloud, points, normals and colours bit for bit, and does not depend on the order of
         the points.  Points whose cell is not finite or outside [-2^20, 2^20) per axis (NaN, infinities, far outliers)
         are dropped.  return_index=True returns (cloud, index): `index` is a HOST uint32 array, index[k] = the position
-        in this cloud of the result's point k (one 4-byte-per-kept-point download; nothing else leaves the device)."""
-        outs, index = DevicePointCloud._voxel_downsample([self], voxel_size, origin, return_index)
-        return (outs[0], index[0]) if return_index else outs[0]
+        in this cloud of the result's point k (one 4-byte-per-kept-point download; nothing else leaves the device).
+
+        mode="mean" gives what PCL's VoxelGrid and Open3D's voxel_down_sample give instead: per occupied cell the centroid
+        of its points, the mean of their normals (renormalised; zero if they cancel) and the mean of their colours
+        (rounded half up), by the integer rule of a3d_point_clouds_voxel_mean_device (include/align3d_hip.h): the same
+        cells, the same count of dropped points, rows in first-occurrence order, a cell of one point copied bit for bit,
+        and the same bits under any permutation of this cloud's rows.  `index` is then each cell's lowest input index,
+        and return_counts=True appends a HOST uint32 array of the cells' point counts: (cloud, counts) or (cloud, index,
+        counts).  Any other mode, or return_counts with mode="nearest", raises InvalidParameter."""
+        res = DevicePointCloud._voxel_downsample([self], voxel_size, origin, return_index, mode, return_counts)
+        extras = [x[0] for x in res[1:] if x is not None]
+        return (res[0][0], *extras) if extras else res[0][0]
 
     @staticmethod
     def estimate_normals_many(clouds, radius, viewpoints=None, min_neighbors=3, orient="viewpoint", curvature=False,

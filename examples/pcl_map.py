@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
-        [--voxel V [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
+        [--voxel V [--mean | --online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
         [--estimate-normals R] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
 back in one resident cloud (one launch).  With --voxel V the map is then thinned to one point per V-sized cell
 (DevicePointCloud.voxel_downsample: still on the device) and the last frame is aligned against the thinned map with Icp,
-frame to map.  With --online the thinned map is built the way a live caller would, frame by frame into a persistent
+frame to map.  With --mean (the offline route only: merge -> voxel_downsample(mode="mean")) a second map is made from the
+same merged cloud, the centroid of each cell with its mean normal and mean colour instead of one picked sample, and the
+figures printed for the nearest-point map are printed for it as well, side by side.  With --online the thinned map is built the way a live caller would, frame by frame into a persistent
 DeviceVoxelMap (insert per frame, one extract at the end) instead of merge + voxel_downsample of everything: no merged
 cloud exists at any time, and the lines it prints are the same; the last frame is then corrected against the live map
 itself (DeviceVoxelMap.align from its odometry pose: no extract, no kd-tree build, the frame in its own coordinates), and
@@ -48,6 +50,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("dataset", nargs="?", default=os.path.join(ROOT, "tests", "golden", "rgbd", "sample1"))
 ap.add_argument("--max-frames", type=int, default=None)
 ap.add_argument("--voxel", type=float, default=None, help="thin the map to one point per cell of this size (metres)")
+ap.add_argument("--mean", action="store_true",
+                help="with --voxel, not --online: also thin the merged cloud to each cell's mean and print both maps' figures")
 ap.add_argument("--online", action="store_true", help="with --voxel: build the thinned map by inserting frame by frame")
 ap.add_argument("--check-batch", action="store_true",
                 help="with --online: also run merge + voxel_downsample and assert that the online map is the same bits")
@@ -65,6 +69,8 @@ ap.add_argument("--out", default=None, help="write the map's points to this .npy
 args = ap.parse_args()
 if args.online and not args.voxel:
     ap.error("--online needs --voxel")
+if args.mean and (not args.voxel or args.online):
+    ap.error("--mean needs --voxel and the offline route (the persistent map keeps its nearest-to-centre rule)")
 if args.check_batch and not args.online:
     ap.error("--check-batch needs --online")
 windowed = args.window_box is not None or args.window_frames is not None
@@ -107,10 +113,16 @@ for k, (now_to_previous, st) in enumerate(zip(poses, status)):
     camera_to_world.append(traj.current_camera_to_world())
 
 
+mean_map = None  # --mean: the map of cell means, beside the nearest-point map
+
+
 def thinned_by_batch():
     """(points offered, thinned map): all frames in one coordinate system, then one point per cell."""
+    global mean_map
     full = DevicePointCloud.merge(clouds, camera_to_world)
     thin = full.voxel_downsample(args.voxel)
+    if args.mean:
+        mean_map = full.voxel_downsample(args.voxel, mode="mean")
     offered = full.len()
     full.free()
     return offered, thin
@@ -195,6 +207,14 @@ if args.voxel:
         icp.free(), last.free()
     print(f"last frame against the thinned map: correction angle {correction.angle():.3e} rad, "
           f"translation {float(np.linalg.norm(correction.t)):.3e}")
+    if mean_map is not None:  # the same figures for the map of cell means
+        last = camera_to_world[-1] * clouds[-1]
+        icp = Icp(ctx, IcpParams.default(), mean_map)
+        mean_correction = icp.align(last)
+        icp.free(), last.free()
+        print(f"voxel {args.voxel} (cell means): {offered} points -> {mean_map.len()}")
+        print(f"last frame against the map of cell means: correction angle {mean_correction.angle():.3e} rad, "
+              f"translation {float(np.linalg.norm(mean_correction.t)):.3e}")
 points, _ = world_map.download()
 finite = points[np.isfinite(points).all(axis=1)]
 print(f"{len(clouds)} frames, map of {world_map.len()} points" + (" with normals" if world_map.d_normals is not None else "")
@@ -209,6 +229,6 @@ if args.out:
         np.save(colors_out, world_map.download_colors())
         print("wrote", colors_out)
 batch.free()
-for x in [world_map] + clouds + images + coarser:
+for x in [world_map] + ([mean_map] if mean_map is not None else []) + clouds + images + coarser:
     x.free()
 ctx.close()

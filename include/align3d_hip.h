@@ -584,6 +584,48 @@ a3d_status a3d_point_clouds_voxel_downsample_rgb_device(a3d_context* ctx, const 
                                                         uint32_t* const* d_out_index, const uint64_t* capacities,
                                                         uint64_t* out_lens, uint64_t* out_dropped);
 
+/* Voxel-grid downsampling by cell MEAN: the sibling of the two entries above for users who expect what PCL's VoxelGrid
+ * and Open3D's voxel_down_sample return, the centroid of each cell with the mean normal and the mean colour.  n resident
+ * clouds, each exactly as if it were passed alone, in a number of launches that does not depend on n; host-synchronous.
+ * The offsets are rounded to a lattice and summed in integers, so the result is the same bits under any permutation of a
+ * cloud's rows (as a multiset of rows) and the same bits as tests/voxel_mean_restatement.py.  The rule.  All f32
+ * operations are rounded on their own (correctly rounded / and sqrt), f64 operations likewise.  Per call: v = voxel_size
+ * finite and > 0, a finite origin o (NULL = (0,0,0)); host constants in f32: s = 32768.0f / v and u = v / 32768.0f.
+ *   1. Cell.  c_k and the cell key of a3d_point_clouds_voxel_downsample_device, unchanged.  A point it refuses is dropped
+ *      and counted.
+ *   2. Offsets.  ctr_k = (c_k + 0.5f) * v + o_k and d_k = p_k - ctr_k, as that entry computes them.
+ *      q_k = (int) rintf(d_k * s), ties to even.  Per cell, in int64: N = sum 1 and S_k = sum q_k.  |q_k| stays near 2^14;
+ *      with len < 2^32 nothing can overflow.
+ *   3. Mean point.  If N == 1 the cell's only row is copied bit for bit: point, normal and colour.  Otherwise
+ *      m_k = (float)((double)S_k / (double)N) and out_k = ctr_k + m_k * u, with ctr taken from the cell's representative
+ *      (step 6).
+ *   4. Mean normal (only when normals are written, N > 1).  A row's normal is counted iff its three components are finite
+ *      and |n_k| <= 2.  r_k = (int) rintf(n_k * 1048576.0f), and T_k = sum r_k in int64 over the counted rows; each sum
+ *      stays <= 2^53, so it is exact in f64.  L = sqrt((T_x*T_x + T_y*T_y) + T_z*T_z) in f64.
+ *      out_n_k = L > 0 ? (float)((double)T_k / L) : 0.  A zero normal stays in the cloud: every aligner's angle gate
+ *      rejects it, as after a3d_point_clouds_estimate_normals_device.
+ *   5. Mean colour (only when colours are written, N > 1).  Per channel C = sum c in u64, and out_c = (2 C + N) / (2 N)
+ *      in integer division, which rounds half up.
+ *   6. Order, index, count.  A cell's representative is its lowest input index.  Output rows are in ascending order of
+ *      representative, which is first-occurrence order.  d_out_index[i][row] is that index, strictly increasing;
+ *      d_out_counts[i][row] = N as u32.
+ * So out_lens, out_dropped and the set of cells are those of a3d_point_clouds_voxel_downsample_device with the same v and
+ * o, a cloud whose cells are all singletons comes back bit for bit in input order, and each output coordinate differs
+ * from the exact mean of its cell by at most v * 2^-15 + 2 ulp32(M), M the largest absolute input or origin coordinate.
+ * The outputs, their NULL forms, capacities, A3D_MISSING_FIELD for a normals or colour output of a cloud that lacks the
+ * field, and every check made on the host before anything is launched are those of
+ * a3d_point_clouds_voxel_downsample_rgb_device; d_out_counts (NULL, or NULL entries: not written; capacities[i] u32) is
+ * one more output of the overlap check.  If any cloud's rows do not fit its capacity the call returns
+ * A3D_INVALID_PARAMETER with every count in out_lens (and out_dropped) and NOTHING written to any output.
+ * Scratch memory (context-owned, grow-only, shared with the calls above): what the nearest-point entry takes, plus 20
+ * bytes per point (a 16-byte record of the counting sort by cell and a 4-byte row number) and 96 bytes per 64 points. */
+a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                              const uint8_t* const* d_colors, uint64_t n, float voxel_size,
+                                              const float origin[3], float* const* d_out_points,
+                                              float* const* d_out_normals, uint8_t* const* d_out_colors,
+                                              uint32_t* const* d_out_index, uint32_t* const* d_out_counts,
+                                              const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped);
+
 /* Normals of n resident clouds from their own neighbourhoods, each exactly as if it were passed alone, in a number of
  * launches that does not depend on n; host-synchronous like the entries above.  For clouds that have no pixel grid to take
  * normals from (a lidar scan, an uploaded cloud, a voxel map's extract).  Per point: the eigenvector of the smallest
