@@ -228,6 +228,8 @@ SIGNATURES = {
         [_P, C.POINTER(PointCloudViewC), _PP, C.POINTER(PoseC), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
     "a3d_voxel_map_extract_rgb": (_ST, [_P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "a3d_voxel_map_new_mean": (_ST, [_P, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_uint64, _PP]),
+    "a3d_voxel_map_extract_mean": (_ST, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "a3d_voxel_map_retain": (
         _ST,
         [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),

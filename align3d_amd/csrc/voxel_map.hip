@@ -43,10 +43,30 @@
 // new table's slot count follows from k, which the host learns only at the call's one wait: the block is sized for
 // every old cell, the rebuild derives slots and the arrays' places from k on the device, and the host derives the same
 // after the wait.  The old table is only read, so a failure of any kind leaves the map as it was.
+//
+// A map of MEANS (a3d_voxel_map_new_mean) keeps the cell-mean rule of voxel_mean.hip as running sums: per slot, in
+// planes of their own behind the colours, a 64-bit count N, the three int64 sums of the lattice offsets, the three int64
+// sums of the rounded normals (maps with normals), the three u64 sums of the colours (maps with colours) and a 32-bit
+// epoch word.  Every term is an integer, so the atomic adds of any grouping of the inserts end in the same sums, and the
+// finish arithmetic (voxel_mean.hpp, shared with the batch call) gives the batch call's bits.  `best` holds the cell's
+// lowest seq with a distance half of zero.  The insert is again two launches over every tile of every cloud:
+//  A. voxel_map_sum_kernel: a wave combines each run of lanes with the same key (segmented scan, vmean_scan_runs); the
+//     run's last lane claims the slot, atomicMins the run's first seq into `best` and adds the run's sums to the slot's
+//     with no-return 64-bit atomics (a term that is zero is not sent).
+//  B. voxel_map_finish_kernel: the first lane of every run finds its slot and atomicMaxes the call's number into the
+//     slot's epoch word; the one thread per cell that raises it reads the final sums and writes the cell's row: its own
+//     raw row if N == 1, else steps 3 to 5 with ctr from the key's cell numbers.  So the row planes hold the rule's
+//     output for every touched cell when the call's work is done, the readers (extract, nearest, align, render, retain)
+//     read them as before, and the cost follows the call's points, never the slot count.
+// Growth and retain move N and the sums with the row (the epoch words of a new table are zero: every call's number is
+// above).  A retain of a map of means is six launches: one more, ahead of the rebuild, zeroes the sum planes of the new
+// table, whose place follows from k.  The nearest-point kernels are the same code as before: the mode is a template
+// parameter of the bodies they share with the mean forms.
 #include <cmath>
 #include <vector>
 
 #include "voxel_map.hpp"
+#include "voxel_mean.hpp"
 
 using namespace a3d;
 
@@ -85,6 +105,34 @@ __device__ __forceinline__ f32x3 world_point(const MapJob& j, uint32_t p) {
   if (!j.has_pose) return pt;  // verbatim, as the merge without poses
   const V3 v = transform_vector(j.pose, V3{pt.x, pt.y, pt.z});
   return f32x3{v.x, v.y, v.z};
+}
+
+__device__ __forceinline__ f32x3 world_normal(const MapJob& j, uint32_t p) {
+  const f32x3 nv = *(const f32x3_u*)(j.normals + 3 * (size_t)p);
+  if (!j.has_pose) return nv;
+  const V3 w = transform_normal(j.pose, V3{nv.x, nv.y, nv.z});
+  return f32x3{w.x, w.y, w.z};
+}
+
+// The planes a map of means keeps beside MapTable's (all null in a nearest-point map).
+struct MeanPlanes {
+  unsigned long long* n;  // [slots] points of the cell
+  long long* s;           // [slots][3] lattice sums
+  long long* t;           // [slots][3] sums of the rounded normals, or null
+  unsigned long long* c;  // [slots][3] colour sums, or null
+  uint32_t* epoch;        // [slots] the number of the last insert call that finished the cell's row
+};
+
+// The slot that holds `key`, or ~0 (the walk stops at the first empty slot).
+__device__ __forceinline__ unsigned long long find_key(const VoxelSlot* __restrict__ table, unsigned long long mask,
+                                                       unsigned long long key) {
+  unsigned long long s = slot_hash(key) & mask;
+  for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
+    const unsigned long long k = table[s].key;
+    if (k == key) return s;
+    if (k == VX_EMPTY) break;
+  }
+  return ~0ull;
 }
 
 // The slot that holds `key`, claimed if no slot does yet (*claimed); false = the table is full (it cannot be).
@@ -193,11 +241,145 @@ __global__ void __launch_bounds__(VM_THREADS)
   }
 }
 
-// Growth: every occupied slot of the old table into the new one (key, best, row); counts the new table's cells.
+// Mean pass A.  COMBINE = false (diagnostics build): every lane is a run of its own, to show what combining buys.
+template <bool COMBINE>
 __global__ void __launch_bounds__(VM_THREADS)
-    voxel_map_rehash_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
-                            const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
-                            unsigned long long old_slots, MapTable m, unsigned long long* __restrict__ fault) {
+    voxel_map_sum_kernel(const MapJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, float lattice, MapTable m,
+                         MeanPlanes mp, unsigned long long* __restrict__ dropped, unsigned long long* __restrict__ fault) {
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MapJob& j = jobs[ji];
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (total + L < 2^32 - span: checked by the host)
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t n_dropped = 0, n_claimed = 0;
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += VM_THREADS) {  // wave-uniform
+    const uint32_t p = base + lane;
+    unsigned long long key = VX_EMPTY;  // no key: a lane past the end or a dropped point
+    VmSums a{};
+    if (p < p_end) {
+      const f32x3 pt = world_point(j, p);
+      if (voxel_key(pt, grid, &key, nullptr)) {
+        a.n = 1;
+        vmean_offsets(pt, grid, lattice, a.s);
+        if (mp.t) vmean_round_normal(world_normal(j, p), a.t);
+        if (mp.c) {
+          const uint32_t rgb = load_color(j.colors, p);
+          a.c[0] = rgb & 255u, a.c[1] = (rgb >> 8) & 255u, a.c[2] = (rgb >> 16) & 255u;
+        }
+      } else {
+        key = VX_EMPTY, ++n_dropped;
+      }
+    }
+    uint32_t first_lane = lane, end_lane = lane + 1u;
+    if (COMBINE) {
+      bool first;
+      const uint64_t heads = run_heads(key, lane, &first);
+      first_lane = run_first_lane(heads, lane), end_lane = run_end_lane(heads, lane);
+      vmean_scan_runs(a, lane, first_lane);
+    }
+    if (key != VX_EMPTY && end_lane == lane + 1u) {  // the run's last lane (no lane leaves the trip early: the next one shuffles again)
+      unsigned long long s;
+      bool claimed = false;
+      if (!claim_slot(m.table, m.mask, key, &s, &claimed)) {
+        atomicMax(fault, 1ull);
+      } else {
+        n_claimed += claimed ? 1u : 0u;
+        const unsigned long long word = j.seq0 + base + first_lane;  // the run's lowest seq; the distance half is zero
+        if (VX_LOAD_AGENT(&m.table[s].best) > word) atomicMin(&m.table[s].best, word);
+        atomicAdd(&mp.n[s], (unsigned long long)a.n);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          if (a.s[k]) atomicAdd((unsigned long long*)&mp.s[3 * s + k], (unsigned long long)a.s[k]);
+          if (mp.t && a.t[k]) atomicAdd((unsigned long long*)&mp.t[3 * s + k], (unsigned long long)(long long)a.t[k]);
+          if (mp.c && a.c[k]) atomicAdd(&mp.c[3 * s + k], (unsigned long long)a.c[k]);
+        }
+      }
+    }
+  }
+  n_dropped = wave_sum(n_dropped), n_claimed = wave_sum(n_claimed);
+  if (lane == 0) {
+    if (n_dropped) atomicAdd(&dropped[ji], (unsigned long long)n_dropped);
+    if (n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
+  }
+}
+
+// Steps 3 to 5 for the cell of slot `s`, whose sums are final; `raw_*`: the only row of a cell with N == 1.
+__device__ __forceinline__ void finish_slot(const MapTable& m, const MeanPlanes& mp, VoxelGrid grid, float u,
+                                            unsigned long long s, unsigned long long key, f32x3 raw_point, f32x3 raw_normal,
+                                            uint32_t raw_color) {
+  const unsigned long long n = mp.n[s];
+  f32x3 point = raw_point, normal = raw_normal;
+  uint32_t color = raw_color;
+  if (n != 1) {
+    const float cx = (float)((int)(key >> 42) - (1 << 20)), cy = (float)((int)((key >> 21) & 0x1FFFFFull) - (1 << 20)),
+                cz = (float)((int)(key & 0x1FFFFFull) - (1 << 20));  // the integers voxel_key's floorf gave
+    const long long sum_s[3] = {mp.s[3 * s], mp.s[3 * s + 1], mp.s[3 * s + 2]};
+    point = vmean_point(cx, cy, cz, grid, u, n, sum_s);
+    if (mp.t) {
+      const long long sum_t[3] = {mp.t[3 * s], mp.t[3 * s + 1], mp.t[3 * s + 2]};
+      normal = vmean_normal(sum_t);
+    }
+    if (mp.c) {
+      const unsigned long long sum_c[3] = {mp.c[3 * s], mp.c[3 * s + 1], mp.c[3 * s + 2]};
+      color = vmean_color(n, sum_c);
+    }
+  }
+  *(f32x3_u*)(m.points + 3 * (size_t)s) = point;
+  if (m.normals) *(f32x3_u*)(m.normals + 3 * (size_t)s) = normal;
+  if (m.colors) m.colors[s] = color;
+}
+
+// Mean pass B: one thread per touched cell, the one that raises the slot's epoch word to the call's number, writes the
+// cell's row from the final sums.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_finish_kernel(const MapJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, float u, MapTable m,
+                            MeanPlanes mp, uint32_t epoch_no) {
+  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
+  const MapJob& j = jobs[ji];
+  const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
+  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += VM_THREADS) {  // wave-uniform
+    const uint32_t p = base + lane;
+    unsigned long long key = VX_EMPTY;
+    f32x3 pt = {0.f, 0.f, 0.f};
+    if (p < p_end) {
+      pt = world_point(j, p);
+      if (!voxel_key(pt, grid, &key, nullptr)) key = VX_EMPTY;
+    }
+    bool first;
+    run_heads(key, lane, &first);
+    if (first && key != VX_EMPTY) {  // (no lane leaves the trip early: the next one shuffles again)
+      const unsigned long long s = find_key(m.table, m.mask, key);
+      // (a missing slot cannot happen: pass A placed every kept point; a bound on every store)
+      if (s <= m.mask && VX_LOAD_AGENT(&mp.epoch[s]) < epoch_no && atomicMax(&mp.epoch[s], epoch_no) < epoch_no) {
+        // (a cell with N == 1 holds this very point: it is the cell's only one)
+        const f32x3 zero = {0.f, 0.f, 0.f};
+        finish_slot(m, mp, grid, u, s, key, pt, m.normals ? world_normal(j, p) : zero,
+                    m.colors ? load_color(j.colors, p) : 0u);
+      }
+    }
+  }
+}
+
+// N and the sums of slot `o` of one table into slot `s` of another (the epoch word stays zero).
+__device__ __forceinline__ void move_sums(const MeanPlanes& mp, unsigned long long s, const MeanPlanes& old_mp,
+                                          unsigned long long o) {
+  mp.n[s] = old_mp.n[o];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    mp.s[3 * s + k] = old_mp.s[3 * o + k];
+    if (mp.t) mp.t[3 * s + k] = old_mp.t[3 * o + k];
+    if (mp.c) mp.c[3 * s + k] = old_mp.c[3 * o + k];
+  }
+}
+
+// The body of both growth passes.  MEAN: N and the sums move with the row.
+template <bool MEAN>
+__device__ __forceinline__ void rehash_slots(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                                             const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                                             unsigned long long old_slots, const MapTable& m, const MeanPlanes& old_mp,
+                                             const MeanPlanes& mp, unsigned long long* __restrict__ fault) {
   uint32_t n_claimed = 0;
   for (unsigned long long o = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; o < old_slots;
        o += (unsigned long long)gridDim.x * VM_THREADS) {
@@ -214,9 +396,27 @@ __global__ void __launch_bounds__(VM_THREADS)
     *(f32x3_u*)(m.points + 3 * (size_t)s) = *(const f32x3_u*)(old_points + 3 * (size_t)o);
     if (m.normals) *(f32x3_u*)(m.normals + 3 * (size_t)s) = *(const f32x3_u*)(old_normals + 3 * (size_t)o);
     if (m.colors) m.colors[s] = old_colors[o];
+    if (MEAN) move_sums(mp, s, old_mp, o);
   }
   n_claimed = wave_sum(n_claimed);
   if ((threadIdx.x & 63u) == 0 && n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
+}
+
+// Growth: every occupied slot of the old table into the new one (key, best, row); counts the new table's cells.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_rehash_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                            const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                            unsigned long long old_slots, MapTable m, unsigned long long* __restrict__ fault) {
+  rehash_slots<false>(old_table, old_points, old_normals, old_colors, old_slots, m, MeanPlanes{}, MeanPlanes{}, fault);
+}
+
+// Growth of a map of means.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_rehash_mean_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                                 const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                                 unsigned long long old_slots, MapTable m, MeanPlanes old_mp, MeanPlanes mp,
+                                 unsigned long long* __restrict__ fault) {
+  rehash_slots<true>(old_table, old_points, old_normals, old_colors, old_slots, m, old_mp, mp, fault);
 }
 
 // The survival rule of a retain: seq >= min_seq and lo <= row <= hi per axis, plain f32 compares on the stored bits (no
@@ -322,14 +522,16 @@ __global__ void __launch_bounds__(VM_THREADS)
   }
 }
 
-// Extract 4: every occupied slot's row to its rank among the set bits: ascending seq.
-__global__ void __launch_bounds__(VM_THREADS)
-    voxel_map_write_kernel(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
-                           const float* __restrict__ normals, const uint32_t* __restrict__ colors,
-                           unsigned long long slots, const unsigned long long* __restrict__ bitmap,
-                           const uint32_t* __restrict__ word_prefix, unsigned long long total, unsigned long long rows,
-                           float* __restrict__ out_points, float* __restrict__ out_normals, uint32_t* __restrict__ out_index,
-                           uint8_t* __restrict__ out_colors) {
+// The body of both write passes.  COUNTS: out_counts[row] = the cell's N as u32, saturating.
+template <bool COUNTS>
+__device__ __forceinline__ void write_rows(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
+                                           const float* __restrict__ normals, const uint32_t* __restrict__ colors,
+                                           unsigned long long slots, const unsigned long long* __restrict__ bitmap,
+                                           const uint32_t* __restrict__ word_prefix, unsigned long long total,
+                                           unsigned long long rows, float* __restrict__ out_points,
+                                           float* __restrict__ out_normals, uint32_t* __restrict__ out_index,
+                                           uint8_t* __restrict__ out_colors, const unsigned long long* __restrict__ sum_n,
+                                           uint32_t* __restrict__ out_counts) {
   for (unsigned long long s = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; s < slots;
        s += (unsigned long long)gridDim.x * VM_THREADS) {
     if (table[s].key == VX_EMPTY) continue;
@@ -343,7 +545,33 @@ __global__ void __launch_bounds__(VM_THREADS)
     if (out_normals) *(f32x3_u*)(out_normals + 3 * dst) = *(const f32x3_u*)(normals + 3 * (size_t)s);
     if (out_index) out_index[dst] = seq;
     if (out_colors) store_color(out_colors, dst, colors[s]);  // (dst < rows: the last byte written is 3 * rows - 1)
+    if (COUNTS) out_counts[dst] = (uint32_t)min(sum_n[s], 0xFFFFFFFFull);
   }
+}
+
+// Extract 4: every occupied slot's row to its rank among the set bits: ascending seq.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_write_kernel(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
+                           const float* __restrict__ normals, const uint32_t* __restrict__ colors,
+                           unsigned long long slots, const unsigned long long* __restrict__ bitmap,
+                           const uint32_t* __restrict__ word_prefix, unsigned long long total, unsigned long long rows,
+                           float* __restrict__ out_points, float* __restrict__ out_normals, uint32_t* __restrict__ out_index,
+                           uint8_t* __restrict__ out_colors) {
+  write_rows<false>(table, points, normals, colors, slots, bitmap, word_prefix, total, rows, out_points, out_normals,
+                    out_index, out_colors, nullptr, nullptr);
+}
+
+// Extract 4 of a map of means with the cells' counts.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_write_counts_kernel(const VoxelSlot* __restrict__ table, const float* __restrict__ points,
+                                  const float* __restrict__ normals, const uint32_t* __restrict__ colors,
+                                  unsigned long long slots, const unsigned long long* __restrict__ bitmap,
+                                  const uint32_t* __restrict__ word_prefix, unsigned long long total,
+                                  unsigned long long rows, float* __restrict__ out_points, float* __restrict__ out_normals,
+                                  uint32_t* __restrict__ out_index, uint8_t* __restrict__ out_colors,
+                                  const unsigned long long* __restrict__ sum_n, uint32_t* __restrict__ out_counts) {
+  write_rows<true>(table, points, normals, colors, slots, bitmap, word_prefix, total, rows, out_points, out_normals,
+                   out_index, out_colors, sum_n, out_counts);
 }
 
 // The set bits below bit `m` of the bitmap, m <= total.  m = total with total a multiple of 64 names the word one past
@@ -370,15 +598,44 @@ __global__ void __launch_bounds__(VM_THREADS)
 
 // A table of `slots` slots inside a block: slots | point rows | normal rows | packed colours, as ensure_slots lays them
 // out (a plane the map does not keep takes no room: the next one starts where it would).
+// A map of means goes on behind them: counts | lattice sums | normal sums | colour sums | epoch words (sums_at ... end,
+// one stretch that is zero in an empty table).  In a nearest-point map sums_at == end and nothing is added.
 struct TableLayout {
-  size_t points_at, normals_at, colors_at, end;
+  size_t points_at, normals_at, colors_at, sums_at, s_at, t_at, c_at, epoch_at, end;
 };
-__host__ __device__ __forceinline__ TableLayout table_layout(unsigned long long slots, bool with_normals, bool with_colors) {
+__host__ __device__ __forceinline__ TableLayout table_layout(unsigned long long slots, bool with_normals, bool with_colors,
+                                                             bool mean) {
   const size_t table_bytes = ((size_t)slots * sizeof(VoxelSlot) + 255) & ~(size_t)255;
   const size_t row_bytes = ((size_t)slots * 12 + 255) & ~(size_t)255;
   const size_t color_bytes = ((size_t)slots * 4 + 255) & ~(size_t)255;
   const size_t colors_at = table_bytes + row_bytes * (with_normals ? 2 : 1);
-  return TableLayout{table_bytes, table_bytes + row_bytes, colors_at, colors_at + (with_colors ? color_bytes : 0)};
+  TableLayout lay{};
+  lay.points_at = table_bytes, lay.normals_at = table_bytes + row_bytes, lay.colors_at = colors_at;
+  lay.sums_at = colors_at + (with_colors ? color_bytes : 0);
+  const size_t count_bytes = ((size_t)slots * 8 + 255) & ~(size_t)255, sum_bytes = ((size_t)slots * 24 + 255) & ~(size_t)255;
+  lay.s_at = lay.sums_at + (mean ? count_bytes : 0);
+  lay.t_at = lay.s_at + (mean ? sum_bytes : 0);
+  lay.c_at = lay.t_at + (mean && with_normals ? sum_bytes : 0);
+  lay.epoch_at = lay.c_at + (mean && with_colors ? sum_bytes : 0);
+  lay.end = lay.epoch_at + (mean ? color_bytes : 0);
+  return lay;
+}
+// The planes of a table of `slots` slots at `base`.
+struct PlacedTable {
+  MapTable m;
+  MeanPlanes mp;
+};
+__host__ __device__ __forceinline__ PlacedTable place_table(char* base, unsigned long long slots, bool with_normals,
+                                                            bool with_colors, bool mean, unsigned long long* cell_count) {
+  const TableLayout lay = table_layout(slots, with_normals, with_colors, mean);
+  PlacedTable t{};
+  t.m = MapTable{(VoxelSlot*)base, (float*)(base + lay.points_at), with_normals ? (float*)(base + lay.normals_at) : nullptr,
+                 with_colors ? (uint32_t*)(base + lay.colors_at) : nullptr, slots - 1, cell_count};
+  if (mean)
+    t.mp = MeanPlanes{(unsigned long long*)(base + lay.sums_at), (long long*)(base + lay.s_at),
+                      with_normals ? (long long*)(base + lay.t_at) : nullptr,
+                      with_colors ? (unsigned long long*)(base + lay.c_at) : nullptr, (uint32_t*)(base + lay.epoch_at)};
+  return t;
 }
 // The slots of a map of k > 0 retained cells: the smallest power of two >= max(2 k, min_slots), min_slots the power of two
 // of an empty map (max(2 * reserve_cells, 64)).  Host and device evaluate it alike.
@@ -392,24 +649,25 @@ __host__ __device__ __forceinline__ unsigned long long retained_slots(unsigned l
 // its rank among the survivors, the new seq; the distance half of `best` stays.  The new table's size follows from k,
 // which only the device knows yet: the block has room for max_slots (the size for every old cell) and its first
 // max_slots slots are VX_EMPTY.  Counts the new table's cells.
-__global__ void __launch_bounds__(VM_THREADS)
-    voxel_map_rebuild_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
-                             const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
-                             unsigned long long old_slots, const unsigned long long* __restrict__ bitmap,
-                             const uint32_t* __restrict__ word_prefix, unsigned long long total,
-                             const unsigned long long* __restrict__ k_word, char* new_base, unsigned long long min_slots,
-                             unsigned long long max_slots, uint32_t with_normals, uint32_t with_colors,
-                             unsigned long long* __restrict__ cell_count, unsigned long long* __restrict__ fault) {
+// MEAN: N and the sums move with the row (the new table's sum planes were zeroed by voxel_map_zero_sums_kernel).
+template <bool MEAN>
+__device__ __forceinline__ void rebuild_slots(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                                              const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                                              unsigned long long old_slots, const unsigned long long* __restrict__ bitmap,
+                                              const uint32_t* __restrict__ word_prefix, unsigned long long total,
+                                              const unsigned long long* __restrict__ k_word, char* new_base,
+                                              unsigned long long min_slots, unsigned long long max_slots,
+                                              uint32_t with_normals, uint32_t with_colors,
+                                              unsigned long long* __restrict__ cell_count,
+                                              unsigned long long* __restrict__ fault, const MeanPlanes& old_mp) {
   const unsigned long long k = *k_word;
   if (2 * k > max_slots) {  // (cannot happen: k <= the old cells; a bound on every store below)
     if (threadIdx.x == 0) atomicMax(fault, 1ull);
     return;
   }
   const unsigned long long slots = retained_slots(k, min_slots);  // <= max_slots
-  const TableLayout lay = table_layout(slots, with_normals != 0, with_colors != 0);
-  const MapTable m{(VoxelSlot*)new_base, (float*)(new_base + lay.points_at),
-                   with_normals ? (float*)(new_base + lay.normals_at) : nullptr,
-                   with_colors ? (uint32_t*)(new_base + lay.colors_at) : nullptr, slots - 1, cell_count};
+  const PlacedTable placed = place_table(new_base, slots, with_normals != 0, with_colors != 0, MEAN, cell_count);
+  const MapTable& m = placed.m;
   uint32_t n_claimed = 0;
   for (unsigned long long o = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; o < old_slots;
        o += (unsigned long long)gridDim.x * VM_THREADS) {
@@ -433,9 +691,51 @@ __global__ void __launch_bounds__(VM_THREADS)
     *(f32x3_u*)(m.points + 3 * (size_t)s) = *(const f32x3_u*)(old_points + 3 * (size_t)o);
     if (m.normals) *(f32x3_u*)(m.normals + 3 * (size_t)s) = *(const f32x3_u*)(old_normals + 3 * (size_t)o);
     if (m.colors) m.colors[s] = old_colors[o];
+    if (MEAN) move_sums(placed.mp, s, old_mp, o);
   }
   n_claimed = wave_sum(n_claimed);
   if ((threadIdx.x & 63u) == 0 && n_claimed) atomicAdd(m.cell_count, (unsigned long long)n_claimed);
+}
+
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_rebuild_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                             const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                             unsigned long long old_slots, const unsigned long long* __restrict__ bitmap,
+                             const uint32_t* __restrict__ word_prefix, unsigned long long total,
+                             const unsigned long long* __restrict__ k_word, char* new_base, unsigned long long min_slots,
+                             unsigned long long max_slots, uint32_t with_normals, uint32_t with_colors,
+                             unsigned long long* __restrict__ cell_count, unsigned long long* __restrict__ fault) {
+  rebuild_slots<false>(old_table, old_points, old_normals, old_colors, old_slots, bitmap, word_prefix, total, k_word, new_base,
+                       min_slots, max_slots, with_normals, with_colors, cell_count, fault, MeanPlanes{});
+}
+
+// Retain 5 of a map of means.
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_rebuild_mean_kernel(const VoxelSlot* __restrict__ old_table, const float* __restrict__ old_points,
+                                  const float* __restrict__ old_normals, const uint32_t* __restrict__ old_colors,
+                                  unsigned long long old_slots, const unsigned long long* __restrict__ bitmap,
+                                  const uint32_t* __restrict__ word_prefix, unsigned long long total,
+                                  const unsigned long long* __restrict__ k_word, char* new_base,
+                                  unsigned long long min_slots, unsigned long long max_slots, uint32_t with_normals,
+                                  uint32_t with_colors, unsigned long long* __restrict__ cell_count,
+                                  unsigned long long* __restrict__ fault, MeanPlanes old_mp) {
+  rebuild_slots<true>(old_table, old_points, old_normals, old_colors, old_slots, bitmap, word_prefix, total, k_word, new_base,
+                      min_slots, max_slots, with_normals, with_colors, cell_count, fault, old_mp);
+}
+
+// Retain of a map of means, ahead of the rebuild: zeroes the sum planes of the new table, whose place follows from k
+// (it may lie inside the stretch that the host filled with VX_EMPTY for max_slots slots).
+__global__ void __launch_bounds__(VM_THREADS)
+    voxel_map_zero_sums_kernel(const unsigned long long* __restrict__ k_word, char* new_base, unsigned long long min_slots,
+                               unsigned long long max_slots, uint32_t with_normals, uint32_t with_colors) {
+  const unsigned long long k = *k_word;
+  if (2 * k > max_slots) return;  // (cannot happen; the rebuild reports it)
+  const TableLayout lay = table_layout(retained_slots(k, min_slots), with_normals != 0, with_colors != 0, true);
+  unsigned long long* words = (unsigned long long*)(new_base + lay.sums_at);
+  const unsigned long long n_words = (lay.end - lay.sums_at) / 8;  // (every plane is a multiple of 256 bytes)
+  for (unsigned long long w = (unsigned long long)blockIdx.x * VM_THREADS + threadIdx.x; w < n_words;
+       w += (unsigned long long)gridDim.x * VM_THREADS)
+    words[w] = 0ull;
 }
 
 uint32_t slot_blocks(uint64_t slots) {
@@ -445,6 +745,16 @@ uint32_t slot_blocks(uint64_t slots) {
 MapTable table_of(const a3d_voxel_map* m) {
   return MapTable{m->table, m->points, m->normals, m->colors, m->slots - 1, m->cell_count};
 }
+MeanPlanes planes_of(const a3d_voxel_map* m) { return MeanPlanes{m->sum_n, m->sum_s, m->sum_t, m->sum_c, m->epoch}; }
+
+// The map's table is from now on the one of `slots` slots at the start of `block`.
+void adopt_table(a3d_voxel_map* m, void* block, size_t block_bytes, uint64_t slots, unsigned long long* cell_count) {
+  const PlacedTable t = place_table((char*)block, slots, m->with_normals, m->with_colors, m->mean, cell_count);
+  m->block = block, m->block_bytes = block_bytes, m->slots = slots;
+  m->table = t.m.table, m->points = t.m.points, m->normals = t.m.normals, m->colors = t.m.colors;
+  m->cell_count = cell_count;
+  m->sum_n = t.mp.n, m->sum_s = t.mp.s, m->sum_t = t.mp.t, m->sum_c = t.mp.c, m->epoch = t.mp.epoch;
+}
 
 // Makes sure the table has at least 2 * (cells + incoming) slots; `fault` is the call's guard word in scratch.
 a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long* d_fault) {
@@ -453,26 +763,28 @@ a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long*
   uint64_t slots = 64;
   while (slots < need || slots < 2 * m->reserve_cells) slots <<= 1;
   a3d_context* ctx = m->ctx;
-  const TableLayout lay = table_layout(slots, m->with_normals, m->with_colors);
+  const TableLayout lay = table_layout(slots, m->with_normals, m->with_colors, m->mean);
   const size_t bytes = lay.end + 256;
   void* block = nullptr;
   size_t block_bytes = 0;
   A3D_TRY(ctx_block_alloc(ctx, bytes, &block, &block_bytes));
   char* base = (char*)block;
   a3d_voxel_map old = *m;
-  m->block = block, m->block_bytes = block_bytes, m->slots = slots;
-  m->table = (VoxelSlot*)base;
-  m->points = (float*)(base + lay.points_at);
-  m->normals = m->with_normals ? (float*)(base + lay.normals_at) : nullptr;
-  m->colors = m->with_colors ? (uint32_t*)(base + lay.colors_at) : nullptr;
-  m->cell_count = (unsigned long long*)(base + bytes - 256);
+  adopt_table(m, block, block_bytes, slots, (unsigned long long*)(base + bytes - 256));
   hipStream_t s = ctx->stream;
   hipError_t e = hipMemsetAsync(m->table, 0xFF, slots * sizeof(VoxelSlot), s);  // every key VX_EMPTY, every best word ~0
   if (e == hipSuccess) e = hipMemsetAsync(m->cell_count, 0, 8, s);
+  if (e == hipSuccess && m->mean) e = hipMemsetAsync(base + lay.sums_at, 0, lay.end - lay.sums_at, s);
   if (e == hipSuccess && old.block && old.cells) {
-    hipLaunchKernelGGL(voxel_map_rehash_kernel, dim3(slot_blocks(old.slots)), dim3(VM_THREADS), 0, s,
-                       (const VoxelSlot*)old.table, (const float*)old.points, (const float*)old.normals,
-                       (const uint32_t*)old.colors, (unsigned long long)old.slots, table_of(m), d_fault);
+    if (m->mean)
+      hipLaunchKernelGGL(voxel_map_rehash_mean_kernel, dim3(slot_blocks(old.slots)), dim3(VM_THREADS), 0, s,
+                         (const VoxelSlot*)old.table, (const float*)old.points, (const float*)old.normals,
+                         (const uint32_t*)old.colors, (unsigned long long)old.slots, table_of(m), planes_of(&old),
+                         planes_of(m), d_fault);
+    else
+      hipLaunchKernelGGL(voxel_map_rehash_kernel, dim3(slot_blocks(old.slots)), dim3(VM_THREADS), 0, s,
+                         (const VoxelSlot*)old.table, (const float*)old.points, (const float*)old.normals,
+                         (const uint32_t*)old.colors, (unsigned long long)old.slots, table_of(m), d_fault);
     e = hipGetLastError();
   }
   if (e != hipSuccess) {  // the old table stays the map's
@@ -487,6 +799,11 @@ a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long*
     ctx_block_release(ctx, old.block, old.block_bytes);  // reuse is ordered on the context's stream, behind the rehash
   }
   return A3D_OK;
+}
+
+bool no_combine_setting() {
+  const char* env = A3D_DIAG_ENV("A3D_VOXEL_MAP_MEAN_NO_COMBINE");  // diagnostics build: mean pass A without run combining
+  return env && *env == '1';
 }
 
 bool stored_slot_setting() {
@@ -520,6 +837,13 @@ a3d_status a3d_voxel_map_new_rgb(a3d_context* ctx, float voxel_size, const float
 a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
                              uint64_t reserve_cells, a3d_voxel_map** out) {
   return a3d_voxel_map_new_rgb(ctx, voxel_size, origin, with_normals, 0, reserve_cells, out);
+}
+
+a3d_status a3d_voxel_map_new_mean(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
+                                  int with_colors, uint64_t reserve_cells, a3d_voxel_map** out) {
+  A3D_TRY(a3d_voxel_map_new_rgb(ctx, voxel_size, origin, with_normals, with_colors, reserve_cells, out));
+  (*out)->mean = true;
+  return A3D_OK;
 }
 
 a3d_status a3d_voxel_map_insert_rgb(a3d_voxel_map* map, const a3d_point_cloud_view* d_clouds, const uint8_t* const* d_colors,
@@ -562,7 +886,7 @@ a3d_status a3d_voxel_map_insert_rgb(a3d_voxel_map* map, const a3d_point_cloud_vi
   a3d_context* ctx = map->ctx;
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
-  const bool want_stored = stored_slot_setting();
+  const bool want_stored = !map->mean && stored_slot_setting();
   BatchScratch scratch;  // the words: dropped per job, fault; the tail: the per-point slots of the stored-slot form
   A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(MapJob), n_jobs + 1, 0, want_stored ? incoming * 4 : 0, &scratch));
   const MapJob* d_jobs = (const MapJob*)scratch.jobs;
@@ -576,6 +900,25 @@ a3d_status a3d_voxel_map_insert_rgb(a3d_voxel_map* map, const a3d_point_cloud_vi
   const bool stored = want_stored && map->slots <= (1ull << 31);  // (a slot fits the 32-bit word, VM_NO_SLOT apart)
   const dim3 grid_dim((uint32_t)tiles), block(VM_THREADS);
   const uint32_t seq_base = (uint32_t)map->total;
+  if (map->mean) {
+    if (++map->epoch_no == 0) {  // the call numbers wrapped: every epoch word starts again below them
+      A3D_HIP_TRY(hipMemsetAsync(map->epoch, 0, map->slots * 4, s));
+      map->epoch_no = 1;
+    }
+    const MeanParams prm = voxel_mean_params(map->grid.v);
+    const MeanPlanes planes = planes_of(map);
+#ifdef A3D_DIAGNOSTICS
+    if (no_combine_setting())
+      hipLaunchKernelGGL(voxel_map_sum_kernel<false>, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, prm.s, table,
+                         planes, d_dropped, d_fault);
+    else
+#endif
+      hipLaunchKernelGGL(voxel_map_sum_kernel<true>, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, prm.s, table,
+                         planes, d_dropped, d_fault);
+    A3D_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(voxel_map_finish_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, prm.u, table,
+                       planes, map->epoch_no);
+  } else
 #ifdef A3D_DIAGNOSTICS  // (the product library holds the one form it launches)
   if (stored) {
     hipLaunchKernelGGL(voxel_map_insert_kernel<true>, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, map->grid, table,
@@ -614,9 +957,11 @@ a3d_status a3d_voxel_map_insert(a3d_voxel_map* map, const a3d_point_cloud_view* 
   return a3d_voxel_map_insert_rgb(map, d_clouds, nullptr, poses_host, n, out_dropped, out_cells);
 }
 
-a3d_status a3d_voxel_map_extract_rgb(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
-                                     uint32_t* d_out_index, uint64_t capacity, uint64_t* out_len) {
+a3d_status a3d_voxel_map_extract_mean(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
+                                      uint32_t* d_out_index, uint32_t* d_out_counts, uint64_t capacity, uint64_t* out_len) {
   A3D_REQUIRE(map && d_out_points && out_len, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE(!d_out_counts || map->mean, A3D_INVALID_PARAMETER,
+              "a3d_voxel_map_extract_mean: a nearest-point map keeps no counts (a3d_voxel_map_new_mean makes a map of means)");
   A3D_REQUIRE(!d_out_normals || map->with_normals, A3D_MISSING_FIELD, "a3d_voxel_map_extract: the map has no normals");
   A3D_REQUIRE(!d_out_colors || map->with_colors, A3D_MISSING_FIELD, "a3d_voxel_map_extract: the map has no colours");
   {  // the outputs as the caller declared them: `capacity` rows each (no map has 2^32 cells)
@@ -627,6 +972,7 @@ a3d_status a3d_voxel_map_extract_rgb(a3d_voxel_map* map, float* d_out_points, fl
       if (d_out_normals) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + rows * 12, true});
       if (d_out_index) ranges.push_back({(uintptr_t)d_out_index, (uintptr_t)d_out_index + rows * 4, true});
       if (d_out_colors) ranges.push_back({(uintptr_t)d_out_colors, (uintptr_t)d_out_colors + rows * 3, true});
+      if (d_out_counts) ranges.push_back({(uintptr_t)d_out_counts, (uintptr_t)d_out_counts + rows * 4, true});
     }
     A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER, "a3d_voxel_map_extract: the outputs overlap one another");
   }
@@ -662,14 +1008,26 @@ a3d_status a3d_voxel_map_extract_rgb(a3d_voxel_map* map, float* d_out_points, fl
   hipLaunchKernelGGL(voxel_map_prefix_kernel, over_words, block, 0, s, (const unsigned long long*)d_bitmap, (uint32_t)n_words,
                      chunks_per_tile, (const uint32_t*)d_tile_counts, d_prefix);
   A3D_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(voxel_map_write_kernel, over_slots, block, 0, s, (const VoxelSlot*)map->table, (const float*)map->points,
-                     (const float*)map->normals, (const uint32_t*)map->colors, (unsigned long long)map->slots,
-                     (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix, (unsigned long long)map->total,
-                     (unsigned long long)map->cells, d_out_points, d_out_normals, d_out_index, d_out_colors);
+  if (d_out_counts)
+    hipLaunchKernelGGL(voxel_map_write_counts_kernel, over_slots, block, 0, s, (const VoxelSlot*)map->table,
+                       (const float*)map->points, (const float*)map->normals, (const uint32_t*)map->colors,
+                       (unsigned long long)map->slots, (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix,
+                       (unsigned long long)map->total, (unsigned long long)map->cells, d_out_points, d_out_normals,
+                       d_out_index, d_out_colors, (const unsigned long long*)map->sum_n, d_out_counts);
+  else
+    hipLaunchKernelGGL(voxel_map_write_kernel, over_slots, block, 0, s, (const VoxelSlot*)map->table, (const float*)map->points,
+                       (const float*)map->normals, (const uint32_t*)map->colors, (unsigned long long)map->slots,
+                       (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix, (unsigned long long)map->total,
+                       (unsigned long long)map->cells, d_out_points, d_out_normals, d_out_index, d_out_colors);
   A3D_HIP_TRY(hipGetLastError());
   // host-synchronous: the caller may read or free the outputs right after
   A3D_HIP_TRY(hipStreamSynchronize(s));
   return A3D_OK;
+}
+
+a3d_status a3d_voxel_map_extract_rgb(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
+                                     uint32_t* d_out_index, uint64_t capacity, uint64_t* out_len) {
+  return a3d_voxel_map_extract_mean(map, d_out_points, d_out_normals, d_out_colors, d_out_index, nullptr, capacity, out_len);
 }
 
 a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint32_t* d_out_index,
@@ -720,7 +1078,7 @@ a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], cons
   uint64_t min_slots = 64;
   while (min_slots < 2 * map->reserve_cells) min_slots <<= 1;
   const uint64_t max_slots = retained_slots(map->cells, min_slots);
-  const size_t bytes = table_layout(max_slots, map->with_normals, map->with_colors).end + 256;
+  const size_t bytes = table_layout(max_slots, map->with_normals, map->with_colors, map->mean).end + 256;
   void* block = nullptr;
   size_t block_bytes = 0;
   A3D_TRY(ctx_block_alloc(ctx, bytes, &block, &block_bytes));
@@ -758,13 +1116,27 @@ a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], cons
                        (const unsigned long long*)d_marks, (unsigned long long)n_all, d_out);
     e = hipGetLastError();
   }
+  if (e == hipSuccess && map->mean) {
+    hipLaunchKernelGGL(voxel_map_zero_sums_kernel, dim3(slot_blocks(8 * max_slots)), block_dim, 0, s,
+                       (const unsigned long long*)(d_out + n_marks), base, (unsigned long long)min_slots,
+                       (unsigned long long)max_slots, map->with_normals ? 1u : 0u, map->with_colors ? 1u : 0u);
+    e = hipGetLastError();
+  }
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(voxel_map_rebuild_kernel, over_slots, block_dim, 0, s, (const VoxelSlot*)map->table,
-                       (const float*)map->points, (const float*)map->normals, (const uint32_t*)map->colors,
-                       (unsigned long long)map->slots, (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix,
-                       (unsigned long long)total, (const unsigned long long*)(d_out + n_marks), base,
-                       (unsigned long long)min_slots, (unsigned long long)max_slots, map->with_normals ? 1u : 0u,
-                       map->with_colors ? 1u : 0u, d_cell_count, d_fault);
+    if (map->mean)
+      hipLaunchKernelGGL(voxel_map_rebuild_mean_kernel, over_slots, block_dim, 0, s, (const VoxelSlot*)map->table,
+                         (const float*)map->points, (const float*)map->normals, (const uint32_t*)map->colors,
+                         (unsigned long long)map->slots, (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix,
+                         (unsigned long long)total, (const unsigned long long*)(d_out + n_marks), base,
+                         (unsigned long long)min_slots, (unsigned long long)max_slots, map->with_normals ? 1u : 0u,
+                         map->with_colors ? 1u : 0u, d_cell_count, d_fault, planes_of(map));
+    else
+      hipLaunchKernelGGL(voxel_map_rebuild_kernel, over_slots, block_dim, 0, s, (const VoxelSlot*)map->table,
+                         (const float*)map->points, (const float*)map->normals, (const uint32_t*)map->colors,
+                         (unsigned long long)map->slots, (const unsigned long long*)d_bitmap, (const uint32_t*)d_prefix,
+                         (unsigned long long)total, (const unsigned long long*)(d_out + n_marks), base,
+                         (unsigned long long)min_slots, (unsigned long long)max_slots, map->with_normals ? 1u : 0u,
+                         map->with_colors ? 1u : 0u, d_cell_count, d_fault);
     e = hipGetLastError();
   }
   unsigned long long counted = 0;
@@ -791,14 +1163,7 @@ a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], cons
   if (out_removed) *out_removed = removed;
   if (k == 0) return A3D_OK;
   ctx_block_release(ctx, map->block, map->block_bytes);  // (nothing enqueued reads it any more)
-  const uint64_t slots = retained_slots(k, min_slots);
-  const TableLayout lay = table_layout(slots, map->with_normals, map->with_colors);
-  map->block = block, map->block_bytes = block_bytes, map->slots = slots;
-  map->table = (VoxelSlot*)base;
-  map->points = (float*)(base + lay.points_at);
-  map->normals = map->with_normals ? (float*)(base + lay.normals_at) : nullptr;
-  map->colors = map->with_colors ? (uint32_t*)(base + lay.colors_at) : nullptr;
-  map->cell_count = d_cell_count;
+  adopt_table(map, block, block_bytes, retained_slots(k, min_slots), d_cell_count);
   map->cells = map->total = k, map->dropped_total = 0;
   return A3D_OK;
 }
@@ -816,6 +1181,10 @@ a3d_status a3d_voxel_map_clear(a3d_voxel_map* map) {
     A3D_HIP_TRY(hipSetDevice(map->ctx->device));
     A3D_HIP_TRY(hipMemsetAsync(map->table, 0xFF, map->slots * sizeof(VoxelSlot), map->ctx->stream));
     A3D_HIP_TRY(hipMemsetAsync(map->cell_count, 0, 8, map->ctx->stream));
+    if (map->mean) {  // N, the sums and the epoch words: one stretch
+      const TableLayout lay = table_layout(map->slots, map->with_normals, map->with_colors, true);
+      A3D_HIP_TRY(hipMemsetAsync(map->sum_n, 0, lay.end - lay.sums_at, map->ctx->stream));
+    }
   }
   map->cells = map->total = map->dropped_total = 0;
   return A3D_OK;

@@ -17,6 +17,16 @@ struct a3d_voxel_map {
   float* normals = nullptr;
   uint32_t* colors = nullptr;  // [slots] r | g << 8 | b << 16, or null
   unsigned long long* cell_count = nullptr;
+  // a map of means (a3d_voxel_map_new_mean) keeps per slot, beside the row: the count of the cell's points, the sums of
+  // their lattice offsets, of their rounded normals (maps with normals) and of their colours (maps with colours), and
+  // the number of the last insert call that touched the cell; all null in a nearest-point map
+  bool mean = false;
+  unsigned long long* sum_n = nullptr;  // [slots]
+  long long* sum_s = nullptr;           // [slots][3]
+  long long* sum_t = nullptr;           // [slots][3] or null
+  unsigned long long* sum_c = nullptr;  // [slots][3] or null
+  uint32_t* epoch = nullptr;            // [slots]
+  uint32_t epoch_no = 0;                // of the last insert call that launched
   uint64_t cells = 0, total = 0, dropped_total = 0, growths = 0;
   // the working buffers of the frame-to-map ICP (voxel_map_icp.hip): one block of the context's, taken by the first
   // align or accumulate and released with the map

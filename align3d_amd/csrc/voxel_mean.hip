@@ -49,7 +49,7 @@
 #include <cmath>
 #include <vector>
 
-#include "voxel_grid.hpp"  // VoxelGrid, voxel_key, slot_hash, VoxelSlot: shared with voxel_downsample.hip and voxel_map.hip
+#include "voxel_mean.hpp"  // the rule's arithmetic and the run combining: shared with voxel_map.hip (a map of means)
 
 using namespace a3d;
 
@@ -100,10 +100,6 @@ struct MeanJob {
 };
 static_assert(sizeof(MeanJob) == 136, "MeanJob layout");
 
-struct MeanParams {
-  float s, u;
-};
-
 // The halves of a slot's second word (little-endian: [0] the count, [1] ~lowest index, later the run's start).
 __device__ __forceinline__ uint32_t* slot_half(VoxelSlot* slot, int h) { return (uint32_t*)&slot->best + h; }
 
@@ -117,20 +113,6 @@ __device__ __forceinline__ unsigned long long find_slot(const VoxelSlot* __restr
     if (k == 0) break;
   }
   return ~0ull;
-}
-
-// A run is a maximal stretch of lanes of one wave with the same key.  first: this lane starts one.
-__device__ __forceinline__ uint64_t run_heads(unsigned long long key, uint32_t lane, bool* first) {
-  const unsigned long long prev = __shfl_up(key, 1, 64);
-  *first = lane == 0 || prev != key;
-  return __builtin_amdgcn_ballot_w64(*first);
-}
-__device__ __forceinline__ uint32_t run_first_lane(uint64_t heads, uint32_t lane) {  // (lane 0 always starts a run)
-  return 63u - (uint32_t)__builtin_clzll(heads & (~0ull >> (63u - lane)));
-}
-__device__ __forceinline__ uint32_t run_end_lane(uint64_t heads, uint32_t lane) {  // one past the run's last lane
-  const uint64_t above = lane == 63u ? 0ull : heads >> (lane + 1u);
-  return above ? lane + 1u + (uint32_t)__builtin_ctzll(above) : 64u;
 }
 
 // Pass 1.  dropped[job] += dropped points (zeroed by the host upload); *fault is set if a table were ever full (it cannot
@@ -357,14 +339,6 @@ __global__ void __launch_bounds__(VM_THREADS)
   }
 }
 
-// The sums of a cell, or of the part of one that a wave holds.
-struct VmSums {
-  uint32_t n;
-  long long s[3];
-  int t[3];  // (a wave's 64 rows of |r| <= 2^21 fit; the spill accumulators are 64-bit)
-  uint32_t c[3];
-};
-
 // Steps 3 to 6 for one cell: `rec` is its representative, the sums are the whole cell's.
 __device__ __forceinline__ void vmean_finish(const MeanJob& j, VoxelGrid grid, float u, unsigned long long row, f32x4 rec,
                                              unsigned long long n, const long long* s, const long long* t,
@@ -377,26 +351,11 @@ __device__ __forceinline__ void vmean_finish(const MeanJob& j, VoxelGrid grid, f
     if (j.out_normals) *(f32x3_u*)(j.out_normals + 3 * row) = *(const f32x3_u*)(j.normals + 3 * (size_t)index);
     if (j.out_colors) store_color(j.out_colors, row, load_color(j.colors, index));
   } else {
-    const double dn = (double)n;
     const float cx = floorf((rec.x - grid.ox) / grid.v), cy = floorf((rec.y - grid.oy) / grid.v),
                 cz = floorf((rec.z - grid.oz) / grid.v);
-    const float mx = (float)((double)s[0] / dn), my = (float)((double)s[1] / dn), mz = (float)((double)s[2] / dn);
-    out.x = ((cx + 0.5f) * grid.v + grid.ox) + mx * u;
-    out.y = ((cy + 0.5f) * grid.v + grid.oy) + my * u;
-    out.z = ((cz + 0.5f) * grid.v + grid.oz) + mz * u;
-    *(f32x3_u*)(j.out_points + 3 * row) = out;
-    if (j.out_normals) {
-      const double tx = (double)t[0], ty = (double)t[1], tz = (double)t[2];
-      const double l = sqrt((tx * tx + ty * ty) + tz * tz);
-      f32x3 nrm = {0.f, 0.f, 0.f};
-      if (l > 0.0) nrm.x = (float)(tx / l), nrm.y = (float)(ty / l), nrm.z = (float)(tz / l);
-      *(f32x3_u*)(j.out_normals + 3 * row) = nrm;
-    }
-    if (j.out_colors) {
-      const uint32_t r = (uint32_t)((2 * c[0] + n) / (2 * n)), g = (uint32_t)((2 * c[1] + n) / (2 * n)),
-                     b = (uint32_t)((2 * c[2] + n) / (2 * n));
-      store_color(j.out_colors, row, r | g << 8 | b << 16);
-    }
+    *(f32x3_u*)(j.out_points + 3 * row) = vmean_point(cx, cy, cz, grid, u, n, s);
+    if (j.out_normals) *(f32x3_u*)(j.out_normals + 3 * row) = vmean_normal(t);
+    if (j.out_colors) store_color(j.out_colors, row, vmean_color(n, c));
   }
   if (j.out_index) j.out_index[row] = index;
   if (j.out_counts) j.out_counts[row] = (uint32_t)n;
@@ -440,19 +399,10 @@ __global__ void __launch_bounds__(VM_THREADS)
       rec = *(const f32x4*)(sorted + pos);
       const f32x3 pt = {rec.x, rec.y, rec.z};
       if (!voxel_key(pt, grid, &key, nullptr)) key = VX_EMPTY;  // (a record is a kept point: never refused)
-      const float cx = floorf((pt.x - grid.ox) / grid.v), cy = floorf((pt.y - grid.oy) / grid.v),
-                  cz = floorf((pt.z - grid.oz) / grid.v);
-      const float dx = pt.x - ((cx + 0.5f) * grid.v + grid.ox), dy = pt.y - ((cy + 0.5f) * grid.v + grid.oy),
-                  dz = pt.z - ((cz + 0.5f) * grid.v + grid.oz);
       a.n = 1;
-      a.s[0] = (int)rintf(dx * prm.s), a.s[1] = (int)rintf(dy * prm.s), a.s[2] = (int)rintf(dz * prm.s);
+      vmean_offsets(pt, grid, prm.s, a.s);
       const uint32_t index = __float_as_uint(rec.w);
-      if (normals) {
-        const f32x3 nr = *(const f32x3_u*)(normals + 3 * (size_t)index);
-        // (a NaN fails every comparison)
-        if (fabsf(nr.x) <= 2.f && fabsf(nr.y) <= 2.f && fabsf(nr.z) <= 2.f)
-          a.t[0] = (int)rintf(nr.x * 1048576.0f), a.t[1] = (int)rintf(nr.y * 1048576.0f), a.t[2] = (int)rintf(nr.z * 1048576.0f);
-      }
+      if (normals) vmean_round_normal(*(const f32x3_u*)(normals + 3 * (size_t)index), a.t);
       if (colors) {
         const uint32_t rgb = load_color(colors, index);
         a.c[0] = rgb & 255u, a.c[1] = (rgb >> 8) & 255u, a.c[2] = (rgb >> 16) & 255u;
@@ -478,20 +428,7 @@ __global__ void __launch_bounds__(VM_THREADS)
     bool first;
     const uint64_t heads = run_heads(key, lane, &first);
     const uint32_t first_lane = run_first_lane(heads, lane), end_lane = run_end_lane(heads, lane);
-    // inclusive scan inside every run: its last lane ends with the run's sums
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t un = __shfl_up(a.n, o, 64);
-      const long long us0 = __shfl_up(a.s[0], o, 64), us1 = __shfl_up(a.s[1], o, 64), us2 = __shfl_up(a.s[2], o, 64);
-      const int ut0 = __shfl_up(a.t[0], o, 64), ut1 = __shfl_up(a.t[1], o, 64), ut2 = __shfl_up(a.t[2], o, 64);
-      const uint32_t uc0 = __shfl_up(a.c[0], o, 64), uc1 = __shfl_up(a.c[1], o, 64), uc2 = __shfl_up(a.c[2], o, 64);
-      if (lane >= first_lane + (uint32_t)o) {
-        a.n += un;
-        a.s[0] += us0, a.s[1] += us1, a.s[2] += us2;
-        a.t[0] += ut0, a.t[1] += ut1, a.t[2] += ut2;
-        a.c[0] += uc0, a.c[1] += uc1, a.c[2] += uc2;
-      }
-    }
+    vmean_scan_runs(a, lane, first_lane);  // a run's last lane ends with the run's sums
     // the run's first record, for its last lane
     f32x4 head;
     head.x = __shfl(rec.x, (int)first_lane, 64), head.y = __shfl(rec.y, (int)first_lane, 64);
@@ -560,7 +497,7 @@ a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_
                 "a3d_point_clouds_voxel_mean_device: the origin must be finite");
     grid.ox = origin[0], grid.oy = origin[1], grid.oz = origin[2];
   }
-  const MeanParams prm{32768.0f / voxel_size, voxel_size / 32768.0f};
+  const MeanParams prm = voxel_mean_params(voxel_size);
   std::vector<MeanJob> jobs;
   std::vector<uint64_t> cloud_of_job;
   std::vector<ByteRange> ranges;

@@ -820,12 +820,18 @@ class DeviceVoxelMap:
     origin) bit for bit — points, normals, order and indices — however the inserts were grouped.  normals=True: the map
     keeps a normal per cell and every inserted cloud must have normals.  colors=True: the same for colours (the winner's
     colour per cell; extract() then returns a cloud with colours).  reserve_cells: cells the first table holds without
-    growing."""
+    growing.  mode="mean" (a3d_voxel_map_new_mean): a map of cell means, kept as running integer sums; the contract is the
+    same with voxel_downsample(voxel_size, origin, mode="mean") in place of the nearest-point downsample: centroid, mean
+    normal, mean colour, representative index and count per cell, bit for bit, however the inserts were grouped.  Every
+    method works on either kind of map."""
 
-    def __init__(self, ctx, voxel_size, origin=None, normals=True, reserve_cells=0, colors=False):
+    def __init__(self, ctx, voxel_size, origin=None, normals=True, reserve_cells=0, colors=False, mode="nearest"):
+        if mode not in ("nearest", "mean"):
+            raise _abi.InvalidParameter(f'DeviceVoxelMap: mode is "nearest" or "mean" (got {mode!r})')
         self.ctx = ctx
         self.normals = bool(normals)
         self.colors = bool(colors)
+        self.mode = mode
         self.handle = C.c_void_p()
         o = None
         if origin is not None:
@@ -833,7 +839,10 @@ class DeviceVoxelMap:
             if o.size != 3:
                 raise _abi.InvalidParameter("DeviceVoxelMap: the origin has three coordinates")
             o = (C.c_float * 3)(*o.tolist())
-        if self.colors:
+        if mode == "mean":
+            _abi.check(ctx.lib.a3d_voxel_map_new_mean(ctx.handle, float(voxel_size), o, int(self.normals), int(self.colors),
+                                                      int(reserve_cells), C.byref(self.handle)), "a3d_voxel_map_new_mean")
+        elif self.colors:
             _abi.check(ctx.lib.a3d_voxel_map_new_rgb(ctx.handle, float(voxel_size), o, int(self.normals), 1, int(reserve_cells),
                                                      C.byref(self.handle)), "a3d_voxel_map_new_rgb")
         else:
@@ -865,40 +874,64 @@ class DeviceVoxelMap:
         """Inserts one resident cloud (under `transform`); returns its dropped count."""
         return self.insert_many([cloud], None if transform is None else [transform])[0]
 
-    def extract(self, return_index=False):
+    def extract(self, return_index=False, return_counts=False):
         """The map as a new DevicePointCloud of exactly cells() rows, in ascending sequence number (the order of the
         downsampled merged cloud; the same bits on every run).  return_index=True returns (cloud, index): `index` is a
-        HOST uint32 array, index[k] = the position of row k in the merged cloud of everything inserted."""
+        HOST uint32 array, index[k] = the position of row k in the merged cloud of everything inserted (on a map of
+        means: of the cell's representative, its first point).  return_counts=True (a map of means only, else
+        InvalidParameter) appends `counts`, a HOST uint32 array of the points offered to each row's cell, saturating:
+        the order is (cloud, index, counts), as voxel_downsample returns them."""
+        if return_counts and self.mode != "mean":
+            raise _abi.InvalidParameter('DeviceVoxelMap.extract: return_counts needs a map of means (mode="mean")')
         ctx, cells = self.ctx, self.cells()
         out = DevicePointCloud._allocate(ctx, cells, self.normals, self.colors)
-        d_index = None
+        d_index = d_counts = None
         try:
             if return_index:
                 d_index = ctx.malloc(max(1, cells) * 4)
+            if return_counts:
+                d_counts = ctx.malloc(max(1, cells) * 4)
             n_out = C.c_uint64()
-            if self.colors:
+            if return_counts:
+                _abi.check(ctx.lib.a3d_voxel_map_extract_mean(self.handle, out.d_points, out.d_normals, out.d_colors, d_index,
+                                                              d_counts, cells, C.byref(n_out)), "a3d_voxel_map_extract_mean")
+            elif self.colors:
                 _abi.check(ctx.lib.a3d_voxel_map_extract_rgb(self.handle, out.d_points, out.d_normals, out.d_colors, d_index,
                                                              cells, C.byref(n_out)), "a3d_voxel_map_extract_rgb")
             else:
                 _abi.check(ctx.lib.a3d_voxel_map_extract(self.handle, out.d_points, out.d_normals, d_index, cells,
                                                          C.byref(n_out)), "a3d_voxel_map_extract")
             out.n = int(n_out.value)
-            index = None
-            if return_index:
-                index = ctx.to_host(d_index, np.empty(out.n, np.uint32)) if out.n else np.empty(0, np.uint32)
+            result = [out]
+            for wanted, d_words in ((return_index, d_index), (return_counts, d_counts)):
+                if wanted:
+                    result.append(ctx.to_host(d_words, np.empty(out.n, np.uint32)) if out.n else np.empty(0, np.uint32))
         except BaseException:
             out.free()
             raise
         finally:
-            if d_index is not None:
-                ctx.free(d_index)
-        return (out, index) if return_index else out
+            for d_words in (d_index, d_counts):
+                if d_words is not None:
+                    ctx.free(d_words)
+        return tuple(result) if len(result) > 1 else out
+
+    def bytes_per_slot(self):
+        """Device memory per slot of the table (include/align3d_hip.h): 16 + 12 (+ 12 with normals) (+ 4 with colours),
+        and in a map of means 8 + 24 (+ 24 with normals) (+ 24 with colours) + 4 more."""
+        nearest = 16 + 12 + (12 if self.normals else 0) + (4 if self.colors else 0)
+        if self.mode != "mean":
+            return nearest
+        return nearest + 8 + 24 + (24 if self.normals else 0) + (24 if self.colors else 0) + 4
 
     def stats(self):
-        """{cells, slots, total, dropped_total, growths} (a3d_voxel_map_stats)."""
+        """{cells, slots, total, dropped_total, growths} (a3d_voxel_map_stats); a map of means adds mode = "mean" and its
+        bytes_per_slot (a nearest-point map's dict is what it always was; its mode is the attribute `mode`)."""
         s = _abi.VoxelMapStatsC()
         _abi.check(self.ctx.lib.a3d_voxel_map_get_stats(self.handle, C.byref(s)), "a3d_voxel_map_get_stats")
-        return s.as_dict()
+        d = s.as_dict()
+        if self.mode == "mean":
+            d["mode"], d["bytes_per_slot"] = self.mode, self.bytes_per_slot()
+        return d
 
     def cells(self):
         return self.stats()["cells"]
@@ -912,7 +945,10 @@ class DeviceVoxelMap:
         the surviving rows went as one cloud (a3d_voxel_map_retain), total() is k and the table has shrunk to fit.
         Returns the number of removed cells, or (removed, new_marks) when `marks` (sequence numbers, e.g. total() at frame
         boundaries) is given: new_marks[i], a numpy uint64 array, is the survivors below marks[i], the same boundary in
-        the new numbering."""
+        the new numbering.  On a map of means the box is tested on the cell's mean row and min_seq on the seq of its
+        representative, its FIRST point (age by last observation is not kept); the survivors keep their sums and counts,
+        and later inserts go on summing into them: the map is then the mean downsample of everything ever offered to the
+        surviving cells followed by whatever comes later, not a new map of the surviving rows."""
         lo = hi = None
         if box is not None:
             try:

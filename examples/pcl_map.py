@@ -1,22 +1,25 @@
 #!/usr/bin/env python3
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
-        [--voxel V [--mean | --online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
+        [--voxel V [--mean] [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
         [--estimate-normals R] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
 back in one resident cloud (one launch).  With --voxel V the map is then thinned to one point per V-sized cell
 (DevicePointCloud.voxel_downsample: still on the device) and the last frame is aligned against the thinned map with Icp,
-frame to map.  With --mean (the offline route only: merge -> voxel_downsample(mode="mean")) a second map is made from the
+frame to map.  With --mean on the offline route (merge -> voxel_downsample(mode="mean")) a second map is made from the
 same merged cloud, the centroid of each cell with its mean normal and mean colour instead of one picked sample, and the
 figures printed for the nearest-point map are printed for it as well, side by side.  With --online the thinned map is built the way a live caller would, frame by frame into a persistent
 DeviceVoxelMap (insert per frame, one extract at the end) instead of merge + voxel_downsample of everything: no merged
 cloud exists at any time, and the lines it prints are the same; the last frame is then corrected against the live map
 itself (DeviceVoxelMap.align from its odometry pose: no extract, no kd-tree build, the frame in its own coordinates), and
 the correction printed is that alignment relative to the odometry pose (the map's association is not the kd-tree's, so
-its figures differ from the batch path's).  --check-batch runs the batch path as well, only to
-assert that the two maps are the same bits.  --window-box R and --window-frames W keep the online map LOCAL, the way
+its figures differ from the batch path's).  --online --mean makes the live map a map of cell means
+(DeviceVoxelMap(mode="mean"): running integer sums per cell; everything else, the windows and --render-track included, runs
+unchanged on it, and a window then keeps a cell by its mean row and by the age of its FIRST point).  --check-batch runs the
+batch path as well, only to assert that the two maps are the same bits (with --mean: the bits of
+voxel_downsample(mode="mean")).  --window-box R and --window-frames W keep the online map LOCAL, the way
 an odometry loop that runs for hours must: after each insert DeviceVoxelMap.retain drops the cells outside the box of
 half-side R (metres) around the current camera position, or the cells whose point is older than the last W frames
 (frame boundaries are recorded as total() and carried through every retain by its `marks`).  A retain also renumbers the
@@ -51,7 +54,8 @@ ap.add_argument("dataset", nargs="?", default=os.path.join(ROOT, "tests", "golde
 ap.add_argument("--max-frames", type=int, default=None)
 ap.add_argument("--voxel", type=float, default=None, help="thin the map to one point per cell of this size (metres)")
 ap.add_argument("--mean", action="store_true",
-                help="with --voxel, not --online: also thin the merged cloud to each cell's mean and print both maps' figures")
+                help="with --voxel: also thin the merged cloud to each cell's mean and print both maps' figures; with --online: "
+                     "the live map is a map of cell means")
 ap.add_argument("--online", action="store_true", help="with --voxel: build the thinned map by inserting frame by frame")
 ap.add_argument("--check-batch", action="store_true",
                 help="with --online: also run merge + voxel_downsample and assert that the online map is the same bits")
@@ -69,8 +73,8 @@ ap.add_argument("--out", default=None, help="write the map's points to this .npy
 args = ap.parse_args()
 if args.online and not args.voxel:
     ap.error("--online needs --voxel")
-if args.mean and (not args.voxel or args.online):
-    ap.error("--mean needs --voxel and the offline route (the persistent map keeps its nearest-to-centre rule)")
+if args.mean and not args.voxel:
+    ap.error("--mean needs --voxel")
 if args.check_batch and not args.online:
     ap.error("--check-batch needs --online")
 windowed = args.window_box is not None or args.window_frames is not None
@@ -120,16 +124,20 @@ def thinned_by_batch():
     """(points offered, thinned map): all frames in one coordinate system, then one point per cell."""
     global mean_map
     full = DevicePointCloud.merge(clouds, camera_to_world)
-    thin = full.voxel_downsample(args.voxel)
-    if args.mean:
-        mean_map = full.voxel_downsample(args.voxel, mode="mean")
+    if args.online and args.mean:  # --check-batch of a live map of means: the batch call it must equal
+        thin = full.voxel_downsample(args.voxel, mode="mean")
+    else:
+        thin = full.voxel_downsample(args.voxel)
+        if args.mean:
+            mean_map = full.voxel_downsample(args.voxel, mode="mean")
     offered = full.len()
     full.free()
     return offered, thin
 
 
 if args.online:
-    online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None, colors=args.colors)
+    online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None, colors=args.colors,
+                            mode="mean" if args.mean else "nearest")
     offered = 0
     starts = collections.deque()  # --window-frames: the first sequence number of each kept frame, in the map's numbering
     corrected = []  # --render-track: the poses the frames went in under
@@ -188,7 +196,7 @@ if args.online:
         same = batch_map.len() == world_map.len() and all(
             a is None and b is None or np.array_equal(a.view(np.uint32), b.view(np.uint32))
             for a, b in zip(batch_map.download(), world_map.download()))
-        assert same, "the online map differs from merge + voxel_downsample"
+        assert same, "the online map differs from merge + voxel_downsample" + (' (mode="mean")' if args.mean else "")
         if args.colors:
             assert np.array_equal(batch_map.download_colors(), world_map.download_colors()), "the maps' colours differ"
         batch_map.free()
@@ -197,7 +205,8 @@ elif args.voxel:
 else:
     world_map = DevicePointCloud.merge(clouds, camera_to_world)  # the last step: all frames in one coordinate system
 if args.voxel:
-    print(f"voxel {args.voxel}: {offered} points -> {world_map.len()}")
+    print(f"voxel {args.voxel}{' (a live map of cell means)' if args.online and args.mean else ''}: {offered} points -> "
+          f"{world_map.len()}")
     if not args.online:
         # frame to map: the last frame, brought to the world by its odometry pose, against the thinned map; what Icp
         # returns is the correction the map asks of that pose

@@ -685,6 +685,23 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
  * after any sequence of inserts a3d_voxel_map_extract_rgb equals a3d_point_clouds_merge_rgb_device of everything inserted
  * followed by a3d_point_clouds_voxel_downsample_rgb_device, colours included.  After a retain the map is a new map into
  * which the surviving rows, colours too, went as one cloud.  Nearest, align and accumulate never read colours.
+ * A map of MEANS (a3d_voxel_map_new_mean) keeps a3d_point_clouds_voxel_mean_device's rule instead of the nearest-point rule,
+ * as running integer sums per slot, and the contract carries over word for word: after any sequence of inserts
+ * a3d_voxel_map_extract_mean equals a3d_point_clouds_merge_rgb_device of everything inserted followed by
+ * a3d_point_clouds_voxel_mean_device(voxel_size, origin): points, normals, colours, order, representative indices and
+ * counts, bit for bit, however the inserts were grouped (every term of every sum is an integer, so no order of addition
+ * can matter; poses are applied before a point or a normal is quantised, the bits the merge writes).  A cell's
+ * representative is its lowest seq, rows are in ascending representative, a cell with one point holds that point's row
+ * bit for bit.  The count of a cell is kept in 64 bits and exported as u32, saturating; the normal sums are exact in f64
+ * up to 2^32 points per cell, as in the batch rule.  Every other call takes a map of means through the same entry:
+ * insert (two launches, as on a nearest-point map), extract, retain, nearest, icp_*, render, clear, get_stats; the
+ * readers see the mean row where they saw the winner's.  Retain on a map of means: the box is tested on the stored row,
+ * the mean; min_seq on the representative's seq (age by last observation is not kept); the survivors keep their rows,
+ * sums and counts and are numbered 0 ... k-1 in their old order, and later inserts go on summing into them.  Such a map
+ * is then NOT a new map into which the surviving rows went as one cloud: it is the mean downsample of every point ever
+ * offered to the surviving cells, in their original order, followed by whatever comes later.  Six launches.  Device memory
+ * of a map of means, per slot: the above plus 8 (count) + 24 (lattice sums) (+ 24 with normals) (+ 24 with colours) + 4
+ * (the number of the last insert call that touched the cell): 64 bytes for points alone, 100 with normals, 128 with both.
  * Multi-GPU maps are NOT built.
  * Every call is host-synchronous (one wait, at its end) and ordered on the context's stream; a map belongs to its context
  * and must be freed before it. */
@@ -707,6 +724,11 @@ a3d_status a3d_voxel_map_new(a3d_context* ctx, float voxel_size, const float ori
  * a3d_voxel_map_new has no colours. */
 a3d_status a3d_voxel_map_new_rgb(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
                                  int with_colors, uint64_t reserve_cells, a3d_voxel_map** out);
+/* The same arguments and errors; the map is a map of means (above): per cell the centroid, the mean normal and the mean
+ * colour of everything offered to it, by the rule of a3d_point_clouds_voxel_mean_device.  The mode is fixed for the map's
+ * life. */
+a3d_status a3d_voxel_map_new_mean(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
+                                  int with_colors, uint64_t reserve_cells, a3d_voxel_map** out);
 /* Inserts n resident clouds (device pointers on the map's context) under poses_host[i] (NULL = as they are, bit for bit;
  * otherwise Transform::transform_vector / transform_normal as a3d_point_clouds_merge_device).  out_dropped (NULL ok): [n],
  * the dropped points of each cloud; out_cells (NULL ok): the map's occupied cells afterwards.
@@ -735,6 +757,12 @@ a3d_status a3d_voxel_map_extract(a3d_voxel_map* map, float* d_out_points, float*
  * check by its first 3 * capacity bytes; bytes at or past 3 * cells are never written. */
 a3d_status a3d_voxel_map_extract_rgb(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
                                      uint32_t* d_out_index, uint64_t capacity, uint64_t* out_len);
+/* The same with the cells' counts into d_out_counts (NULL ok; room for `capacity` u32): the points ever offered to each
+ * row's cell, saturating at 2^32 - 1; d_out_index is then each cell's representative, its lowest seq.  A non-NULL
+ * d_out_counts on a nearest-point map is A3D_INVALID_PARAMETER (it keeps no counts); with d_out_counts NULL the call is
+ * a3d_voxel_map_extract_rgb on either kind of map.  The counts take part in the overlap check by 4 * capacity bytes. */
+a3d_status a3d_voxel_map_extract_mean(a3d_voxel_map* map, float* d_out_points, float* d_out_normals, uint8_t* d_out_colors,
+                                      uint32_t* d_out_index, uint32_t* d_out_counts, uint64_t capacity, uint64_t* out_len);
 /* Rebuilds the map from the cells that survive and numbers them anew.  A cell survives iff its winner's seq >= min_seq
  * and, if a box is given, its stored row p has box_min[k] <= p[k] <= box_max[k] for k = 0, 1, 2: plain f32 comparisons
  * on the stored bits (the cell centre plays no part).  box_min and box_max are both NULL (no box) or both given; infinite
