@@ -343,6 +343,7 @@ DIAG_SIGNATURES = {
     ),
     "a3d_range_image_download_depth16": (_ST, [_P, _P, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "a3d_backproject_proven": (_ST, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "a3d_backproject_short_division_proven": (_ST, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "a3d_acos_gate_threshold": (_ST, [C.c_float, C.c_int32, C.POINTER(C.c_float)]),
 }
 

@@ -181,6 +181,10 @@ struct a3d_context {
   // a3d_context_set_tiling: 0 = the tiling of the ICP pixel pass follows the batch size (throughput); otherwise every
   // (pair, level) is cut into this many blocks whatever the batch: a pair's pose bits no longer depend on its batch.
   uint32_t tiles_per_pair = 0;
+  // short_division_proven (devmath.hpp) of every focal length a level-0 image of this context has shown to an
+  // alignment, keyed by the f32's bits: the sweep (tens of milliseconds) runs once per camera, never per batch or rebind.
+  std::mutex short_div_mutex;
+  std::vector<std::pair<uint32_t, bool>> short_div_verdicts;
   // Pyramid arenas held by live images.  a3d_context_destroy with arenas outstanding only marks the context (zombie);
   // the release of the last arena destroys it (both under pool_mutex).
   int live_arenas = 0;

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <stdint.h>
 
 #define A3D_HD __host__ __device__ __forceinline__
@@ -264,6 +265,22 @@ __device__ __forceinline__ V3 backproject_px_proven(uint32_t d, int row, int col
   p.x = div_by(ax, dfx), p.y = div_by(ay, dfy);
   return p;
 }
+// The same with the pixel's row and column already in f32 (the pixel loop carries the source's that way: integers below
+// 2^24 are exact), and, SHORT, with the focal lengths' host reciprocals d.y = RN(1 / f) in three operations per quotient
+// (div_short; only for focal lengths that pass short_division_proven below: the same bits as div_by, as `/`).
+__device__ __forceinline__ float div_short(float a, const DivBy d) {
+  const float q = a * d.y;
+  return __builtin_fmaf(__builtin_fmaf(d.negz, q, a), d.y, q);
+}
+template <bool SHORT>
+__device__ __forceinline__ V3 backproject_px_proven_f(float d, float row, float col, float cx, float cy, float scale,
+                                                      const DivBy dfx, const DivBy dfy) {
+  V3 p;
+  p.z = d * scale;
+  const float ax = (col - cx) * p.z, ay = (row - cy) * p.z;
+  p.x = SHORT ? div_short(ax, dfx) : div_by(ax, dfx), p.y = SHORT ? div_short(ay, dfy) : div_by(ay, dfy);
+  return p;
+}
 #endif  // __HIPCC__
 
 // Host: whether backproject_px_proven is backproject_px for every (d in [1, 65535], row in [0, h), col in [0, w)) of an
@@ -300,6 +317,50 @@ inline bool backproject_proven(uint32_t w, uint32_t h, float fx, float fy, float
     return !zero || f > 0.0f;
   };
   return axis_ok(w, fx, cx) && axis_ok(h, fy, cy);
+}
+
+// ---- division by a wave-uniform focal length in three operations (div_short) -------------------------------------
+// div_by spends a second correction because the device's refined reciprocal is not the correctly rounded one.  For a
+// divisor that the host knows, y = RN(1 / f) comes from the host, and whether
+//   q = a y;  r = fma(-f, q, a);  q' = fma(r, y, q)
+// is the IEEE quotient a / f is decided for that f by exhaustion (short_division_proven): inside the ranges that
+// backproject_proven guarantees (1e-20 < |a| < 1e9, 1e-9 < |f| < 1e9) the product, the remainder (whose last bit is
+// near a 2^-48 > 3e-35) and the quotient stay normal, so every operation scales exactly with the numerator's power of
+// two, and all four are odd in a: the 2^23 mantissas of a in [1, 2) decide every non-zero numerator.  a = +0 gives
+// +0 +0 +0 for f > 0, what backproject_proven already requires where a zero numerator exists.
+// (std::fmaf without the host's FMA unit is a library call of ~50 ns: the sweep is compiled a second time for it)
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#define A3D_HOST_FMA 1
+#define A3D_HOST_FMA_TARGET __attribute__((target("fma")))
+#else
+#define A3D_HOST_FMA 0
+#define A3D_HOST_FMA_TARGET
+#endif
+template <bool HW>
+__attribute__((always_inline)) inline bool short_division_sweep(float f, float y) {
+  const float nf = -f;
+  uint32_t bad = 0;
+  for (uint32_t m = 0; m < (1u << 23); ++m) {
+    const uint32_t bits = 0x3f800000u | m;
+    float a;
+    memcpy(&a, &bits, 4);
+    const float q = a * y;
+    const float r = HW ? __builtin_fmaf(nf, q, a) : std::fmaf(nf, q, a);
+    const float q1 = HW ? __builtin_fmaf(r, y, q) : std::fmaf(r, y, q);
+    bad |= (uint32_t)(q1 != a / f);
+  }
+  return bad == 0;
+}
+A3D_HOST_FMA_TARGET inline bool short_division_sweep_fma(float f, float y) { return short_division_sweep<true>(f, y); }
+// Host: whether div_short(a, -f, RN(1 / f)) == a / f for every numerator backproject_px_proven can meet (tens of
+// milliseconds: the callers cache the verdict per focal length, common.hpp short_division_cached).
+inline bool short_division_proven(float f) {
+  if (!((std::fabs(f) > 1e-9f) & (std::fabs(f) < 1e9f))) return false;  // div_den_ok
+  const float y = 1.0f / f;
+#if A3D_HOST_FMA
+  if (__builtin_cpu_supports("fma")) return short_division_sweep_fma(f, y);
+#endif
+  return short_division_sweep<false>(f, y);
 }
 
 #if defined(__HIPCC__)

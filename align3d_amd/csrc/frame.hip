@@ -1032,6 +1032,17 @@ a3d_status a3d_backproject_proven(uint32_t width, uint32_t height, const float b
   *out_proven = a3d::backproject_proven(width, height, k[0], k[1], k[2], k[3], k[4]) ? 1 : 0;
   return A3D_OK;
 }
+
+a3d_status a3d_backproject_short_division_proven(uint32_t width, uint32_t height, const float backproject[5],
+                                                 int32_t* out_proven) {
+  A3D_REQUIRE(backproject && out_proven, A3D_INVALID_PARAMETER, "null argument");
+  const float* k = backproject;
+  *out_proven = (a3d::backproject_proven(width, height, k[0], k[1], k[2], k[3], k[4]) && a3d::short_division_proven(k[0]) &&
+                 a3d::short_division_proven(k[1]))
+                    ? 1
+                    : 0;
+  return A3D_OK;
+}
 #endif
 
 }  // extern "C"

@@ -26,7 +26,8 @@ struct LevelDesc {
   uint32_t src_n;
   uint32_t tw, th;
   float fx, fy, cx, cy;
-  uint32_t flags;  // bit 0: both images carry mask_is_z; bit 1: both carry points_from_depth (common.hpp)
+  uint32_t flags;  // bit 0: both images carry mask_is_z; bit 1: both carry points_from_depth (common.hpp); bit 2: and the
+                   // four focal lengths of src_bp / tgt_bp pass short_division_proven (devmath.hpp)
   uint32_t ppt;    // source pixels per thread at this level: the pair's tiles are ceil(src_n / (256 ppt)) blocks
   uint32_t src_w;  // source width (DEPTH16: the source pixel's row and column)
   // DEPTH16 (level 0 of device-built pyramids): the depth planes the points were back-projected from, and each side's
@@ -36,8 +37,9 @@ struct LevelDesc {
   float src_bp[5], tgt_bp[5];
   float src_inv_w;            // 1.0f / src_w (correctly rounded, host)
   uint32_t pad;
+  float src_rcp_f[2], tgt_rcp_f[2];  // RN(1 / fx), RN(1 / fy) of each side's back-projection (host): div_short
 };
-static_assert(sizeof(LevelDesc) == 160, "LevelDesc layout");
+static_assert(sizeof(LevelDesc) == 176, "LevelDesc layout");
 
 struct Gates {
   float max_distance_sqr;
@@ -113,8 +115,26 @@ struct SrcPx {  // stage A: one source record
   uint8_t intensity;   // the raw byte; converted to f32 where it is used (stage D), two steps after its load,
                        // so that the conversion does not wait for the load inside the step that issued it
   bool live;
-  uint32_t depth, row, col;  // D16 & D16_SRC: the raw u16 depth (back-projected in stage B, where it is consumed) and its pixel
+  uint32_t depth;  // D16 & D16_SRC: the raw u16 depth (back-projected in stage B, where it is consumed)
+  float row, col;  // ... and its pixel, in f32 (exact: below 2^24).  They feed the back-projection ONLY: every address
+                   // comes from the clamped index.  A lane that is out of range carries coordinates of no pixel and is dead.
 };
+// A thread's pixels are 256 apart: row and column of the next one from this one's, with the wave-uniform quotient and
+// remainder of 256 by the width (SrcStride), instead of a division of the index per pixel.  Exact in f32.
+struct SrcStride {
+  float q, q1, r, w;  // 256 / w, 256 / w + 1, 256 % w, w
+};
+__device__ __forceinline__ SrcStride make_src_stride(uint32_t w) {
+  w = w ? w : 1u;
+  const uint32_t q = 256u / w;
+  return {(float)q, (float)(q + 1u), (float)(256u - q * w), (float)w};
+}
+__device__ __forceinline__ void src_advance(const SrcStride& st, float row, float col, float* nrow, float* ncol) {
+  const float c = col + st.r;
+  const bool wrap = c >= st.w;
+  *ncol = wrap ? c - st.w : c;
+  *nrow = row + (wrap ? st.q1 : st.q);
+}
 // The back-projection constants of one side (DEPTH16), wave-uniform: fx, fy, cx, cy, scale, the two shared reciprocals.
 struct BackProj {
   float fx, fy, cx, cy, scale;
@@ -126,9 +146,14 @@ struct BackProj2 {
 __device__ __forceinline__ float uniform_f(float x) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
 }
-__device__ __forceinline__ BackProj make_backproj(const float (&k)[5]) {
+template <bool SHORT = false>
+__device__ __forceinline__ BackProj make_backproj(const float (&k)[5], const float (&rcp_f)[2]) {
   BackProj b;
   b.fx = k[0], b.fy = k[1], b.cx = k[2], b.cy = k[3], b.scale = k[4];
+  if (SHORT) {  // div_short: the host's correctly rounded reciprocals, straight out of the descriptor
+    b.dfx = DivBy{-b.fx, rcp_f[0]}, b.dfy = DivBy{-b.fy, rcp_f[1]};
+    return b;
+  }
   // (computed once per kernel in the VALU; readfirstlane parks the results in SGPRs, not in eight VGPRs)
   const DivBy dx = div_prepare(b.fx), dy = div_prepare(b.fy);
   b.dfx = DivBy{uniform_f(dx.negz), uniform_f(dx.y)}, b.dfy = DivBy{uniform_f(dy.negz), uniform_f(dy.y)};
@@ -146,15 +171,22 @@ constexpr int D16_SIDES = D16_TGT | (A3D_ICP_DEPTH16_SRC ? D16_SRC : 0);
 // (0, 0, 0), frame.hip) — the two mask bytes per pixel need not be read.  Decided per launch on the host.
 // D16 & D16_SRC (level 0 of device-built pyramids, decided per launch on the host): the record is the pixel's 2-byte depth
 // instead of its 12-byte point; mask == (depth != 0) on these images.
+// `prev` (D16 & D16_SRC): the record of the thread's pixel before this one, 256 pixels back; none for its first pixel.
 template <bool ZMASK = false, int D16 = 0>
-__device__ __forceinline__ SrcPx stage_a(const LevelDesc& d, uint32_t i, bool in_range) {
+__device__ __forceinline__ SrcPx stage_a(const LevelDesc& d, uint32_t i, bool in_range, const SrcPx* prev = nullptr,
+                                         const SrcStride* stride = nullptr) {
   const uint32_t ii = in_range ? i : 0u;
   SrcPx s;
   if (D16 & D16_SRC) {
-    // row = floor((ii + 0.5) / w) in f32: exact below 2^22 pixels (the host checks) — (ii + 0.5) is representable, the two
-    // roundings move the quotient by less than 2^-23 of itself, less than its distance 0.5 / w from an integer
-    const uint32_t r = f32_as_usize(((float)ii + 0.5f) * d.src_inv_w);
-    s.row = r, s.col = ii - __umul24(r, d.src_w);
+    if (prev) {
+      src_advance(*stride, prev->row, prev->col, &s.row, &s.col);
+    } else {
+      // row = floor((i + 0.5) / w) in f32: exact below 2^22 pixels (the host checks) — (i + 0.5) is representable, the two
+      // roundings move the quotient by less than 2^-23 of itself, less than its distance 0.5 / w from an integer.  (Of the
+      // index itself, not the clamped one: a lane whose first pixel is out of range has no later pixel in range either.)
+      const uint32_t r = f32_as_usize(((float)i + 0.5f) * d.src_inv_w);
+      s.row = (float)r, s.col = (float)(i - __umul24(r, d.src_w));
+    }
     s.depth = ld<uint16_t>(d.src_depth, ii * 2u);
     s.intensity = ld<uint8_t>(d.src_intensities, ii);
     s.live = in_range;  // & (depth != 0): in stage B, where the depth is consumed
@@ -179,20 +211,22 @@ struct ProjPx {  // stage B: transformed point, projection, the gathered target 
   V3 tp, tn;
   uint8_t tmask;  // consumed in stage C, so that stage B only ISSUES the gathers
   bool live;
-  uint16_t tdepth;        // D16 & D16_TGT: the gathered u16 depth, widened where it is consumed (stage C)
+  _Float16 tdepth;        // D16 & D16_TGT: the gathered u16 depth, converted where it is consumed (stage C).  Sixteen opaque
+                          // bits: a float type, because an integer one is zero-extended by an instruction on its way there
   uint32_t trow, tcol;    // ... and its pixel (tp is rebuilt in stage C)
   float t00, t10, t01, t11;     // the map cell at (u, v), requested here unless CLASSIC (then stage C requests it)
 };
 // CLASSIC (diagnostics build only, A3D_ICP_STEP_ORDER=classic): the map cell is requested by stage C, after its gates, as
 // it was before the step was reordered (pixel_pass) — the same values either way.
-template <bool ZMASK = false, int D16 = 0, bool CLASSIC = false>
+// SHORT (with D16 only): the back-projections divide by the focal lengths through div_short (devmath.hpp).
+template <bool ZMASK = false, int D16 = 0, bool CLASSIC = false, bool SHORT = false>
 __device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, const SrcPx& s, float twf, float thf,
                                           const BackProj2& bp = BackProj2{}) {
   ProjPx o;
   V3 sp = s.sp;
   bool slive = s.live;
   if (D16 & D16_SRC) {  // the source point from its depth: the builder's function in its proven form (devmath.hpp), the same bits
-    sp = backproject_px_proven(s.depth, (int)s.row, (int)s.col, bp.src.cx, bp.src.cy, bp.src.scale, bp.src.dfx, bp.src.dfy);
+    sp = backproject_px_proven_f<SHORT>((float)s.depth, s.row, s.col, bp.src.cx, bp.src.cy, bp.src.scale, bp.src.dfx, bp.src.dfy);
     slive = slive & (s.depth != 0u);  // (a depth-0 pixel's (±0, ±0, +0) is never summed)
   }
   o.p = transform_vector(T, sp);
@@ -212,7 +246,7 @@ __device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, con
   const uint32_t col = (uint32_t)f32_as_i32(ur), row = (uint32_t)f32_as_i32(vr);  // (NaN casts to 0)
   const uint32_t tidx = o.live ? __umul24(row, d.tw) + col : 0u;
   if (D16 & D16_TGT) {  // 2 bytes instead of the 12-byte point (and the mask byte: mask == (depth != 0))
-    o.tdepth = ld<uint16_t>(d.tgt_depth, tidx * 2u);
+    o.tdepth = ld<_Float16>(d.tgt_depth, tidx * 2u);
     o.trow = row, o.tcol = col;
     o.tn = ld_v3(d.tgt_normals, tidx);
   } else {
@@ -240,18 +274,20 @@ struct MapPx {  // stage C: gates passed, the intensity-map cell
   float t00, t10, t01, t11;
   uint32_t ui, vi;
 };
-template <bool ZMASK = false, int D16 = 0, bool CLASSIC = false>
+template <bool ZMASK = false, int D16 = 0, bool CLASSIC = false, bool SHORT = false>
 __device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, ProjPx& px, uint32_t mw,
                                          const BackProj2& bp = BackProj2{}) {
   bool tvalid;
   if (D16 & D16_TGT) {  // the gathered depth lands here: the builder's function in its proven form, the same bits
-    // (the depth is widened by an instruction of this stage: a widening left to the compiler is merged across the two
-    // unrolled steps and scheduled into stage B, between its loads, where it waits for the depth of the pixel before)
-    uint32_t wide;
-    asm volatile("v_and_b32 %0, 0xffff, %1" : "=v"(wide) : "v"(px.tdepth));
-    const uint32_t td = px.live ? wide : 0u;  // (a rejected lane's row / column are not a pixel's: no point)
-    px.tp = backproject_px_proven(td, (int)px.trow, (int)px.tcol, bp.tgt.cx, bp.tgt.cy, bp.tgt.scale, bp.tgt.dfx, bp.tgt.dfy);
-    tvalid = td != 0u;  // (td == 0: (±0, ±0, +0), dead below)
+    // (a u16 field widened by the compiler here was merged across the two unrolled steps and scheduled into stage B,
+    // between its loads, where it waited for the depth of the pixel before; widened by hand it cost an instruction twice)
+    // The conversion to f32 reads the register's low half itself, so nothing has to widen the depth first.
+    float wide;
+    asm volatile("v_cvt_f32_u32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(wide) : "v"(px.tdepth));
+    const float td = px.live ? wide : 0.0f;  // (a rejected lane's row / column are not a pixel's: no point)
+    px.tp = backproject_px_proven_f<SHORT>(td, (float)(int)px.trow, (float)(int)px.tcol, bp.tgt.cx, bp.tgt.cy,
+                                           bp.tgt.scale, bp.tgt.dfx, bp.tgt.dfy);
+    tvalid = td != 0.0f;  // (depth 0: (±0, ±0, +0), dead below)
   } else {
     tvalid = ZMASK ? px.tp.z != 0.0f : px.tmask == 1;  // RangeImage::get_point: mask == 1 (structure.rs:176)
   }
@@ -522,7 +558,7 @@ __global__ void __launch_bounds__(256)
 // loads of k, which were requested a whole step (C(k-1) + D(k-1) + B(k+1), ~320 instructions) earlier; C(k), D(k) and the
 // accumulation.  (Before, C(k) came first and requested the cell of k behind its gates, ~115 instructions ahead of its
 // use, with a second wait per pixel; that order is CLASSIC, kept in the diagnostics build as a cross-check:
-// A3D_ICP_STEP_ORDER=classic.)  The cell travels in ProjPx: 112 VGPRs (116 with the masks read), four waves per SIMD.
+// A3D_ICP_STEP_ORDER=classic.)  The cell travels in ProjPx: 112 VGPRs (116 with the masks read, and with DEPTH16's stride constants), four waves per SIMD.
 // The pipeline is unrolled by two with the buffers swapping roles, so that the rotation cur <- nxt, s1 <- s2 costs no
 // register copies.  Reading the loop's s_waitcnt's in the ISA is part of maintaining this code
 // (profiles/steporder_isa_stats.txt): a short-circuit `&&` around a load, a u8 -> f32 conversion next to its load, a
@@ -530,34 +566,38 @@ __global__ void __launch_bounds__(256)
 // cost a drain of the pipeline per pixel before they were found.
 // The first two source records do not depend on the pose: the callers issue them (pixel_source_at) BEFORE they wait
 // for the pose of the iteration, so those loads are in flight during the head.
+// (D16 & D16_SRC: `prev` is the thread's record of pixel k0 - 1, whose row and column this one's follow from; none at k0 = 0)
 template <bool ZMASK, int D16 = 0>
-__device__ __forceinline__ SrcPx pixel_source_at(const LevelDesc& d, uint32_t base, int ppt, int k0) {
+__device__ __forceinline__ SrcPx pixel_source_at(const LevelDesc& d, uint32_t base, int ppt, int k0,
+                                                 const SrcPx* prev = nullptr, const SrcStride* stride = nullptr) {
   const uint32_t i = base + (uint32_t)k0 * 256u;
-  return stage_a<ZMASK, D16>(d, i, (k0 < ppt) && (i < d.src_n));
+  return stage_a<ZMASK, D16>(d, i, (k0 < ppt) && (i < d.src_n), prev, stride);
 }
-template <bool ZMASK, int D16 = 0, bool CLASSIC = false>
+template <bool ZMASK, int D16 = 0, bool CLASSIC = false, bool SHORT = false>
 __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, const Pose& T, uint32_t base, int ppt,
                                            const SrcPx& s0, SrcPx sa, float (&acc)[GN_PARTIAL]) {
   const uint32_t mw = d.tw + 2;
   const float twf = (float)d.tw, thf = (float)d.th;
   BackProj2 bp{};
-  if (D16 & D16_SRC) bp.src = make_backproj(d.src_bp);
-  if (D16 & D16_TGT) bp.tgt = make_backproj(d.tgt_bp);
+  if (D16 & D16_SRC) bp.src = make_backproj<SHORT>(d.src_bp, d.src_rcp_f);
+  if (D16 & D16_TGT) bp.tgt = make_backproj<SHORT>(d.tgt_bp, d.tgt_rcp_f);
+  SrcStride stride{};
+  if (D16 & D16_SRC) stride = make_src_stride(d.src_w);
   SrcPx sb;
-  ProjPx pa = stage_b<ZMASK, D16, CLASSIC>(d, T, s0, twf, thf, bp), pb;
+  ProjPx pa = stage_b<ZMASK, D16, CLASSIC, SHORT>(d, T, s0, twf, thf, bp), pb;
   uint8_t ia = s0.intensity, ib;
   // one step: `cur` holds the projected pixel k, `s_next` the source record of pixel k+1 (consumed here); leaves the
   // projected pixel k+1 in `nxt` and the source record of pixel k+2 in `s_new`
   auto step = [&](ProjPx& cur, uint8_t cur_i, ProjPx& nxt, uint8_t& nxt_i, const SrcPx& s_next, SrcPx& s_new, int k0) {
-    s_new = pixel_source_at<ZMASK, D16>(d, base, ppt, k0 + 2);  // issue source record k+2
+    s_new = pixel_source_at<ZMASK, D16>(d, base, ppt, k0 + 2, &s_next, &stride);  // issue source record k+2
     if constexpr (!CLASSIC) {
       // (the barriers pin the order A(k+2), B(k+1), C(k): left alone, the scheduler sinks stage B below stage C's wait
       // to shorten live ranges, and the loads of k+1 are requested only when those of k have landed)
       __builtin_amdgcn_sched_barrier(0);
-      nxt = stage_b<ZMASK, D16>(d, T, s_next, twf, thf, bp);      // source record k+1 lands; issue gathers and map cell(k+1)
+      nxt = stage_b<ZMASK, D16, false, SHORT>(d, T, s_next, twf, thf, bp);  // source record k+1 lands; issue gathers and map cell(k+1)
       nxt_i = s_next.intensity;
       __builtin_amdgcn_sched_barrier(0);
-      const MapPx mp = stage_c<ZMASK, D16>(d, gt, cur, mw, bp);   // the loads of k land: the step's one wait for them
+      const MapPx mp = stage_c<ZMASK, D16, false, SHORT>(d, gt, cur, mw, bp);  // the loads of k land: the step's one wait for them
       if (cur.live) {
         const Terms t = stage_d(d, gt, cur, mp, cur_i, mw);
         gn_step(acc, t.rg, t.Jg);  // the geometric term counts even when the colour term is rejected
@@ -568,8 +608,8 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
     // (DEPTH16: otherwise the source depth load takes the register of the gathered depth of k, is issued after that
     // depth is read, and the step starts with vmcnt(0) instead of keeping the source record in flight)
     if (D16) __builtin_amdgcn_sched_barrier(0);
-    const MapPx mp = stage_c<ZMASK, D16, true>(d, gt, cur, mw, bp);  // gathers(k) land; issue map cell(k)
-    nxt = stage_b<ZMASK, D16, true>(d, T, s_next, twf, thf, bp);     // issue gathers(k+1)
+    const MapPx mp = stage_c<ZMASK, D16, true, SHORT>(d, gt, cur, mw, bp);  // gathers(k) land; issue map cell(k)
+    nxt = stage_b<ZMASK, D16, true, SHORT>(d, T, s_next, twf, thf, bp);     // issue gathers(k+1)
     nxt_i = s_next.intensity;
     if (cur.live) {
       const Terms t = stage_d(d, gt, cur, mp, cur_i, mw);
@@ -593,7 +633,9 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
 // the points are rebuilt, in straight-line code (backproject_px_proven), from the u16 depth
 // planes (D16_SIDES: the target's, and the source's unless A3D_ICP_DEPTH16_SRC=0) instead of read.
 // CLASSIC (diagnostics build only): the step order of pixel_pass before B(k+1) moved ahead of C(k), as a cross-check.
-template <bool ZMASK, bool DEPTH16, bool CLASSIC = false>
+// SHORT (with DEPTH16): every focal length of the batch's level-0 images passes short_division_proven too, and the
+// rebuilt points divide by them in three operations (div_short) instead of five.
+template <bool ZMASK, bool DEPTH16, bool CLASSIC = false, bool SHORT = false>
 __global__ void __launch_bounds__(256, 1)
     image_icp_head_kernel(const LevelDesc* __restrict__ descs, const JobState* __restrict__ states_in,
                           JobState* __restrict__ states_out, Gates gt, const float* __restrict__ partials_in,
@@ -618,7 +660,9 @@ __global__ void __launch_bounds__(256, 1)
   const int ppt = (int)d.ppt;
   const uint32_t base = tile * (256u * (uint32_t)ppt) + threadIdx.x;
   constexpr int D16 = DEPTH16 ? D16_SIDES : 0;
-  const SrcPx s0 = pixel_source_at<ZMASK, D16>(d, base, ppt, 0), s1 = pixel_source_at<ZMASK, D16>(d, base, ppt, 1);
+  SrcStride stride{};
+  if (D16 & D16_SRC) stride = make_src_stride(d.src_w);
+  const SrcPx s0 = pixel_source_at<ZMASK, D16>(d, base, ppt, 0), s1 = pixel_source_at<ZMASK, D16>(d, base, ppt, 1, &s0, &stride);
   A3D_HEAD_STAMP(1);  // descriptor loaded, first source pixels requested
   head_advance(states_in + pair, tile == 0 ? states_out + pair : nullptr, partials_in + (size_t)pair * job_stride, head,
                pair, s_state, tile == 0);
@@ -626,7 +670,7 @@ __global__ void __launch_bounds__(256, 1)
   if ((int)s_state[15] == A3D_OK) {  // a failed job stays frozen: its blocks contribute nothing
     auto uni = [&](int k) { return __uint_as_float(__builtin_amdgcn_readfirstlane(s_state[k])); };
     const Pose T{{uni(0), uni(1), uni(2)}, {uni(3), uni(4), uni(5), uni(6)}};
-    pixel_pass<ZMASK, D16, CLASSIC>(d, gt, T, base, ppt, s0, s1, acc);
+    pixel_pass<ZMASK, D16, CLASSIC, SHORT>(d, gt, T, base, ppt, s0, s1, acc);
   }
   A3D_HEAD_STAMP(3);  // pixel pass done
   block_reduce_store<GN_PARTIAL, false>(acc, partials_out + (size_t)pair * job_stride + (size_t)tile * GN_PARTIAL);
@@ -1183,6 +1227,8 @@ struct a3d_multiscale_batch {
   bool zmask = false;
   // and every level-0 image carries its depth plane (points_from_depth): level 0 rebuilds the points from it (DEPTH16)
   bool depth16 = false;
+  // and every focal length of those images passes short_division_proven: the level-0 kernel divides by them through div_short
+  bool short_div = false;
   // Pair groups launched on separate streams: one group's launch ramp and head overlap the other groups' streaming
   // (pairs are independent, so the groups never synchronise until the final read-out).
   uint32_t n_streams = 1;
@@ -1225,6 +1271,18 @@ struct a3d_multiscale_batch {
 
 namespace {
 
+// short_division_proven(f) (devmath.hpp), swept once per focal length and context.
+bool short_division_cached(a3d_context* ctx, float f) {
+  uint32_t key;
+  memcpy(&key, &f, 4);
+  std::lock_guard<std::mutex> lock(ctx->short_div_mutex);
+  for (const auto& kv : ctx->short_div_verdicts)
+    if (kv.first == key) return kv.second;
+  const bool ok = short_division_proven(f);
+  ctx->short_div_verdicts.emplace_back(key, ok);
+  return ok;
+}
+
 a3d_status fill_desc(const a3d_device_image* target, const a3d_device_image* source, LevelDesc* d) {
   A3D_REQUIRE(target && source, A3D_INVALID_PARAMETER, "null image handle");
   // the reference `expect`s these three (image_icp.rs:44-57)
@@ -1251,6 +1309,13 @@ a3d_status fill_desc(const a3d_device_image* target, const a3d_device_image* sou
   };
   const bool from_depth = proven(target) && proven(source);
   if (from_depth) d->flags |= 2u;
+  // ... and in three operations per quotient where the exhaustive sweep passes for all four focal lengths (one sweep per
+  // camera and context: short_division_cached)
+  if (from_depth && short_division_cached(target->ctx, target->bp_fx) && short_division_cached(target->ctx, target->bp_fy) &&
+      short_division_cached(target->ctx, source->bp_fx) && short_division_cached(target->ctx, source->bp_fy))
+    d->flags |= 4u;
+  d->src_rcp_f[0] = 1.0f / source->bp_fx, d->src_rcp_f[1] = 1.0f / source->bp_fy;
+  d->tgt_rcp_f[0] = 1.0f / target->bp_fx, d->tgt_rcp_f[1] = 1.0f / target->bp_fy;
   d->src_depth = from_depth ? source->depth16 : nullptr;
   d->tgt_depth = from_depth ? target->depth16 : nullptr;
   const float sbp[5] = {source->bp_fx, source->bp_fy, source->bp_cx, source->bp_cy, source->depth_scale};
@@ -1425,7 +1490,10 @@ a3d_status launch_head_kernel(a3d_multiscale_batch* b, uint32_t level, uint32_t 
     return A3D_OK;
   }
 #endif
-  if (b->depth16 && level == 0)
+  if (b->depth16 && level == 0 && b->short_div)
+    hipLaunchKernelGGL((image_icp_head_kernel<true, true, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
+                       st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+  else if (b->depth16 && level == 0)
     hipLaunchKernelGGL((image_icp_head_kernel<true, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
                        st_out, b->gates[level], part_in, part_out, job_stride, prev);
   else if (b->zmask)
@@ -1458,6 +1526,11 @@ a3d_status batch_commit_descs(a3d_multiscale_batch* b) {
     const LevelDesc& dsc = b->h_descs[p];
     b->depth16 = (dsc.flags & 2u) && dsc.src_n <= (1u << 22);
   }
+  // the short division by the focal lengths: one more per-launch choice with the same rule (the diagnostics build's
+  // A3D_ICP_SHORT_DIV=0 keeps div_by)
+  const char* senv = A3D_DIAG_ENV("A3D_ICP_SHORT_DIV");
+  b->short_div = b->depth16 && !(senv && atoi(senv) == 0);
+  for (uint32_t p = 0; p < P && b->short_div; ++p) b->short_div = (b->h_descs[p].flags & 4u) != 0;
   b->partials_half = max_partials;  // floats per buffer: the launches alternate between two
   if (b->partials_capacity < 2 * max_partials) {  // grow-only: a reused engine keeps its buffer
     if (b->d_partials) A3D_HIP_TRY(hipFree(b->d_partials));

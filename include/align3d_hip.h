@@ -367,6 +367,12 @@ a3d_status a3d_range_image_download_depth16(a3d_device_image* image, uint16_t* o
  * depth scale} in straight-line code: the host proof the alignment applies to every level-0 image before it takes its
  * depth plane (1 = proven, 0 = its points are read).  No device work.  Test hook. */
 a3d_status a3d_backproject_proven(uint32_t width, uint32_t height, const float backproject[5], int32_t* out_proven);
+/* Whether that kernel may also divide by the image's two focal lengths in three operations (q = a y, r = fma(-f, q, a),
+ * q + r y with y = RN(1 / f)) instead of five: a3d_backproject_proven and, for fx and for fy, the exhaustive sweep over
+ * the 2^23 mantissas of the numerator that the alignment runs once per focal length and context (1 = every quotient is
+ * the IEEE one).  Tens of milliseconds per focal length, no device work.  Test hook. */
+a3d_status a3d_backproject_short_division_proven(uint32_t width, uint32_t height, const float backproject[5],
+                                                 int32_t* out_proven);
 /* The dot-product cut that stands in for the reference's normal-angle gate: a correspondence whose dot product d
  * satisfies -1 <= d <= *out is rejected, which is |acos(d)| > thr when `strict` (point-cloud ICP) and |acos(d)| >= thr
  * otherwise (image ICP).  The host bisection the ICP launches use.  No device work.  Test hook. */
