@@ -765,6 +765,201 @@ class DevicePointCloud:
             return out[0]
         return (out[0][0],) + tuple(x[0] for x in out[1:])
 
+    @staticmethod
+    def _per_cloud_u32(value, n, what):
+        """A scalar or one entry per cloud as a (c_uint32 * n) array."""
+        values = [value] * n if np.isscalar(value) else list(value)
+        if len(values) != n:
+            raise _abi.InvalidParameter(f"{what}: {n} clouds but {len(values)} bounds")
+        for v in values:
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise _abi.InvalidParameter(f"{what}: a bound must fit 32 unsigned bits (got {v})")
+        return (C.c_uint32 * n)(*[int(v) for v in values])
+
+    @staticmethod
+    def select_many(clouds, values, lo=1, hi=0xFFFFFFFF, return_index=False):
+        """[c.select(v, lo, hi) for c, v in zip(clouds, values)] as new resident clouds of one context, in ONE call whose
+        launch count does not depend on the number of clouds (a3d_point_clouds_select_device).  values: one entry per
+        cloud, a host array of len() booleans or unsigned integers (uploaded as u32) or a device pointer to len() u32
+        (ctypes.c_void_p, taken as it is); lo, hi: one number for all clouds or one per cloud.  Returns the clouds, or
+        (clouds, [uint32 host index arrays]) with return_index=True."""
+        clouds, values = list(clouds), list(values)
+        if len(values) != len(clouds):
+            raise _abi.InvalidParameter(f"select: {len(clouds)} clouds but {len(values)} value arrays")
+        if not clouds:
+            return ([], []) if return_index else []
+        clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "select")
+        n = len(clouds)
+        lo, hi = DevicePointCloud._per_cloud_u32(lo, n, "select"), DevicePointCloud._per_cloud_u32(hi, n, "select")
+        outs, d_index, uploaded, d_values = [], [], [], []
+        try:
+            for c, v in zip(clouds, values):
+                if isinstance(v, (C.c_void_p, int)):
+                    d_values.append(v if isinstance(v, C.c_void_p) else C.c_void_p(v))
+                    continue
+                v = np.asarray(v)
+                if v.ndim != 1 or len(v) != c.n:
+                    raise _abi.InvalidParameter(f"select: a cloud of {c.n} rows but values of shape {v.shape}")
+                if v.dtype != np.bool_ and not (np.issubdtype(v.dtype, np.integer) and (v >= 0).all() and (v <= 0xFFFFFFFF).all()):
+                    raise _abi.InvalidParameter(f"select: values are booleans or unsigned 32-bit integers (got {v.dtype})")
+                uploaded.append(ctx.to_device(np.ascontiguousarray(v, np.uint32)) if c.n else ctx.malloc(4))
+                d_values.append(uploaded[-1])
+            for c in clouds:
+                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
+                if return_index:
+                    d_index.append(ctx.malloc(max(1, c.n) * 4))
+            lens = (C.c_uint64 * n)()
+            colours = any(c.d_colors is not None for c in clouds)
+            _abi.check(
+                ctx.lib.a3d_point_clouds_select_device(
+                    ctx.handle, DevicePointCloud._views(clouds), DevicePointCloud._colors_array(clouds) if colours else None,
+                    n, (C.c_void_p * n)(*d_values), lo, hi, (C.c_void_p * n)(*[x.d_points for x in outs]),
+                    (C.c_void_p * n)(*[x.d_normals for x in outs]), DevicePointCloud._colors_array(outs) if colours else None,
+                    (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens),
+                "a3d_point_clouds_select_device",
+            )
+            for x, k in zip(outs, lens):
+                x.n = int(k)
+            index = None
+            if return_index:
+                index = [ctx.to_host(d, np.empty(x.n, np.uint32)) if x.n else np.empty(0, np.uint32)
+                         for d, x in zip(d_index, outs)]
+        except BaseException:
+            for x in outs:
+                x.free()
+            raise
+        finally:
+            for d in d_index + uploaded:
+                ctx.free(d)
+        return (outs, index) if return_index else outs
+
+    def select(self, values_or_mask, lo=1, hi=0xFFFFFFFF, return_index=False):
+        """The rows p of this cloud with lo <= values[p] <= hi, in input order, as a new resident cloud
+        (a3d_point_clouds_select_device): points, normals and colours copied bit for bit; the coordinates are never looked
+        at.  values_or_mask: a host array of len() booleans (True = 1, so the defaults keep the True rows) or unsigned
+        integers, uploaded as u32, or a device pointer (ctypes.c_void_p) to len() u32, taken as it is.  The result keeps
+        buffers sized for this cloud, like voxel_downsample's.  return_index=True returns (cloud, index): a HOST uint32
+        array, index[k] = the row of this cloud that row k of the result was; strictly increasing."""
+        out = DevicePointCloud.select_many([self], [values_or_mask], lo, hi, return_index)
+        return (out[0][0], out[1][0]) if return_index else out[0]
+
+    @staticmethod
+    def neighbor_distances_many(clouds, radius, k):
+        """neighbor_distances for resident clouds of one context in ONE call and one wait
+        (a3d_point_clouds_knn_distance_device).  Returns ([d_counts], [d_qsum], [stats]): per cloud a device buffer of
+        len() u32 neighbour counts, a device buffer of len() u32 distance sums (None when k == 0), and the tuple
+        (m, sum Q, sum Q^2) of Python ints.  The buffers are RESIDENT: they go to select() as they are, and the caller
+        releases each with the context's free()."""
+        clouds = list(clouds)
+        if not clouds:
+            return [], [], []
+        clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "neighbor_distances")
+        n, k = len(clouds), int(k)
+        if k < 0:
+            raise _abi.InvalidParameter(f"neighbor_distances: k is at least 0 (got {k})")
+        d_counts, d_qsum = [], []
+        try:
+            for c in clouds:
+                d_counts.append(ctx.malloc(max(1, c.n) * 4))
+                if k:
+                    d_qsum.append(ctx.malloc(max(1, c.n) * 4))
+            stats = (C.c_uint64 * (4 * n))()
+            _abi.check(
+                ctx.lib.a3d_point_clouds_knn_distance_device(
+                    ctx.handle, DevicePointCloud._views(clouds), n, float(radius), k, (C.c_void_p * n)(*d_counts),
+                    (C.c_void_p * n)(*d_qsum) if k else None, stats, None),
+                "a3d_point_clouds_knn_distance_device",
+            )
+        except BaseException:
+            for d in d_counts + d_qsum:
+                ctx.free(d)
+            raise
+        tuples = [(int(stats[4 * i]), int(stats[4 * i + 1]), int(stats[4 * i + 2]) + (int(stats[4 * i + 3]) << 32))
+                  for i in range(n)]
+        return d_counts, d_qsum if k else [None] * n, tuples
+
+    def neighbor_distances(self, radius, k):
+        """Per row of this cloud, resident: the number N of rows within `radius` (the row itself included; the cells of
+        a grid of pitch `radius` around the row's own, then the ball: estimate_normals' neighbours and its counts, bit for
+        bit), and, for k > 0, Q = the sum of the distances to the k nearest OTHER rows within `radius`, each rounded to a
+        lattice of radius / 32768 (0xFFFFFFFF for a row with fewer than k others, or with a coordinate that is not finite
+        or beyond 2^20 cells).  0 <= k <= 32.  Returns (d_counts, d_qsum, (m, sum Q, sum Q^2)): two device buffers of
+        len() u32 (d_qsum is None when k == 0; release them with the context's free()) and the integer sums over the m
+        rows that have a Q, the same on every run and for every order of the rows."""
+        counts, qsum, stats = DevicePointCloud.neighbor_distances_many([self], radius, k)
+        return counts[0], qsum[0], stats[0]
+
+    @staticmethod
+    def knn_distance_threshold(stats, std_ratio):
+        """The largest Q the statistical filter keeps (a3d_knn_distance_threshold; host only): floor(mean +
+        std_ratio * sample standard deviation) of the Q that neighbor_distances summed into stats = (m, sum Q, sum Q^2)."""
+        m, total, squares = (int(x) for x in stats)
+        if min(m, total, squares) < 0 or max(m, total) >= 1 << 64 or squares >= 1 << 96:
+            raise _abi.InvalidParameter("knn_distance_threshold: statistics that no call can have produced")
+        words = (C.c_uint64 * 4)(m, total, squares & 0xFFFFFFFF, squares >> 32)
+        out = C.c_uint32()
+        _abi.check(_abi.load_library().a3d_knn_distance_threshold(words, float(std_ratio), C.byref(out)),
+                   "a3d_knn_distance_threshold")
+        return int(out.value)
+
+    @staticmethod
+    def remove_radius_outliers_many(clouds, radius, min_neighbors, return_index=False):
+        """[c.remove_radius_outliers(radius, min_neighbors) for c in clouds] for resident clouds of one context: one knn
+        call (k = 0) and one select call, whatever the number of clouds."""
+        clouds = list(clouds)
+        if not clouds:
+            return ([], []) if return_index else []
+        ctx = clouds[0].ctx
+        counts, _, _ = DevicePointCloud.neighbor_distances_many(clouds, radius, 0)
+        try:
+            return DevicePointCloud.select_many(clouds, counts, int(min_neighbors), 0xFFFFFFFF, return_index)
+        finally:
+            for d in counts:
+                ctx.free(d)
+
+    def remove_radius_outliers(self, radius, min_neighbors, return_index=False):
+        """This cloud without the rows that have fewer than `min_neighbors` rows within `radius`, THE ROW ITSELF COUNTED,
+        as a new resident cloud in input order with normals and colours when this cloud has them: the k = 0 call of
+        neighbor_distances followed by select(counts, lo=min_neighbors).  That rule is the definition.  PCL's
+        RadiusOutlierRemoval(min_neighbors_in_radius = n) keeps a point with at least n neighbours, itself included,
+        as here; Open3D's remove_radius_outlier(nb_points, radius) counts the point itself as well and keeps it when the
+        count EXCEEDS nb_points, so it corresponds to min_neighbors = nb_points + 1.  Neighbours are estimate_normals'
+        (the 27 cells of a grid of pitch `radius`, then the ball); a row with a coordinate that is not finite or beyond
+        2^20 cells has no neighbours and goes for every min_neighbors >= 1.  return_index as in select()."""
+        out = DevicePointCloud.remove_radius_outliers_many([self], radius, min_neighbors, return_index)
+        return (out[0][0], out[1][0]) if return_index else out[0]
+
+    @staticmethod
+    def remove_statistical_outliers_many(clouds, radius, k, std_ratio, return_index=False):
+        """[c.remove_statistical_outliers(radius, k, std_ratio) for c in clouds] for resident clouds of one context, each
+        with its own mean and deviation: one knn call, the thresholds on the host, one select call."""
+        clouds = list(clouds)
+        if not clouds:
+            return ([], []) if return_index else []
+        if int(k) < 1:
+            raise _abi.InvalidParameter(f"remove_statistical_outliers: k is at least 1 (got {k})")
+        ctx = clouds[0].ctx
+        counts, qsum, stats = DevicePointCloud.neighbor_distances_many(clouds, radius, k)
+        try:
+            hi = [DevicePointCloud.knn_distance_threshold(s, std_ratio) for s in stats]
+            return DevicePointCloud.select_many(clouds, qsum, 0, hi, return_index)
+        finally:
+            for d in counts + qsum:
+                ctx.free(d)
+
+    def remove_statistical_outliers(self, radius, k, std_ratio, return_index=False):
+        """This cloud without the rows whose mean distance to their k nearest other rows is more than `std_ratio` sample
+        standard deviations above the cloud's mean of that figure (PCL StatisticalOutlierRemoval(mean_k, stddev_mul),
+        Open3D remove_statistical_outlier(nb_neighbors, std_ratio)), as a new resident cloud in input order with normals
+        and colours when this cloud has them: neighbor_distances(radius, k), knn_distance_threshold, select(qsum, 0, T).
+        The k nearest are searched WITHIN `radius` only: PCL and Open3D search without a bound, here the bound keeps the
+        search inside the 27 cells around the row, and a row with fewer than k others within `radius` is an outlier by
+        rule and takes no part in the mean and the deviation.  Choose `radius` a few times the spacing the k-th neighbour
+        of an inlier has.  1 <= k <= 32.  All decisions are on integers (distances on a lattice of radius / 32768), so
+        the result does not depend on the order of the rows.  return_index as in select()."""
+        out = DevicePointCloud.remove_statistical_outliers_many([self], radius, k, std_ratio, return_index)
+        return (out[0][0], out[1][0]) if return_index else out[0]
+
     def render(self, camera, camera_to_world=None, radius=0.0, return_index=False):
         """What a pinhole camera sees of this cloud, as a new DeviceRangeImage (a3d_point_cloud_render_device): the
         inverse of from_range_image, PinholeCamera::project_to_image (src/camera.rs:177-202) over every point.  `camera`

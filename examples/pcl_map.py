@@ -2,7 +2,7 @@
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
         [--voxel V [--mean] [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
-        [--estimate-normals R] [--out map.npy]
+        [--estimate-normals R] [--radius-outliers R N] [--stat-outliers R K A] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -36,7 +36,12 @@ from a sensor without a pixel grid: every frame's cloud drops its image normals 
 points within R metres (DevicePointCloud.estimate_normals_many, the viewpoint at the frame's camera) before anything is
 aligned; with --render-track the model that is rendered is then the map's extract with its normals refreshed from the
 map's own neighbourhood (estimate_normals(3 V, orient="normals"): one raw sensor normal per cell otherwise), and the
-trajectory errors printed are those of this variant.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+trajectory errors printed are those of this variant.  --radius-outliers R N and --stat-outliers R K A clean each frame's
+cloud before it goes into the map, whichever route builds it (the odometry still aligns the full clouds): the first drops
+the rows with fewer than N rows within R metres, themselves counted (DevicePointCloud.remove_radius_outliers_many), the
+second the rows whose mean distance to their K nearest others within R lies more than A standard deviations above the
+frame's mean (remove_statistical_outliers_many); with both, the radius filter runs first.  The flying pixels at depth edges
+and isolated returns then never own a cell of the map.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -69,6 +74,11 @@ ap.add_argument("--colors", action="store_true", help="carry the frames' RGB col
 ap.add_argument("--estimate-normals", type=float, default=None, metavar="R",
                 help="replace every frame's image normals by normals estimated from the cloud itself within R metres "
                      "(with --render-track the rendered model's normals are refreshed too, within 3 V whatever R is)")
+ap.add_argument("--radius-outliers", nargs=2, type=float, default=None, metavar=("R", "N"),
+                help="before a frame's cloud goes into the map, drop its rows with fewer than N rows within R metres")
+ap.add_argument("--stat-outliers", nargs=3, type=float, default=None, metavar=("R", "K", "A"),
+                help="before a frame's cloud goes into the map, drop its rows whose mean distance to their K nearest others "
+                     "within R metres is more than A standard deviations above the frame's mean")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
 args = ap.parse_args()
 if args.online and not args.voxel:
@@ -116,6 +126,21 @@ for k, (now_to_previous, st) in enumerate(zip(poses, status)):
         traj.accumulate(now_to_previous, float(k + 1))
     camera_to_world.append(traj.current_camera_to_world())
 
+# what goes into the map: the frames' clouds, cleaned if asked for (one knn call and one select call per filter, all frames)
+map_clouds = clouds
+for name, spec in (("radius", args.radius_outliers), ("statistical", args.stat_outliers)):
+    if spec is None:
+        continue
+    if name == "radius":
+        cleaned = DevicePointCloud.remove_radius_outliers_many(map_clouds, spec[0], int(spec[1]))
+    else:
+        cleaned = DevicePointCloud.remove_statistical_outliers_many(map_clouds, spec[0], int(spec[1]), spec[2])
+    print(f"{name} outlier filter {spec}: {sum(c.len() for c in map_clouds)} rows -> {sum(c.len() for c in cleaned)}")
+    if map_clouds is not clouds:
+        for c in map_clouds:
+            c.free()
+    map_clouds = cleaned
+
 
 mean_map = None  # --mean: the map of cell means, beside the nearest-point map
 
@@ -123,7 +148,7 @@ mean_map = None  # --mean: the map of cell means, beside the nearest-point map
 def thinned_by_batch():
     """(points offered, thinned map): all frames in one coordinate system, then one point per cell."""
     global mean_map
-    full = DevicePointCloud.merge(clouds, camera_to_world)
+    full = DevicePointCloud.merge(map_clouds, camera_to_world)
     if args.online and args.mean:  # --check-batch of a live map of means: the batch call it must equal
         thin = full.voxel_downsample(args.voxel, mode="mean")
     else:
@@ -136,12 +161,12 @@ def thinned_by_batch():
 
 
 if args.online:
-    online = DeviceVoxelMap(ctx, args.voxel, normals=clouds[0].d_normals is not None, colors=args.colors,
+    online = DeviceVoxelMap(ctx, args.voxel, normals=map_clouds[0].d_normals is not None, colors=args.colors,
                             mode="mean" if args.mean else "nearest")
     offered = 0
     starts = collections.deque()  # --window-frames: the first sequence number of each kept frame, in the map's numbering
     corrected = []  # --render-track: the poses the frames went in under
-    for k, (cloud, pose) in enumerate(zip(clouds, camera_to_world)):  # what a live caller does as each frame arrives
+    for k, (cloud, pose) in enumerate(zip(map_clouds, camera_to_world)):  # what a live caller does as each frame arrives
         if args.render_track:
             if k > 0:
                 pose = corrected[-1] * poses[k - 1] if status[k - 1] == 0 else corrected[-1]  # the odometry's prediction
@@ -203,7 +228,7 @@ if args.online:
 elif args.voxel:
     offered, world_map = thinned_by_batch()
 else:
-    world_map = DevicePointCloud.merge(clouds, camera_to_world)  # the last step: all frames in one coordinate system
+    world_map = DevicePointCloud.merge(map_clouds, camera_to_world)  # the last step: all frames in one coordinate system
 if args.voxel:
     print(f"voxel {args.voxel}{' (a live map of cell means)' if args.online and args.mean else ''}: {offered} points -> "
           f"{world_map.len()}")
@@ -238,6 +263,7 @@ if args.out:
         np.save(colors_out, world_map.download_colors())
         print("wrote", colors_out)
 batch.free()
-for x in [world_map] + ([mean_map] if mean_map is not None else []) + clouds + images + coarser:
+for x in [world_map] + ([mean_map] if mean_map is not None else []) + clouds + images + coarser + (
+        map_clouds if map_clouds is not clouds else []):
     x.free()
 ctx.close()

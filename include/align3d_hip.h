@@ -672,6 +672,72 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
                                                     float* const* d_out_curvature, uint32_t* const* d_out_counts,
                                                     uint64_t* out_valid, uint64_t* out_dropped);
 
+/* Outlier removal for resident clouds: the three entries below.  The radius filter (PCL RadiusOutlierRemoval, Open3D
+ * remove_radius_outlier) is the k = 0 form of the knn entry followed by a select on its counts with lo = min_neighbors;
+ * the statistical filter (StatisticalOutlierRemoval, remove_statistical_outlier) is the knn entry, the threshold entry
+ * and a select on qsum with lo = 0, hi = T.
+ *
+ * Keep rows by value, in input order: row p of cloud i is kept iff lo[i] <= d_values[i][p] <= hi[i] (lo > hi keeps
+ * nothing).  n resident clouds, each exactly as if it were passed alone, in a number of launches that does not depend on n
+ * (one upload, two launches); host-synchronous like the entries above.  Kept rows go out in input order, point, normal
+ * and colour copied bit for bit; d_out_index holds the input row of each kept row and is strictly increasing.  The
+ * coordinates are never looked at: a NaN row with a kept value is kept.  d_values: one device array of len_i u32 per
+ * cloud; lo, hi: [n] u32 in host memory.  The outputs, their NULL forms, capacities, A3D_MISSING_FIELD for a normals or
+ * colour output of a cloud that lacks the field, and the colour buffers' freedom of alignment are those of
+ * a3d_point_clouds_voxel_downsample_rgb_device: if any cloud's rows do not fit its capacity the call returns
+ * A3D_INVALID_PARAMETER with every count in out_lens and NOTHING written to any output.
+ * Decided on the host before anything is launched (nothing is touched): n == 0 is A3D_OK; a NULL ctx, d_clouds, d_values,
+ * lo, hi, d_out_points, capacities or out_lens, a cloud of 2^32 points or more (or within one tile, < 2^21 points, of
+ * it), NULL points, values or output points of a non-empty cloud, any overlap of an output (its first min(len_i,
+ * capacities[i]) elements) with an input (the values are one) or another output — there is no in-place form — are
+ * A3D_INVALID_PARAMETER.  A cloud with len == 0 may have null pointers and yields out_lens[i] = 0.
+ * Scratch memory (context-owned, grow-only, shared with the calls above): len_i / 8 bytes of flags, 4 bytes per 1024
+ * points and 104 bytes per cloud. */
+a3d_status a3d_point_clouds_select_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds,
+                                          const uint8_t* const* d_colors, uint64_t n, const uint32_t* const* d_values,
+                                          const uint32_t* lo, const uint32_t* hi, float* const* d_out_points,
+                                          float* const* d_out_normals, uint8_t* const* d_out_colors,
+                                          uint32_t* const* d_out_index, const uint64_t* capacities, uint64_t* out_lens);
+
+/* Neighbour count and sum of the k nearest neighbour distances per row of n resident clouds, each exactly as if it were
+ * passed alone, in a number of launches that does not depend on n (one upload, one fill, four launches);
+ * host-synchronous.  The rule, every f32 operation rounded on its own, with r2 = radius * radius and s = 32768.0f / radius
+ * computed on the host:
+ *   1. grid and 2. neighbours: steps 1 and 2 of a3d_point_clouds_estimate_normals_device, word for word (pitch radius;
+ *      dropped rows are nobody's neighbour; cell coordinates differ by at most 1; d2 = (d_x*d_x + d_y*d_y) + d_z*d_z <= r2);
+ *   3. counts[p] = N, the neighbours of row p, itself included, 0 for a dropped row: bit for bit the d_out_counts of
+ *      a3d_point_clouds_estimate_normals_device at the same radius;
+ *   4. the OTHERS of row p are its neighbours with a different row index (a duplicate point is an other at distance 0);
+ *      for each other, t = (uint32) rintf(sqrtf(d2) * s), which is non-decreasing in d2;
+ *   5. qsum[p] = Q = the sum of the k smallest t, or 0xFFFFFFFF if the row is dropped or has fewer than k others; the
+ *      multiset of the k smallest values is unique, so Q does not depend on the order in which candidates are met;
+ *   6. out_stats[i] = {m, sum Q, sum (Q*Q & 0xFFFFFFFF), sum (Q*Q >> 32)} over the m rows of cloud i whose Q is not
+ *      0xFFFFFFFF: u64 integer sums, the same bits on every run and under any permutation of the rows.  r2 is at most
+ *      twice the exact square of the radius (a denormal product), so t <= 46342 < 2^16, Q < 2^21 and Q*Q < 2^42 for k <= 32;
+ *      with len < 2^32 the four sums stay below 2^32, 2^53, 2^64 and 2^42: none can overflow.
+ * 0 <= k <= 32.  k == 0 is the count-only form: no distances are computed, d_out_qsum is not read and the statistics are
+ * zeros.  d_out_counts: NULL, or per cloud NULL / [len_i] u32.  d_out_qsum: NULL only if k == 0, else per cloud [len_i] u32.
+ * out_stats: [n][4] u64 in host memory, NULL ok.  out_dropped[i] (NULL ok) = dropped rows of cloud i.
+ * Decided on the host before anything is launched (nothing is touched): n == 0 is A3D_OK; a NULL ctx or d_clouds, a radius
+ * that is not finite or <= 0 (or so small that its square is 0 in f32), k > 32, a NULL d_out_qsum (or entry of a non-empty
+ * cloud) while k > 0, a cloud of 2^32 points or more (or within one tile, < 2^21 points, of it), NULL points of a non-empty
+ * cloud, any overlap of an output with an input or another output are A3D_INVALID_PARAMETER.  A cloud with len == 0 may
+ * have null pointers and yields zeros.
+ * Scratch memory (context-owned, grow-only, shared with the calls above): that of the normals entry (32 to 64 bytes per
+ * point of hash table, 16 bytes per point for the cell-ordered copy) and 64 bytes per cloud. */
+a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
+                                                float radius, uint32_t k, uint32_t* const* d_out_counts,
+                                                uint32_t* const* d_out_qsum, uint64_t* out_stats, uint64_t* out_dropped);
+
+/* The statistical filter's threshold from one cloud's out_stats of the entry above; host only, no GPU call.  With
+ * {m, SQ, lo, hi} = stats and SQ2 = lo + hi * 2^32:  mu = (double)SQ / (double)m;  num = m * SQ2 - SQ * SQ, exact in 128
+ * bits (>= 0 and < 2^107);  var = (double)num / ((double)m * (double)(m - 1)), the sample variance as PCL uses it, 0 when
+ * m < 2;  T = floor(mu + std_ratio * sqrt(var)), clamped to [0, 0xFFFFFFFE] so that the 0xFFFFFFFF of a row without k
+ * others never passes.  m == 0 gives 0.  The filter keeps the rows with 0 <= qsum <= T.  A NULL argument, a std_ratio
+ * that is not finite or negative, and statistics outside the bounds stated above (or with num < 0) are
+ * A3D_INVALID_PARAMETER. */
+a3d_status a3d_knn_distance_threshold(const uint64_t stats[4], double std_ratio, uint32_t* out_hi);
+
 /* A persistent voxel map: the hash table of the downsample above kept between calls, so that resident clouds go in frame
  * by frame (a3d_voxel_map_insert) instead of merge + downsample of the whole map per frame.  The contract:
  *   After any sequence of inserts, the map's contents equal a3d_point_clouds_merge_device(all inserted clouds under their
