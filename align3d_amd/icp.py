@@ -960,6 +960,110 @@ class DevicePointCloud:
         out = DevicePointCloud.remove_statistical_outliers_many([self], radius, k, std_ratio, return_index)
         return (out[0][0], out[1][0]) if return_index else out[0]
 
+    @staticmethod
+    def _cluster_call(clouds, radius, min_points, row_sizes):
+        """One a3d_point_clouds_cluster_device over resident clouds of one context.  Returns (ctx, [d_labels],
+        [d_row_sizes] or None, [sizes], [roots]); the device buffers are the caller's to free."""
+        clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "cluster")
+        n, m = len(clouds), int(min_points)
+        if not 1 <= m <= 0xFFFFFFFF:
+            raise _abi.InvalidParameter(f"cluster: min_points is at least 1 (got {min_points})")
+        d_labels, d_rows, d_sizes, d_roots = [], [], [], []
+        try:
+            for c in clouds:
+                for group in (d_labels, d_sizes, d_roots) + ((d_rows,) if row_sizes else ()):
+                    group.append(ctx.malloc(max(1, c.n) * 4))
+            found = (C.c_uint64 * n)()
+            _abi.check(
+                ctx.lib.a3d_point_clouds_cluster_device(
+                    ctx.handle, DevicePointCloud._views(clouds), n, float(radius), m, (C.c_void_p * n)(*d_labels),
+                    (C.c_void_p * n)(*d_rows) if row_sizes else None, (C.c_void_p * n)(*d_sizes),
+                    (C.c_void_p * n)(*d_roots), found, None, None),
+                "a3d_point_clouds_cluster_device",
+            )
+            sizes = [ctx.to_host(d, np.empty(int(k), np.uint32)) if k else np.empty(0, np.uint32)
+                     for d, k in zip(d_sizes, found)]
+            roots = [ctx.to_host(d, np.empty(int(k), np.uint32)) if k else np.empty(0, np.uint32)
+                     for d, k in zip(d_roots, found)]
+        except BaseException:
+            for d in d_labels + d_rows:
+                ctx.free(d)
+            raise
+        finally:
+            for d in d_sizes + d_roots:
+                ctx.free(d)
+        return ctx, d_labels, d_rows if row_sizes else None, sizes, roots
+
+    @staticmethod
+    def cluster_many(clouds, radius, min_points=1):
+        """cluster for resident clouds of one context in ONE call and one wait (a3d_point_clouds_cluster_device).
+        Returns ([d_labels], [sizes], [roots]): per cloud a RESIDENT buffer of len() u32 labels, and host uint32 arrays of
+        the C cluster sizes and the C root rows.  The label buffers go to select() as they are; the caller releases each
+        with the context's free()."""
+        clouds = list(clouds)
+        if not clouds:
+            return [], [], []
+        _, d_labels, _, sizes, roots = DevicePointCloud._cluster_call(clouds, radius, min_points, False)
+        return d_labels, sizes, roots
+
+    def cluster(self, radius, min_points=1):
+        """Which rows of this cloud belong together: DBSCAN on the device.  Neighbours are estimate_normals' and
+        neighbor_distances' (the 27 cells of a grid of pitch `radius`, then the ball, the row itself counted).  A row with
+        at least `min_points` neighbours is a core row; core rows within `radius` of each other share a cluster; a row
+        that is not core but has a core row within `radius` is a BORDER row and joins the cluster of the NEAREST core row
+        (the lower row on a tie); every other row, and every row with a coordinate that is not finite or beyond 2^20
+        cells, is noise with label 0xFFFFFFFF.  Clusters are numbered 0 ... C-1 by their lowest core row.  Open3D's
+        cluster_dbscan(eps, min_points) takes the same two numbers, counts the point itself too and numbers clusters the
+        same way: core rows get the same labels; a border row within reach of several clusters goes to the first that
+        reaches it there and to the nearest here.  PCL's EuclideanClusterExtraction(tolerance) is min_points = 1 (every
+        row is core, no border rows, no noise but the refused rows); its min / max cluster size is
+        remove_small_clusters().  Returns (d_labels, sizes, roots): a RESIDENT buffer of len() u32 (select(d_labels, c, c)
+        is cluster c, select(d_labels, 0, 0xFFFFFFFE) drops the noise; release it with the context's free()) and host
+        uint32 arrays sizes[C] (border rows included) and roots[C] (strictly increasing).  All decisions are on integers:
+        the same result on every run."""
+        labels, sizes, roots = DevicePointCloud.cluster_many([self], radius, min_points)
+        return labels[0], sizes[0], roots[0]
+
+    @staticmethod
+    def remove_small_clusters_many(clouds, radius, min_points, min_size, max_size=0xFFFFFFFF, return_index=False):
+        """[c.remove_small_clusters(radius, min_points, min_size, max_size) for c in clouds] for resident clouds of one
+        context: one cluster call and one select call, whatever the number of clouds."""
+        clouds = list(clouds)
+        if not clouds:
+            return ([], []) if return_index else []
+        if int(min_size) < 1:
+            raise _abi.InvalidParameter(f"remove_small_clusters: min_size is at least 1 (got {min_size})")
+        ctx, d_labels, d_rows, _, _ = DevicePointCloud._cluster_call(clouds, radius, min_points, True)
+        try:
+            return DevicePointCloud.select_many(clouds, d_rows, int(min_size), int(max_size), return_index)
+        finally:
+            for d in d_labels + d_rows:
+                ctx.free(d)
+
+    def remove_small_clusters(self, radius, min_points, min_size, max_size=0xFFFFFFFF, return_index=False):
+        """This cloud without the noise and without the rows of clusters of fewer than `min_size` or more than `max_size`
+        rows (border rows count), as a new resident cloud in input order with normals and colours when this cloud has
+        them: cluster(radius, min_points) with the size of each row's cluster, then select(row_sizes, min_size,
+        max_size).  min_size >= 1.  With min_points = 1 this is PCL's EuclideanClusterExtraction(tolerance = radius,
+        min_cluster_size, max_cluster_size) with the surviving clusters put back together; with Open3D it is
+        cluster_dbscan(radius, min_points) and a filter on the label counts.  It removes what the radius filter keeps: a
+        floating clump whose points all have neighbours.  return_index as in select()."""
+        out = DevicePointCloud.remove_small_clusters_many([self], radius, min_points, min_size, max_size, return_index)
+        return (out[0][0], out[1][0]) if return_index else out[0]
+
+    def largest_cluster(self, radius, min_points=1, return_index=False):
+        """The cluster of cluster(radius, min_points) with the most rows (border rows count; the lowest label on a tie) as
+        a new resident cloud in input order: one cluster call and one select on the labels.  A cloud without a cluster
+        gives an empty cloud.  return_index as in select()."""
+        d_labels, sizes, _ = self.cluster(radius, min_points)
+        try:
+            if len(sizes) == 0:
+                return self.select(d_labels, 1, 0, return_index)
+            c = int(np.argmax(sizes))  # the first of the largest
+            return self.select(d_labels, c, c, return_index)
+        finally:
+            self.ctx.free(d_labels)
+
     def render(self, camera, camera_to_world=None, radius=0.0, return_index=False):
         """What a pinhole camera sees of this cloud, as a new DeviceRangeImage (a3d_point_cloud_render_device): the
         inverse of from_range_image, PinholeCamera::project_to_image (src/camera.rs:177-202) over every point.  `camera`

@@ -2,7 +2,7 @@
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
         [--voxel V [--mean] [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
-        [--estimate-normals R] [--radius-outliers R N] [--stat-outliers R K A] [--out map.npy]
+        [--estimate-normals R] [--radius-outliers R N] [--stat-outliers R K A] [--clusters R M S] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -41,7 +41,9 @@ cloud before it goes into the map, whichever route builds it (the odometry still
 the rows with fewer than N rows within R metres, themselves counted (DevicePointCloud.remove_radius_outliers_many), the
 second the rows whose mean distance to their K nearest others within R lies more than A standard deviations above the
 frame's mean (remove_statistical_outliers_many); with both, the radius filter runs first.  The flying pixels at depth edges
-and isolated returns then never own a cell of the map.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+and isolated returns then never own a cell of the map.  --clusters R M S runs after them and drops what they keep, the
+floating clumps: the rows that are noise or belong to a cluster of fewer than S rows under DBSCAN with radius R and
+min_points M (DevicePointCloud.remove_small_clusters_many; M = 1 is PCL's Euclidean cluster extraction with a minimum size).  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -79,6 +81,9 @@ ap.add_argument("--radius-outliers", nargs=2, type=float, default=None, metavar=
 ap.add_argument("--stat-outliers", nargs=3, type=float, default=None, metavar=("R", "K", "A"),
                 help="before a frame's cloud goes into the map, drop its rows whose mean distance to their K nearest others "
                      "within R metres is more than A standard deviations above the frame's mean")
+ap.add_argument("--clusters", nargs=3, type=float, default=None, metavar=("R", "M", "S"),
+                help="before a frame's cloud goes into the map, drop the noise and the clusters of fewer than S rows of DBSCAN "
+                     "with radius R metres and min_points M")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
 args = ap.parse_args()
 if args.online and not args.voxel:
@@ -126,15 +131,18 @@ for k, (now_to_previous, st) in enumerate(zip(poses, status)):
         traj.accumulate(now_to_previous, float(k + 1))
     camera_to_world.append(traj.current_camera_to_world())
 
-# what goes into the map: the frames' clouds, cleaned if asked for (one knn call and one select call per filter, all frames)
+# what goes into the map: the frames' clouds, cleaned if asked for (one knn or cluster call and one select call per filter,
+# all frames)
 map_clouds = clouds
-for name, spec in (("radius", args.radius_outliers), ("statistical", args.stat_outliers)):
+for name, spec in (("radius", args.radius_outliers), ("statistical", args.stat_outliers), ("cluster", args.clusters)):
     if spec is None:
         continue
     if name == "radius":
         cleaned = DevicePointCloud.remove_radius_outliers_many(map_clouds, spec[0], int(spec[1]))
-    else:
+    elif name == "statistical":
         cleaned = DevicePointCloud.remove_statistical_outliers_many(map_clouds, spec[0], int(spec[1]), spec[2])
+    else:
+        cleaned = DevicePointCloud.remove_small_clusters_many(map_clouds, spec[0], int(spec[1]), int(spec[2]))
     print(f"{name} outlier filter {spec}: {sum(c.len() for c in map_clouds)} rows -> {sum(c.len() for c in cleaned)}")
     if map_clouds is not clouds:
         for c in map_clouds:

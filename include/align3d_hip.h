@@ -738,6 +738,45 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
  * A3D_INVALID_PARAMETER. */
 a3d_status a3d_knn_distance_threshold(const uint64_t stats[4], double std_ratio, uint32_t* out_hi);
 
+/* Which rows belong together: DBSCAN clusters of n resident clouds, each exactly as if it were passed alone, in a number
+ * of launches that does not depend on n (one upload, one fill, eight launches); host-synchronous.  PCL
+ * EuclideanClusterExtraction(tolerance) is min_points = 1; Open3D cluster_dbscan(eps, min_points) is (radius, min_points).
+ * The rule, every f32 operation rounded on its own, with r2 = radius * radius computed on the host:
+ *   1. grid and neighbours: steps 1 and 2 of a3d_point_clouds_knn_distance_device, word for word (pitch radius; dropped
+ *      rows are nobody's neighbour; cell coordinates differ by at most 1; d2 = (d_x*d_x + d_y*d_y) + d_z*d_z <= r2, the
+ *      same bits seen from either row, so the relation is symmetric);
+ *   2. row p is a CORE row iff it is kept and N_p >= min_points, N_p its neighbours, itself included: bit for bit the
+ *      counts of the knn entry;
+ *   3. two core rows are linked iff they are neighbours; a cluster is a connected component of the core rows under that
+ *      link, and its ROOT is its lowest row;
+ *   4. a kept row that is not core and has a core neighbour is a BORDER row of the cluster of the core neighbour j that
+ *      minimises bits(d2) << 32 | j: the nearest, the lower row on a tie; a border row never links two clusters;
+ *   5. every other row is noise (dropped rows; non-core rows without a core neighbour), label 0xFFFFFFFF;
+ *   6. clusters are numbered 0 ... C-1 by ascending root: labels[p] = the number of row p's cluster, sizes[c] = the rows
+ *      labelled c, border rows included, roots[c] strictly increasing, row_sizes[p] = sizes[labels[p]] and 0 for noise.
+ * min_points = 1 makes every kept row core: Euclidean cluster extraction with tolerance radius.  Core rows get the labels
+ * Open3D gives them for the same neighbour sets (it numbers clusters by their lowest core index too); a border row with
+ * core neighbours in several clusters may land in another of them than Open3D's first-come rule puts it.  Every output is
+ * integers decided on integers or on d2 bits: the same on every run.  Under a permutation of the rows the partition of the
+ * core rows and the noise set do not change.
+ * d_out_labels: per cloud [len_i] u32, required for a non-empty cloud; it goes to a3d_point_clouds_select_device as it is.
+ * d_out_row_sizes: NULL, or per cloud NULL / [len_i] u32.  d_out_sizes, d_out_roots: NULL, or per cloud NULL / [len_i] u32
+ * of which the first C_i are written and the rest left untouched.  out_clusters[i] = C_i, out_noise[i] = noise rows
+ * (dropped ones included), out_dropped[i] = dropped rows: [n] u64 in host memory, each NULL ok.
+ * Decided on the host before anything is launched (nothing is touched): n == 0 is A3D_OK; a NULL ctx, d_clouds or
+ * d_out_labels, a radius that is not finite or <= 0 (or so small that its square is 0 in f32), min_points == 0, a cloud of
+ * 2^32 points or more (or within one tile, < 2^21 points, of it), NULL points or labels of a non-empty cloud, any overlap
+ * of an output ([len_i] u32 each) with an input (points, normals) or another output are A3D_INVALID_PARAMETER.  A cloud with
+ * len == 0 may have null pointers and yields zeros.  A union-find loop that ran past its bound (it cannot) is A3D_HIP_ERROR.
+ * Scratch memory (context-owned, grow-only, shared with the calls above): that of the knn entry (32 to 64 bytes per point
+ * of hash table, 16 for the cell-ordered copy) plus 12 bytes per point (parent, owner, size), 1 / 8 byte per point of flags,
+ * 4 bytes per 1024 points and 168 bytes per cloud. */
+a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n, float radius,
+                                           uint32_t min_points, uint32_t* const* d_out_labels,
+                                           uint32_t* const* d_out_row_sizes, uint32_t* const* d_out_sizes,
+                                           uint32_t* const* d_out_roots, uint64_t* out_clusters, uint64_t* out_noise,
+                                           uint64_t* out_dropped);
+
 /* A persistent voxel map: the hash table of the downsample above kept between calls, so that resident clouds go in frame
  * by frame (a3d_voxel_map_insert) instead of merge + downsample of the whole map per frame.  The contract:
  *   After any sequence of inserts, the map's contents equal a3d_point_clouds_merge_device(all inserted clouds under their
