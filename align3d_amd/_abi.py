@@ -232,6 +232,17 @@ SIGNATURES = {
         [_P, C.POINTER(PointCloudViewC), C.c_uint64, C.c_float, C.c_uint32, _PP, _PP, _PP, _PP, C.POINTER(C.c_uint64),
          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
+    "a3d_point_clouds_segment_plane_device": (
+        _ST,
+        [_P, C.POINTER(PointCloudViewC), C.c_uint64, C.c_float, C.c_uint32, _PP, C.POINTER(C.c_uint32), _PP, _PP,
+         C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    ),
+    "a3d_plane_hypotheses": (_ST, [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "a3d_plane_from_moments": (
+        _ST,
+        [C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_double),
+         C.POINTER(C.c_uint32)],
+    ),
     "a3d_voxel_map_new": (_ST, [_P, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_uint64, _PP]),
     "a3d_voxel_map_insert": (
         _ST,

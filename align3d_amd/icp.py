@@ -1064,6 +1064,165 @@ class DevicePointCloud:
         finally:
             self.ctx.free(d_labels)
 
+    @staticmethod
+    def plane_hypotheses(seed, length, num_iterations):
+        """The candidate triples segment_plane scores by default (a3d_plane_hypotheses; host only): a uint32
+        [num_iterations, 3] array of row numbers below `length`, candidate h a function of (seed, h, length) alone."""
+        seed, length, h = int(seed), int(length), int(num_iterations)
+        if not (0 <= seed < 1 << 64 and 0 <= length < 1 << 64 and 0 <= h < 1 << 64):
+            raise _abi.InvalidParameter("plane_hypotheses: seed, length and num_iterations are unsigned 64-bit integers")
+        out = np.zeros((h if h <= 4096 else 0, 3), np.uint32)
+        _abi.check(_abi.load_library().a3d_plane_hypotheses(seed, length, h, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                   "a3d_plane_hypotheses")
+        return out
+
+    @staticmethod
+    def plane_from_moments(moments, point, distance_threshold, fallback_normal):
+        """(plane float64 [4], valid) from one record of refit moments (a3d_plane_from_moments; host only): 16 integers
+        N, S[3], Lo[6], Hi[6] (signed ones as they are), the f32 point they were taken against, the call's threshold and
+        the normal an invalid refit keeps."""
+        words = [int(m) for m in moments]
+        if len(words) != 16 or any(not -(1 << 63) <= m < 1 << 64 for m in words):
+            raise _abi.InvalidParameter("plane_from_moments: 16 integers of 64 bits")
+        m = (C.c_uint64 * 16)(*[w & 0xFFFFFFFFFFFFFFFF for w in words])
+        a = (C.c_float * 3)(*np.ascontiguousarray(point, np.float32).reshape(3).tolist())
+        f = (C.c_float * 3)(*np.ascontiguousarray(fallback_normal, np.float32).reshape(3).tolist())
+        plane, valid = (C.c_double * 4)(), C.c_uint32()
+        _abi.check(_abi.load_library().a3d_plane_from_moments(m, a, float(distance_threshold), f, plane, C.byref(valid)),
+                   "a3d_plane_from_moments")
+        return np.array(plane[:], np.float64), bool(valid.value)
+
+    @staticmethod
+    def segment_plane_many(clouds, distance_threshold, num_iterations=1000, seed=0, refine=0, triples=None):
+        """segment_plane for resident clouds of one context in ONE call (a3d_point_clouds_segment_plane_device): the
+        number of launches does not depend on the number of clouds.  triples: None (every non-empty cloud gets
+        plane_hypotheses(seed, len, num_iterations), an empty one no candidates), or one entry per cloud, each None or an
+        integer array [H, 3] of row numbers.  Returns ([plane float64 [4]], [d_flags], [inliers]): the flags buffers are
+        RESIDENT, len() u32 each; the caller releases each with the context's free()."""
+        clouds = list(clouds)
+        if not clouds:
+            return [], [], []
+        clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "segment_plane")
+        n, refine = len(clouds), int(refine)
+        if not 0 <= refine <= 8:
+            raise _abi.InvalidParameter(f"segment_plane: refine is 0 to 8 rounds (got {refine})")
+        if not 0 <= int(num_iterations) <= 4096:
+            raise _abi.InvalidParameter(f"segment_plane: num_iterations is at most 4096 (got {num_iterations})")
+        if triples is None:
+            triples = [None] * n
+        triples = list(triples)
+        if len(triples) != n:
+            raise _abi.InvalidParameter(f"segment_plane: {n} clouds but {len(triples)} arrays of triples")
+        host = []
+        for c, tr in zip(clouds, triples):
+            if tr is None:
+                tr = DevicePointCloud.plane_hypotheses(seed, c.n, num_iterations if c.n else 0)
+            else:
+                tr = np.asarray(tr)
+                if tr.ndim != 2 or tr.shape[1] != 3 or not (np.issubdtype(tr.dtype, np.integer) or tr.size == 0):
+                    raise _abi.InvalidParameter(f"segment_plane: triples are an integer array [H, 3] (got {tr.shape} {tr.dtype})")
+                if tr.size and (tr.min() < 0 or tr.max() >= c.n):
+                    raise _abi.InvalidParameter(f"segment_plane: a triple names a row outside a cloud of {c.n} rows")
+                if len(tr) > 4096:
+                    raise _abi.InvalidParameter(f"segment_plane: at most 4096 candidates per cloud (got {len(tr)})")
+            host.append(np.ascontiguousarray(tr, np.uint32).reshape(-1, 3))
+        d_flags = []
+        try:
+            for c in clouds:
+                d_flags.append(ctx.malloc(max(1, c.n) * 4))
+            planes, inliers = (C.c_double * (4 * n))(), (C.c_uint64 * n)()
+            _abi.check(
+                ctx.lib.a3d_point_clouds_segment_plane_device(
+                    ctx.handle, DevicePointCloud._views(clouds), n, float(distance_threshold), refine,
+                    (C.c_void_p * n)(*[t.ctypes.data if len(t) else None for t in host]),
+                    (C.c_uint32 * n)(*[len(t) for t in host]), (C.c_void_p * n)(*d_flags), None, planes, None, inliers, None),
+                "a3d_point_clouds_segment_plane_device",
+            )
+        except BaseException:
+            for d in d_flags:
+                ctx.free(d)
+            raise
+        return ([np.array(planes[4 * i:4 * i + 4], np.float64) for i in range(n)], d_flags, [int(k) for k in inliers])
+
+    def segment_plane(self, distance_threshold, num_iterations=1000, seed=0, refine=0, triples=None):
+        """The dominant plane of this cloud, found on the device: RANSAC with EVERY candidate scored.  Each of the
+        `num_iterations` candidates (at most 4096) is the plane through three rows; a row is an inlier of a plane iff its
+        distance to it is at most `distance_threshold`; the candidate with the most inliers wins (the lowest number on a
+        tie), its inliers are flagged and the plane is refitted to them by least squares (the direction of least spread
+        of the flagged rows, through their centroid).  refine=R repeats flagging and refit R times against the refitted
+        plane (at most 8).  Returns (plane, d_flags, inliers): plane = float64 (a, b, c, d) with a*x + b*y + c*z + d = 0,
+        (a, b, c) a unit normal turned so that d >= 0 (the origin on its positive side); d_flags = a RESIDENT buffer of
+        len() u32, 1 for the rows of the plane and 0 for the rest, which goes to select() as it is (release it with the
+        context's free()); inliers = the number of flagged rows.  A cloud without three rows that span a plane among its
+        candidates gives the plane (0, 0, 0, 0), no flagged row and inliers = 0.
+        This is PCL's SACSegmentation(SACMODEL_PLANE, SAC_RANSAC) with setDistanceThreshold / setMaxIterations (and
+        setOptimizeCoefficients for the refit), and Open3D's segment_plane(distance_threshold, ransac_n=3,
+        num_iterations): refine=0 is Open3D's result shape, the inliers of the best candidate and the model refitted to
+        them.  What does NOT correspond: there is no early exit by inlier probability, all candidates are always scored,
+        so num_iterations is the work done and not an upper bound; and the sampling is a counter-based rule of our own
+        (plane_hypotheses: candidate h depends on seed, h and len() only), not the generators of those libraries, so the
+        same seed does not give their planes.  triples= takes the caller's own candidates ([H, 3] row numbers) instead.
+        A row with a NaN or an infinity is never an inlier.  Every decision is on integers or on bits that no order
+        changes: the same result on every run."""
+        planes, flags, inliers = DevicePointCloud.segment_plane_many([self], distance_threshold, num_iterations, seed, refine,
+                                                                    None if triples is None else [triples])
+        return planes[0], flags[0], inliers[0]
+
+    @staticmethod
+    def split_plane_many(clouds, distance_threshold, num_iterations=1000, seed=0, refine=0, triples=None, return_index=False):
+        """split_plane for resident clouds of one context: one segment call and one select call over the clouds taken
+        twice, whatever their number.  Returns ([planes], [plane clouds], [rest clouds]), with return_index=True also
+        ([plane index arrays], [rest index arrays])."""
+        clouds = list(clouds)
+        if not clouds:
+            return ([], [], [], [], []) if return_index else ([], [], [])
+        n, ctx = len(clouds), clouds[0].ctx
+        planes, d_flags, _ = DevicePointCloud.segment_plane_many(clouds, distance_threshold, num_iterations, seed, refine, triples)
+        try:
+            out = DevicePointCloud.select_many(clouds + clouds, d_flags + d_flags, [1] * n + [0] * n, [1] * n + [0] * n,
+                                               return_index)
+        finally:
+            for d in d_flags:
+                ctx.free(d)
+        if return_index:
+            return planes, out[0][:n], out[0][n:], out[1][:n], out[1][n:]
+        return planes, out[:n], out[n:]
+
+    def split_plane(self, distance_threshold, num_iterations=1000, seed=0, refine=0, triples=None, return_index=False):
+        """This cloud cut at its dominant plane: (plane, plane_cloud, rest_cloud), two new resident clouds in input order
+        with normals and colours carried bit for bit when this cloud has them: segment_plane, then ONE select over the
+        cloud taken twice (flags == 1 and flags == 0).  return_index=True returns (plane, plane_cloud, rest_cloud,
+        plane_index, rest_index), the index arrays as in select().  The arguments, and what corresponds to PCL
+        (SACSegmentation + ExtractIndices, negative and not) and Open3D (segment_plane + select_by_index, inverted and
+        not), are segment_plane's."""
+        out = DevicePointCloud.split_plane_many([self], distance_threshold, num_iterations, seed, refine,
+                                                None if triples is None else [triples], return_index)
+        return tuple(x[0] for x in out)
+
+    @staticmethod
+    def remove_plane_many(clouds, distance_threshold, num_iterations=1000, seed=0, refine=0, triples=None, return_index=False):
+        """[c.remove_plane(...) for c in clouds] for resident clouds of one context: one segment call and one select
+        call, whatever the number of clouds."""
+        clouds = list(clouds)
+        if not clouds:
+            return ([], []) if return_index else []
+        ctx = clouds[0].ctx
+        _, d_flags, _ = DevicePointCloud.segment_plane_many(clouds, distance_threshold, num_iterations, seed, refine, triples)
+        try:
+            return DevicePointCloud.select_many(clouds, d_flags, 0, 0, return_index)
+        finally:
+            for d in d_flags:
+                ctx.free(d)
+
+    def remove_plane(self, distance_threshold, num_iterations=1000, seed=0, refine=0, triples=None, return_index=False):
+        """This cloud without its dominant plane (the floor, the table), as a new resident cloud in input order with
+        normals and colours when this cloud has them: segment_plane followed by select(flags, 0, 0).  It is the step before
+        cluster() in a tabletop pipeline: objects that stand on one plane are one cluster until it is gone.  Calling it
+        again on the result takes the next plane out.  return_index as in select(); everything else as segment_plane."""
+        out = DevicePointCloud.remove_plane_many([self], distance_threshold, num_iterations, seed, refine,
+                                                 None if triples is None else [triples], return_index)
+        return (out[0][0], out[1][0]) if return_index else out[0]
+
     def render(self, camera, camera_to_world=None, radius=0.0, return_index=False):
         """What a pinhole camera sees of this cloud, as a new DeviceRangeImage (a3d_point_cloud_render_device): the
         inverse of from_range_image, PinholeCamera::project_to_image (src/camera.rs:177-202) over every point.  `camera`

@@ -2,7 +2,8 @@
 """A map from a recorded sequence without leaving the device:
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
         [--voxel V [--mean] [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
-        [--estimate-normals R] [--radius-outliers R N] [--stat-outliers R K A] [--clusters R M S] [--out map.npy]
+        [--estimate-normals R] [--remove-plane T] [--radius-outliers R N] [--stat-outliers R K A] [--clusters R M S]
+        [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -43,7 +44,10 @@ second the rows whose mean distance to their K nearest others within R lies more
 frame's mean (remove_statistical_outliers_many); with both, the radius filter runs first.  The flying pixels at depth edges
 and isolated returns then never own a cell of the map.  --clusters R M S runs after them and drops what they keep, the
 floating clumps: the rows that are noise or belong to a cluster of fewer than S rows under DBSCAN with radius R and
-min_points M (DevicePointCloud.remove_small_clusters_many; M = 1 is PCL's Euclidean cluster extraction with a minimum size).  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+min_points M (DevicePointCloud.remove_small_clusters_many; M = 1 is PCL's Euclidean cluster extraction with a minimum size).
+--remove-plane T runs before all of them: each frame's dominant plane (the floor, a wall or a table top: the rows within T
+metres of the best of 1000 candidate planes, DevicePointCloud.remove_plane_many, one segment call and one select call for
+all frames) stays out of the map, and the cluster filter then sees objects instead of one connected room.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -76,6 +80,9 @@ ap.add_argument("--colors", action="store_true", help="carry the frames' RGB col
 ap.add_argument("--estimate-normals", type=float, default=None, metavar="R",
                 help="replace every frame's image normals by normals estimated from the cloud itself within R metres "
                      "(with --render-track the rendered model's normals are refreshed too, within 3 V whatever R is)")
+ap.add_argument("--remove-plane", type=float, default=None, metavar="T",
+                help="before a frame's cloud goes into the map (and before the filters below), drop its dominant plane: the rows "
+                     "within T metres of the best of 1000 candidate planes")
 ap.add_argument("--radius-outliers", nargs=2, type=float, default=None, metavar=("R", "N"),
                 help="before a frame's cloud goes into the map, drop its rows with fewer than N rows within R metres")
 ap.add_argument("--stat-outliers", nargs=3, type=float, default=None, metavar=("R", "K", "A"),
@@ -131,19 +138,23 @@ for k, (now_to_previous, st) in enumerate(zip(poses, status)):
         traj.accumulate(now_to_previous, float(k + 1))
     camera_to_world.append(traj.current_camera_to_world())
 
-# what goes into the map: the frames' clouds, cleaned if asked for (one knn or cluster call and one select call per filter,
+# what goes into the map: the frames' clouds, cleaned if asked for (one plane, knn or cluster call and one select call per filter,
 # all frames)
 map_clouds = clouds
-for name, spec in (("radius", args.radius_outliers), ("statistical", args.stat_outliers), ("cluster", args.clusters)):
+for name, spec in (("plane", args.remove_plane), ("radius", args.radius_outliers), ("statistical", args.stat_outliers),
+                   ("cluster", args.clusters)):
     if spec is None:
         continue
-    if name == "radius":
+    if name == "plane":
+        cleaned = DevicePointCloud.remove_plane_many(map_clouds, spec)
+    elif name == "radius":
         cleaned = DevicePointCloud.remove_radius_outliers_many(map_clouds, spec[0], int(spec[1]))
     elif name == "statistical":
         cleaned = DevicePointCloud.remove_statistical_outliers_many(map_clouds, spec[0], int(spec[1]), spec[2])
     else:
         cleaned = DevicePointCloud.remove_small_clusters_many(map_clouds, spec[0], int(spec[1]), int(spec[2]))
-    print(f"{name} outlier filter {spec}: {sum(c.len() for c in map_clouds)} rows -> {sum(c.len() for c in cleaned)}")
+    print(f"{name} {'removal' if name == 'plane' else 'outlier filter'} {spec}: {sum(c.len() for c in map_clouds)} rows -> "
+          f"{sum(c.len() for c in cleaned)}")
     if map_clouds is not clouds:
         for c in map_clouds:
             c.free()

@@ -777,6 +777,85 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
                                            uint32_t* const* d_out_roots, uint64_t* out_clusters, uint64_t* out_noise,
                                            uint64_t* out_dropped);
 
+/* The dominant plane of n resident clouds (PCL SACSegmentation with SACMODEL_PLANE, Open3D segment_plane), each exactly
+ * as if it were passed alone, in a number of launches that does not depend on n: one upload (job table, triples, zeroed
+ * words), one fill and four launches (candidates, score, best, flag + moments), and one small upload and one launch more
+ * per refinement round; host-synchronous.  There is no early exit by probability: every candidate is scored against every
+ * row.  The rule:
+ * Every f32 and every f64 operation is rounded on its own.  Divide and sqrt are correctly rounded.
+ * Per call: a distance threshold t, f32, finite and > 0, and a number of refinement rounds R with 0 <= R <= 8.
+ * Per cloud i: H_i candidate triples (a, b, c) of row numbers, [H_i][3] u32 in HOST memory.  0 <= H_i <= 4096.  Every
+ * index is < len_i.
+ *   1. Candidate plane of a triple.  The three points are widened to f64.  u = p_b - p_a, v = p_c - p_a.  m = u x v, each
+ *      component as u_y*v_z - u_z*v_y.  L = (m_x*m_x + m_y*m_y) + m_z*m_z.  U = (u_x*u_x + u_y*u_y) + u_z*u_z, and V
+ *      likewise.  The candidate is DEGENERATE iff two of its indices are equal, or L is not finite, or not
+ *      L > (U*V) * 2^-20.  That covers a repeated row, a non-finite row, and three rows whose sine is below 2^-10.
+ *      Otherwise n = (float)(m / sqrt(L)) per component, and the plane's point is p_a, in f32 as stored.
+ *   2. Distance and inlier, in f32.  e_k = p_k - p_ak, d = (n_x*e_x + n_y*e_y) + n_z*e_z.  Row p is an inlier of the
+ *      candidate iff fabsf(d) <= t.  A row with a NaN or an infinity is never an inlier.  The form p - a is deliberate.
+ *      n.p + w saves three operations per test and cancels badly for clouds far from the origin.
+ *   3. Score.  count[h] is the number of inliers of candidate h over ALL rows of the cloud, and 0 for a degenerate
+ *      candidate.  The best candidate maximises count[h] << 32 | (0xFFFFFFFF - h): the most inliers, the lowest h on a
+ *      tie.  If every candidate is degenerate, or H_i == 0 or len_i == 0, there is no plane: flags all 0, plane four
+ *      zeros, best = 0xFFFFFFFF, status A3D_OK.
+ *   4. Flags.  flags[p] = 1 iff p is an inlier of the current plane (n, point), else 0.  After step 3 the current plane
+ *      is the best candidate's.
+ *   5. Refit moments over the rows with flag 1, all in integers.  s = 64.0f / t in f32.  q_k = (int) rintf(e_k * s), ties
+ *      to even, with e from step 2 against the current plane's point.  A flagged row takes part iff
+ *      fabsf(e_k * s) <= 1048576.0f for all three k.  N = sum 1, S_k = sum q_k, and for the six products P = q_k q_l, with
+ *      |P| <= 2^40: Lo_kl = sum (P & 0x7FFFFFFF), Hi_kl = sum (P >> 31), an arithmetic shift.  So
+ *      M_kl = Hi_kl * 2^31 + Lo_kl exactly.  With len < 2^32, N, S, Lo and Hi each fit 64 bits, so no order of summation
+ *      can matter.  The record is 16 u64 words: N, S[3], Lo[6], Hi[6] in the order xx, xy, xz, yy, yz, zz.
+ *   6. Plane from moments, on the HOST (a3d_plane_from_moments).  A_kl = N*M_kl - S_k*S_l, exact in 128-bit integers
+ *      (|A| < 2^105).  Each A_kl converted to f64, round to nearest even.  mx = max |A_kl|.  The refit is VALID iff N >= 3
+ *      and mx > 0.  Then steps 4 (scaling by frexp's exponent) to 6 (normal = column of the smallest diagonal entry,
+ *      normalised) of the rule of a3d_point_clouds_estimate_normals_device: six cyclic Jacobi sweeps in f32.  Centroid in
+ *      f64: c_k = (double)a_k + ((double)S_k / (double)N) / (double)s, with a the point that the moments were taken
+ *      against.  d = -((n_x*c_x + n_y*c_y) + n_z*c_z) in f64, with n widened.  The four numbers are negated iff d < 0.
+ *      This is the side the origin is on: the default viewpoint of the normals call.  If the refit is not valid, the
+ *      plane is the current plane itself: its f32 normal widened, and c = a; d and the sign follow in the same way.
+ *   7. Refinement, R times.  The current plane becomes the plane of step 6: normal (float)n, point (float)c.  Steps 4 and
+ *      5 are repeated against it, then step 6.  R = 0 is the inliers of the best candidate and the model refitted to them
+ *      (Open3D's behaviour).
+ * Every count, flag and moment is an integer decided on f32 bits that no order can change: the same on every run, and under
+ * a permutation of the rows (the triples mapped through it) the same counts, best and plane, and the permuted flags.
+ * triples: [n] host pointers to [H_i][3] u32 (NULL ok where H_i == 0); n_triples: [n] u32, the H_i.  d_out_flags: per cloud
+ * [len_i] u32, required for a non-empty cloud; it goes to a3d_point_clouds_select_device as it is: lo = hi = 1 is the plane,
+ * lo = hi = 0 is the rest.  d_out_counts: NULL, or per cloud NULL / [H_i] u32, count[h] of step 3; words past H_i are left
+ * untouched.  out_planes: [n][4] f64 (n_x, n_y, n_z, d: n.x + d = 0), required.  out_best[i] = the best candidate's h,
+ * out_inliers[i] = the flagged rows of the last round, out_refit_rows[i] = N of the last moments: [n] u64, each NULL ok.
+ * All of these are host memory.
+ * Decided on the host before anything is launched (nothing is touched): n == 0 is A3D_OK; a NULL ctx, d_clouds, triples,
+ * n_triples, d_out_flags or out_planes, a t that is not finite or <= 0 (or so small that 64 / t is not finite in f32),
+ * refine > 8, H_i > 4096, NULL triples of a cloud with H_i > 0, a triple index >= len_i (so every H_i > 0 on an empty cloud),
+ * a cloud of 2^32 points or more, NULL points or flags of a non-empty cloud, any overlap of an output (flags [len_i] u32,
+ * counts [H_i] u32) with an input (points, normals) or another output are A3D_INVALID_PARAMETER.  A cloud with len == 0 may
+ * have null pointers and has no plane.
+ * Scratch memory (context-owned, grow-only, shared with the calls above): 48 bytes per candidate (triple, plane, counter),
+ * 64 bytes per cloud and 136 bytes per cloud and round. */
+a3d_status a3d_point_clouds_segment_plane_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n, float t,
+                                                 uint32_t refine, const uint32_t* const* triples, const uint32_t* n_triples,
+                                                 uint32_t* const* d_out_flags, uint32_t* const* d_out_counts,
+                                                 double* out_planes, uint64_t* out_best, uint64_t* out_inliers,
+                                                 uint64_t* out_refit_rows);
+
+/* The candidate triples the wrappers give the entry above; host only, no GPU call.  For candidate h and k in 0..2:
+ * z = seed + (3h + k + 1) * 0x9E3779B97F4A7C15 mod 2^64, then the splitmix64 finaliser (z ^= z >> 30;
+ * z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31), and the index is
+ * ((z >> 32) * len) >> 32.  A counter-based rule of our own, not the generator of PCL or Open3D: candidate h does not depend
+ * on H.  Repeated indices are allowed: such a candidate is degenerate by the rule above.  out_triples: [H][3] u32.  H == 0
+ * is A3D_OK and writes nothing; a NULL out_triples, len == 0, len >= 2^32 and H > 4096 are A3D_INVALID_PARAMETER. */
+a3d_status a3d_plane_hypotheses(uint64_t seed, uint64_t len, uint64_t H, uint32_t* out_triples);
+
+/* Step 6 of the rule above, from one record of step 5; host only, no GPU call.  moments: N, S[3], Lo[6], Hi[6]; point: the
+ * point a the moments were taken against; t: the call's threshold (s = 64.0f / t); fallback_normal: the current plane's
+ * normal, which an invalid refit keeps.  out_plane: (n_x, n_y, n_z, d).  *out_valid (NULL ok) = 1 iff the refit was valid.
+ * A NULL moments, point, fallback_normal or out_plane, a t that is not finite or <= 0 (or with 64 / t not finite), and
+ * moments that no call can have produced (N >= 2^32, |S_k| > N * 2^20, Lo_kl > N * (2^31 - 1), |Hi_kl| > N * 2^9) are
+ * A3D_INVALID_PARAMETER. */
+a3d_status a3d_plane_from_moments(const uint64_t moments[16], const float point[3], float t, const float fallback_normal[3],
+                                  double out_plane[4], uint32_t* out_valid);
+
 /* A persistent voxel map: the hash table of the downsample above kept between calls, so that resident clouds go in frame
  * by frame (a3d_voxel_map_insert) instead of merge + downsample of the whole map per frame.  The contract:
  *   After any sequence of inserts, the map's contents equal a3d_point_clouds_merge_device(all inserted clouds under their
