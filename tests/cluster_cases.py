@@ -127,3 +127,101 @@ def pairs_far_apart_expected(n, m):
     labels[:paired] = np.arange(paired)
     labels[h:] = np.arange(paired)
     return labels, np.full(paired, 2, np.uint32), np.arange(paired, dtype=np.uint32)
+
+
+# ---- clouds for the union-find under contention (test_gpu_cluster_contention.py): r = 0.05, points `STEP` apart ----------
+
+R_CONTENTION = 0.05
+STEP = 0.9 * R_CONTENTION  # neighbours along a line; two steps are 1.8 r: no neighbours, even in f32 3 km from the origin
+NOISE_SET = -1
+
+
+def labels_of_sets(sets, core=None):
+    """(labels [n] u32, sizes [C] u32, roots [C] u32) from the set number of every row (NOISE_SET: in no cluster) and the
+    mask of its core rows (None: every member is core): the root of a set is its lowest core row, and the clusters are
+    numbered by ascending root.  Nothing here looks at a point."""
+    sets = np.asarray(sets, np.int64)
+    n = len(sets)
+    member = sets != NOISE_SET
+    core = member if core is None else np.asarray(core, bool) & member
+    count = int(sets.max()) + 1 if member.any() else 0
+    root_of_set = np.full(count, n, np.int64)
+    np.minimum.at(root_of_set, sets[core], np.flatnonzero(core))
+    assert (root_of_set < n).all()  # every set has a core row
+    order = np.argsort(root_of_set, kind="stable")
+    number = np.empty(count, np.int64)
+    number[order] = np.arange(count)
+    labels = np.full(n, 0xFFFFFFFF, np.int64)
+    labels[member] = number[sets[member]]
+    sizes = np.bincount(labels[member], minlength=count)
+    return labels.astype(np.uint32), sizes.astype(np.uint32), root_of_set[order].astype(np.uint32)
+
+
+def chain_sets(n, order, cut=None):
+    """The set of every row of chain(n, order, stretch=(cut, 1.001)): the rows at positions 0 .. cut along the chain are
+    set 0, the rest set 1 (cut None: one set)."""
+    position = np.arange(n)
+    if order == "descending":
+        position = position[::-1]
+    elif order == "shuffled":
+        position = np.random.default_rng(n).permutation(n)
+    return np.zeros(n, np.int64) if cut is None else (position > cut).astype(np.int64)
+
+
+def interleaved_lines(n, K, descending=False):
+    """(points [n, 3] f32, line [n], ends [n] bool): row p lies on line p % K at position p // K (descending: counted from
+    the line's far end), STEP apart along a direction off the axes; the lines stand 3 r apart on a square grid of
+    ceil(sqrt(K)) a side.  ends: the first and the last point of every line.  Every line has at least 3 rows."""
+    p = np.arange(n)
+    line, at = p % K, p // K
+    length = (n - line + K - 1) // K  # rows of the row's line
+    assert length.min() >= 3
+    if descending:
+        at = length - 1 - at
+    g = int(np.ceil(np.sqrt(K)))
+    u, v, w = np.float64([0.6, 0.8, 0.0]), np.float64([-0.48, 0.36, 0.8]), np.float64([0.64, -0.48, 0.6])  # orthonormal
+    pitch = 3.0 * R_CONTENTION
+    points = (np.float64([-0.7, 0.4, 0.2]) + (line % g)[:, None] * pitch * u + (line // g)[:, None] * pitch * v
+              + at[:, None] * STEP * w)
+    return points.astype(np.float32), line, (at == 0) | (at == length - 1)
+
+
+def lattice_sheet(side):
+    """(points [side * side, 3] f32, kind [side * side]: neighbours in the sheet, 4 interior, 3 edge, 2 corner): a square
+    lattice of pitch STEP in a plane off the axes, rows shuffled.  The diagonal is 1.27 r, so a row's neighbours are
+    itself and the rows next to it along the two directions: counts 5, 4 and 3."""
+    a, b = np.divmod(np.arange(side * side), side)
+    u, v = np.float64([0.6, 0.8, 0.0]), np.float64([-0.48, 0.36, 0.8])
+    points = np.float64([0.2, -0.3, 0.1]) + a[:, None] * STEP * u + b[:, None] * STEP * v
+    kind = 4 - ((a == 0) | (a == side - 1)).astype(np.int64) - ((b == 0) | (b == side - 1)).astype(np.int64)
+    perm = np.random.default_rng(side).permutation(side * side)
+    return points[perm].astype(np.float32), kind[perm]
+
+
+SHEET_SIDE = 260  # 67 600 rows: 67 tiles of 1024
+COMB_TEETH, COMB_TOOTH = 66, 1024
+
+
+def comb(cut=None, shuffled=False):
+    """(points, sets): COMB_TEETH teeth of COMB_TOOTH rows, tooth t in rows [t L, (t + 1) L) along x from 0 at
+    y = 2 t STEP, even teeth ascending away from the spine and odd teeth descending towards it; then the spine, 2 T - 1
+    points at x = -STEP, y = s STEP, in the highest rows.  The spine point at even s is STEP from the first point of tooth
+    s / 2; at odd s it is 1.27 r from the teeth and touches only the spine.  cut: the spine point 2 cut + 1 is left out,
+    and the rows beyond it (teeth cut + 1 ..., spine points from 2 cut + 2) are set 1.  shuffled: under a seeded row
+    permutation."""
+    T, L = COMB_TEETH, COMB_TOOTH
+    tooth, k = np.divmod(np.arange(T * L), L)
+    along = np.where(tooth % 2 == 0, k, L - 1 - k)
+    teeth = np.stack([along * STEP, 2 * tooth * STEP, np.zeros(T * L)], axis=1)
+    s = np.arange(2 * T - 1)
+    if cut is not None:
+        s = s[s != 2 * cut + 1]
+    spine = np.stack([np.full(len(s), -STEP), s * STEP, np.zeros(len(s))], axis=1)
+    points = (np.float64([0.37, -0.21, 0.55]) + np.r_[teeth, spine]).astype(np.float32)
+    sets = np.zeros(len(points), np.int64)
+    if cut is not None:
+        sets = np.r_[tooth > cut, s > 2 * cut + 1].astype(np.int64)
+    if shuffled:
+        perm = np.random.default_rng(COMB_TEETH).permutation(len(points))
+        points, sets = points[perm], sets[perm]
+    return np.ascontiguousarray(points), sets

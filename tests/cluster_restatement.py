@@ -2,8 +2,10 @@
 by brute force over pairs, chunked, as outlier_restatement.knn_distance finds them (or by a sort by cell, for clouds whose
 full pair count is out of reach; the two are checked against each other), the grid from normals_restatement.cells, a plain
 sequential union-find (quick-find: one component number per row, a union renumbers the higher component) over the
-core-core pairs in row order, the border key and the ranking.  It is the expected value of every cluster test and never
-the code under test.  numpy evaluates each f32 operation on its own, which is the arithmetic the library is compiled for.
+core-core pairs in row order (or, for clouds of tens of thousands of rows, min-label hooking with pointer jumping: the
+two are checked against each other), the border key and the ranking.  It is the expected value of every cluster test and
+never the code under test.  numpy evaluates each f32 operation on its own, which is the arithmetic the library is compiled
+for.
 
 The rule of the cluster call.  All f32 operations are rounded on their own (-ffp-contract=off).  Per call: radius r,
 finite and > 0, r2 = r * r computed on the host in f32; min_points m >= 1.
@@ -107,16 +109,10 @@ def sorted_pairs(pairs):
     return pairs.i[order], pairs.j[order], pairs.d2[order]
 
 
-def cluster_pairs(pairs, min_points):
-    """Rules 2 to 6 from the neighbour pairs."""
-    n, m = pairs.n, int(min_points)
-    assert m >= 1
-    counts = np.bincount(pairs.i, minlength=n).astype(np.int64)  # rule 2 (the row itself is a pair)
-    core = pairs.kept & (counts >= m)
-    # rule 3: sequential union-find over the core-core pairs with j < i, in row order; comp[x] = lowest row of x's set
+def components_quick_find(n, li, lj):
+    """comp [n]: the lowest row of every row's set under the links (li[k], lj[k]), lj < li.  A sequential union-find
+    over the links in row order, one component number per row; a union renumbers the higher component, an O(n) pass."""
     comp = np.arange(n, dtype=np.int64)
-    link = core[pairs.i] & core[pairs.j] & (pairs.j < pairs.i)
-    li, lj = pairs.i[link], pairs.j[link]
     order = np.argsort(li, kind="stable")
     li, lj = li[order], lj[order]
     starts = np.searchsorted(li, np.arange(n + 1))
@@ -126,6 +122,46 @@ def cluster_pairs(pairs, min_points):
         for s in np.r_[sets, comp[row]]:
             if s != low:
                 comp[comp == s] = low
+    return comp
+
+
+def components_hooking(n, li, lj):
+    """The same comp without a pass over the rows per union, for clouds of tens of thousands of rows: every row starts as
+    its own root; a round hooks the root of each end of a link under the lower of the two roots (the minimum wins where
+    several links hook one root), then every row jumps to its parent's parent until nothing moves, so that comp[x] is
+    x's root again; rounds repeat until a round hooks nothing.  A root is only ever hooked under a lower row, so a
+    set's root is its lowest row, and a link whose ends have different roots hooks one of them, so the last round has
+    seen every link inside one set.  The sets that are left at least halve per round: O(log n) rounds."""
+    comp = np.arange(n, dtype=np.int64)
+    while len(li):
+        a, b = comp[li], comp[lj]
+        apart = a != b
+        if not apart.any():
+            break
+        a, b = a[apart], b[apart]
+        low = np.minimum(a, b)
+        np.minimum.at(comp, a, low)  # a and b are roots: comp[root] == root before this
+        np.minimum.at(comp, b, low)
+        while True:
+            up = comp[comp]
+            if np.array_equal(up, comp):
+                break
+            comp = up
+    return comp
+
+
+COMPONENTS = {"quick_find": components_quick_find, "hooking": components_hooking}
+
+
+def cluster_pairs(pairs, min_points, components="quick_find"):
+    """Rules 2 to 6 from the neighbour pairs.  components: the routine of rule 3, a key of COMPONENTS."""
+    n, m = pairs.n, int(min_points)
+    assert m >= 1
+    counts = np.bincount(pairs.i, minlength=n).astype(np.int64)  # rule 2 (the row itself is a pair)
+    core = pairs.kept & (counts >= m)
+    # rule 3: the components of the core-core pairs with j < i; comp[x] = lowest row of x's set
+    link = core[pairs.i] & core[pairs.j] & (pairs.j < pairs.i)
+    comp = COMPONENTS[components](n, pairs.i[link], pairs.j[link])
     # rule 4: the minimum key over the core neighbours of a kept row that is not core
     cand = ~core[pairs.i] & core[pairs.j]
     bi, bj = pairs.i[cand], pairs.j[cand]
@@ -150,10 +186,10 @@ def cluster_pairs(pairs, min_points):
                     ~member, int((~pairs.kept).sum()))
 
 
-def cluster(points, radius, min_points, by_cell=False):
+def cluster(points, radius, min_points, by_cell=False, components="quick_find"):
     """Clusters(labels [n] u32, sizes [C] u32, roots [C] u32, row_sizes [n] u32, counts [n] u32, core / border / noise [n]
     bool, dropped) of one cloud."""
-    return cluster_pairs((pairs_by_cell if by_cell else pairs_brute)(points, radius), min_points)
+    return cluster_pairs((pairs_by_cell if by_cell else pairs_brute)(points, radius), min_points, components)
 
 
 def remove_small_clusters(points, radius, min_points, min_size, max_size=NONE):

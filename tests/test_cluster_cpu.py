@@ -2,7 +2,8 @@
 the ctypes mirror, the Rust bindings, every refusal that is decided on the host, with made-up device addresses: nothing is
 dereferenced), and the numpy restatement (cluster_restatement.py, the expected value of the GPU tests) against
 connected components, against a textbook sequential DBSCAN, against clouds whose clusters are known by construction and
-against what the feature is for."""
+against what the feature is for; and the clouds of test_gpu_cluster_contention.py (cluster_cases.py) against the clusters
+they have by construction, with the restatement's hooking components, which are shown equal to the quick-find's."""
 import ctypes as C
 import os
 import re
@@ -14,8 +15,9 @@ import pytest
 import cluster_restatement as R
 import outlier_restatement as OR
 from align3d_amd import DevicePointCloud, PointCloud, _abi
-from cluster_cases import (CLUMP, N_CLUMPS, border_ties, bridge, chain, exact_chain, floaters_cloud, pairs_far_apart,
-                           pairs_far_apart_expected, raw_bits)
+from cluster_cases import (CLUMP, COMB_TEETH, COMB_TOOTH, N_CLUMPS, NOISE_SET, R_CONTENTION, SHEET_SIDE, border_ties, bridge,
+                           chain, chain_sets, comb, exact_chain, floaters_cloud, interleaved_lines, labels_of_sets,
+                           lattice_sheet, pairs_far_apart, pairs_far_apart_expected, raw_bits)
 from outlier_cases import N_OUTLIERS, RADIUS, effectiveness_cloud
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -317,3 +319,136 @@ def test_a_row_permutation_keeps_the_core_partition_the_noise_and_the_sizes():
     assert _partition(moved.labels, core) == sorted(tuple(sorted(int(np.flatnonzero(perm == r)[0]) for r in g))
                                                     for g in _partition(c.labels, np.flatnonzero(c.core)))
     assert sorted(moved.sizes.tolist()) == sorted(c.sizes.tolist())
+
+
+# ---- the clouds of test_gpu_cluster_contention.py, and the components routine that scales to them ------------------------
+
+
+def _same_clusters(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_hooking_components_give_the_quick_finds_clusters_on_every_cloud_of_this_file():
+    base, _ = effectiveness_cloud()
+    rng = np.random.default_rng(11)
+    mixed = np.r_[rng.uniform(-0.4, 0.4, size=(1500, 3)).astype(np.float32), raw_bits(12, 80),
+                  (rng.integers(-3, 3, size=(300, 3)) * np.float32(0.0625)).astype(np.float32)][rng.permutation(1880)]
+    cases = [(base, RADIUS, (1, 5)), (base, 0.05, (8,)), (np.r_[base, raw_bits(3, 20)], 0.05, (8,)),
+             (np.r_[base, raw_bits(3, 20)], 0.08, (12,)), (np.r_[base, raw_bits(3, 20)], RADIUS, (5, 1)),
+             (floaters_cloud()[0], RADIUS, (1,)), (bridge()[0], 0.05, (10, 3)), (border_ties()[0], 1.0, (5,)),
+             (exact_chain(10, 4), 0.25, (1,)), (mixed, 0.0625, (1, 6)), (mixed, 0.11, (1, 6)),
+             (base[np.random.default_rng(21).permutation(len(base))], 0.05, (8,))]
+    for order in ("ascending", "descending", "shuffled"):
+        cases += [(chain(65, order), 0.05, (1, 3)), (chain(65, order, stretch=(30, 1.001)), 0.05, (1,))]
+    cases += [(pairs_far_apart(n)[0], 0.02, (1, 2, 3)) for n in (3001, 3000)]
+    unions = 0
+    for points, radius, ms in cases:
+        pairs = R.pairs_by_cell(points, radius)
+        for m in ms:
+            quick, hooked = R.cluster_pairs(pairs, m), R.cluster_pairs(pairs, m, components="hooking")
+            assert _same_clusters(quick, hooked), (len(points), radius, m)
+            unions += int(quick.core.sum()) - len(quick.sizes)
+    assert unions > 10000
+    c = R.cluster(base, 0.05, 8, by_cell=True, components="hooking")  # the keyword of cluster()
+    assert _same_clusters(c, R.cluster(base, 0.05, 8)) and len(c.sizes) == 14
+    with pytest.raises(KeyError):
+        R.cluster(base, 0.05, 8, components="none")
+
+
+def _contention(points, m):
+    return R.cluster(points, R_CONTENTION, m, by_cell=True, components="hooking")
+
+
+def _is_construction(c, labels, sizes, roots):
+    return np.array_equal(c.labels, labels) and np.array_equal(c.sizes, sizes) and np.array_equal(c.roots, roots)
+
+
+def test_labels_of_sets_numbers_the_sets_by_their_lowest_core_row():
+    labels, sizes, roots = labels_of_sets([2, 0, NOISE_SET, 2, 0, 1, 1], core=[0, 1, 0, 1, 1, 0, 1])
+    assert labels.tolist() == [1, 0, NONE, 1, 0, 2, 2] and sizes.tolist() == [2, 2, 2] and roots.tolist() == [1, 3, 6]
+    labels, sizes, roots = labels_of_sets(np.full(3, NOISE_SET))
+    assert labels.tolist() == [NONE] * 3 and len(sizes) == len(roots) == 0
+
+
+@pytest.mark.parametrize("order", ("ascending", "descending", "shuffled"))
+def test_long_chains_are_one_cluster_and_two_at_a_stretched_link(order):
+    n = 70001
+    c = _contention(chain(n, order), 1)
+    assert c.sizes.tolist() == [n] and c.roots.tolist() == [0] and c.counts.max() == 3 and not c.labels.any()
+    k = n // 3
+    c = _contention(chain(n, order, stretch=(k, 1.001)), 1)
+    sets = chain_sets(n, order, k)
+    assert _is_construction(c, *labels_of_sets(sets)) and sorted(c.sizes.tolist()) == [k + 1, n - k - 1]
+    if order != "shuffled":  # row 0 is the chain's first point, or its last
+        assert c.roots.tolist() == ([0, k + 1] if order == "ascending" else [0, n - k - 1])
+
+
+@pytest.mark.parametrize("K", (2, 3, 64, 65, 1000))
+def test_interleaved_lines_are_one_cluster_a_line(K):
+    n = 20007
+    for descending in (False, True):
+        points, line, ends = interleaved_lines(n, K, descending)
+        assert np.array_equal(line, np.arange(n) % K) and ends.sum() == 2 * K
+        lengths = np.bincount(line)
+        c = _contention(points, 1)
+        assert np.array_equal(c.labels, line) and np.array_equal(c.roots, np.arange(K)) and np.array_equal(c.sizes, lengths)
+        assert c.counts.max() == 3 and np.array_equal(c.counts == 2, ends)
+        # min_points = 3: the two ends of a line are border rows of that line; the root is the lowest row that is no end
+        c = _contention(points, 3)
+        assert np.array_equal(c.labels, line) and np.array_equal(c.sizes, lengths) and np.array_equal(c.border, ends)
+        assert _is_construction(c, *labels_of_sets(line, ~ends)) and np.array_equal(c.roots, np.arange(K) + K)
+        c = _contention(points, 4)
+        assert c.noise.all() and len(c.sizes) == 0 and _is_construction(c, *labels_of_sets(np.full(n, NOISE_SET)))
+
+
+@pytest.mark.parametrize("side", (150, SHEET_SIDE))
+def test_lattice_sheet_counts_five_four_and_three(side):
+    points, kind = lattice_sheet(side)
+    n = side * side
+    assert (kind == 2).sum() == 4 and (kind == 3).sum() == 4 * (side - 2)
+    c = _contention(points, 1)
+    assert np.array_equal(c.counts, kind + 1) and c.sizes.tolist() == [n] and c.roots.tolist() == [0]
+    c = _contention(points, 5)
+    assert c.sizes.tolist() == [n - 4] and c.noise.sum() == 4 and c.border.sum() == 4 * (side - 2)
+    assert np.array_equal(c.noise, kind == 2) and np.array_equal(c.border, kind == 3)
+    assert c.roots.tolist() == [int(np.flatnonzero(kind == 4)[0])]  # the lowest interior row
+    assert _is_construction(c, *labels_of_sets(np.where(kind == 2, NOISE_SET, 0), kind == 4))
+    if side == 150:
+        assert c.sizes.tolist() == [22496] and c.border.sum() == 592
+    pairs = R.pairs_by_cell(points, R_CONTENTION)  # a border row has exactly one core neighbour
+    core_neighbours = np.bincount(pairs.i[c.core[pairs.j]], minlength=n)
+    assert (core_neighbours[c.border] == 1).all()
+    assert _contention(points, 6).noise.all()
+
+
+@pytest.mark.parametrize("shuffled", (False, True))
+def test_comb_is_one_cluster_and_two_without_one_spine_point(shuffled):
+    points, sets = comb(None, shuffled)
+    assert len(points) == COMB_TEETH * COMB_TOOTH + 2 * COMB_TEETH - 1
+    c = _contention(points, 1)
+    assert c.sizes.tolist() == [len(points)] and c.roots.tolist() == [0] and c.counts.max() == 4
+    cut = 40
+    points, sets = comb(cut, shuffled)
+    c = _contention(points, 1)
+    assert _is_construction(c, *labels_of_sets(sets)) and len(c.sizes) == 2
+    assert sorted(c.sizes.tolist()) == sorted([(cut + 1) * COMB_TOOTH + 2 * cut + 1,
+                                               (COMB_TEETH - cut - 1) * COMB_TOOTH + 2 * (COMB_TEETH - cut - 1) - 1])
+    if not shuffled:
+        assert c.roots.tolist() == [0, (cut + 1) * COMB_TOOTH]
+
+
+def test_hooking_partition_is_scipys_connected_components_on_the_sheet_and_the_comb():
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+
+    for points, m in ((lattice_sheet(SHEET_SIDE)[0], 5), (comb(40, True)[0], 1), (comb(None, True)[0], 1)):
+        n = len(points)
+        pairs = R.pairs_by_cell(points, R_CONTENTION)
+        c = R.cluster_pairs(pairs, m, components="hooking")
+        link = c.core[pairs.i] & c.core[pairs.j]
+        graph = coo_matrix((np.ones(int(link.sum())), (pairs.i[link], pairs.j[link])), shape=(n, n))
+        count, comp = connected_components(graph, directed=False)
+        core = np.flatnonzero(c.core)
+        assert count - (n - len(core)) == len(c.sizes)  # a row that is not core is a component of its own in the graph
+        both = np.unique(np.stack([comp[core], c.labels[core].astype(np.int64)], axis=1), axis=0)  # a bijection
+        assert len(both) == len(np.unique(both[:, 0])) == len(np.unique(both[:, 1])) == len(c.sizes)

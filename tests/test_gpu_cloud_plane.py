@@ -111,6 +111,46 @@ def test_size_grid(ctx):
     assert found > 30
 
 
+SPLIT_EDGE_HS = (127, 128, 129, 255, 256, 257, 511, 512, 513)
+
+
+@pytest.mark.parametrize("n", (300, 2049))
+def test_candidate_counts_at_the_edges_of_the_score_split(ctx, n):
+    """The product build splits the candidates of a score block's tile over grid.y = 1, 2, 4 or 8 blocks, doubling while
+    the largest H of the call is at least 128 per split: H from 128 is split in 2, from 256 in 4, from 512 in 8, and a
+    block's range is ceil(H / split) candidates, the last one shorter.  One H either side of each edge, against the
+    restatement."""
+    t = 0.03
+    points = _grid_cloud(n, n)
+    cloud = _device_cloud(ctx, points)
+    for H in SPLIT_EDGE_HS:
+        triples = R.hypotheses(2000 + H, n, H)
+        want = R.segment(points, triples, t)
+        assert want.best != NONE and (want.counts > 0).sum() > H // 2 and want.counts[-1] > 0 and len(np.unique(want.counts)) > 20
+        st, outs = _segment(ctx, [cloud], [triples], t)
+        assert st == _abi.A3D_OK, H
+        _assert_equal(outs[0], want, n)
+    cloud.free()
+
+
+@pytest.mark.parametrize("Hs", ((700, 5, 130), (4096, 1, 257)))
+def test_several_blocks_of_candidates_per_job_in_a_batch(ctx, Hs):
+    """The candidates kernel takes ceil(max H / 256) blocks per job and finds its job from the block index; here that is
+    3 and 16 blocks per job, for jobs of which two have fewer candidates than one block holds, and one has fewer
+    candidates than the score grid has splits."""
+    hosts = (np.r_[_grid_cloud(51, 3000), raw_bits(52, 30)], _grid_cloud(53, 65), _grid_cloud(54, 1025))
+    triples = [R.hypotheses(10 * Hs[0] + i, len(p), H) for i, (p, H) in enumerate(zip(hosts, Hs))]
+    clouds = [_device_cloud(ctx, p) for p in hosts]
+    st, outs = _segment(ctx, clouds, triples, 0.03, 1)
+    assert st == _abi.A3D_OK
+    for i, p in enumerate(hosts):
+        want = R.segment(p, triples[i], 0.03, 1)
+        assert Hs[i] == 1 or want.best != NONE
+        _assert_equal(outs[i], want, len(p))
+    for c in clouds:
+        c.free()
+
+
 def test_rows_at_exactly_the_threshold_on_exact_coordinates(ctx):
     points, triples, t, flags = exact_sheet()
     assert 0 < flags.sum() < len(flags) and flags[np.abs(points[:, 2]) == t].all() and len(np.unique(np.abs(points[:, 2]))) == 7
