@@ -270,13 +270,49 @@ __device__ __forceinline__ ProjPx stage_b(const LevelDesc& d, const Pose& T, con
   return o;
 }
 
+// The texels that the shifted samples of bilinear_grad (u + 0.005, v) and (u, v + 0.005) need beyond the cell at (u, v),
+// requested at the top of the step that consumes the pixel (pixel_pass), ahead of that step's prefetches, so that stage D
+// finds them landed behind the step's ordinary counted wait instead of draining the pipeline with loads of its own.
+// A lane leaves its cell in u by exactly one column: for u >= 0, fl(u + 0.005) <= u + 0.005 (1 + 2^-24) < floor(u) + 2
+// and fl(u + 0.005) >= u, so usize(u + 0.005) is usize(u) or usize(u) + 1; a u below 0 (a live lane's is above -1.5)
+// gives u + 0.005 < 0.005 and both cast to 0; a NaN casts to 0 twice.  Likewise v.  So the shifted cell in u is columns
+// ui + 1, ui + 2 of rows vi, vi + 1 — its first column is t10, t11 of the held cell — and the shifted cell in v is rows
+// vi + 1, vi + 2 of columns ui, ui + 1, its first row t01, t11.  (uh samples at v and vh at u: a lane that leaves in
+// both needs nothing more.)  Proven by exhaustion around every cut in tests/test_image_icp_resample_cpu.py.
+struct Shifted {
+  bool u_leaves, v_leaves;  // lanes whose shifted sample sits in the next texel
+  uint64_t leaving;         // ... of the whole wave, either way (wave-uniform: SGPRs, and the branches on it are scalar)
+  uint32_t ui, vi;          // usize(u), usize(v): computed once for the decision, stage C takes them from here
+  float c0, c1;             // u_leaves: column ui + 2 of rows vi, vi + 1
+  f32x2 r;                  // v_leaves: row vi + 2, columns ui, ui + 1
+};
+__device__ __forceinline__ Shifted request_shifted(const LevelDesc& d, const ProjPx& px, uint32_t mw) {
+  Shifted s;
+  const uint32_t ui = f32_as_usize(px.u), vi = f32_as_usize(px.v);  // (the instruction stage B used: the same bits)
+  const bool ul = f32_as_usize(px.u + 0.005f) != ui, vl = f32_as_usize(px.v + 0.005f) != vi;
+  s.ui = ui, s.vi = vi, s.u_leaves = ul, s.v_leaves = vl;
+  // (the wave's decision is taken on the compares alone, dead lanes included, so that it is two v_cmp into SGPR pairs and
+  // a scalar or: a mask that mixes in px.live costs the common path a v_cndmask and a v_cmp per pixel here and in stage D.
+  // Only lanes that are live after the bounds test load.)
+  s.leaving = __builtin_amdgcn_ballot_w64(ul) | __builtin_amdgcn_ballot_w64(vl);
+  if (__builtin_expect(s.leaving != 0ull, 0)) {
+    // In bounds: a lane that is live after the bounds test has ui <= tw - 1 and vi <= th - 1 (stage B), so columns up to
+    // ui + 2 <= tw + 1 and rows up to vi + 2 <= th + 1 lie inside the (th + 2) x (tw + 2) map.  A lane that is dead, or
+    // does not leave, loads nothing.  A lane that fails a gate in stage C has read valid texels that nothing uses.
+    const uint32_t mo = texel_offset(vi, mw, ui);
+    if (px.live & s.u_leaves) s.c0 = ld<float>(d.imap, mo + 8u), s.c1 = ld<float>(d.imap, mo + mw * 4u + 8u);
+    if (px.live & s.v_leaves) s.r = ld<f32x2_u>(d.imap, mo + mw * 8u);
+  }
+  return s;
+}
+
 struct MapPx {  // stage C: gates passed, the intensity-map cell
   float t00, t10, t01, t11;
   uint32_t ui, vi;
 };
 template <bool ZMASK = false, int D16 = 0, bool CLASSIC = false, bool SHORT = false>
 __device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, ProjPx& px, uint32_t mw,
-                                         const BackProj2& bp = BackProj2{}) {
+                                         const BackProj2& bp = BackProj2{}, const Shifted* sh = nullptr) {
   bool tvalid;
   if (D16 & D16_TGT) {  // the gathered depth lands here: the builder's function in its proven form, the same bits
     // (a u16 field widened by the compiler here was merged across the two unrolled steps and scheduled into stage B,
@@ -299,7 +335,8 @@ __device__ __forceinline__ MapPx stage_c(const LevelDesc& d, const Gates& gt, Pr
             & !(norm_squared(diff) > gt.max_distance_sqr)        // image_icp.rs:114
             & !((pn >= -1.0f) & (pn <= gt.dot_reject_max));
   MapPx m;
-  m.ui = f32_as_usize(px.u), m.vi = f32_as_usize(px.v);  // (the instruction stage B used: the same bits)
+  if (sh) m.ui = sh->ui, m.vi = sh->vi;  // (request_shifted converted them at the top of the step)
+  else m.ui = f32_as_usize(px.u), m.vi = f32_as_usize(px.v);  // (the instruction stage B used: the same bits)
   if (!CLASSIC) {  // stage B requested the cell: no load here
     m.t00 = px.t00, m.t10 = px.t10, m.t01 = px.t01, m.t11 = px.t11;
     return m;
@@ -320,7 +357,7 @@ struct Terms {  // stage D: the two residuals and Jacobians of a live pixel
 // that every per-pixel value is the oracle's bit for bit and only the order of the sums differs.
 template <bool EXACT = false>
 __device__ __forceinline__ Terms stage_d(const LevelDesc& d, const Gates& gt, const ProjPx& px, const MapPx& m,
-                                         uint8_t intensity, uint32_t mw) {
+                                         uint8_t intensity, uint32_t mw, const Shifted* sh = nullptr) {
   // What decides whether a pixel counts — the transform, the projection, the gates above, and here the colour
   // residual with its gate — is the reference's arithmetic operation for operation (no fused multiply-adds, IEEE
   // division).  What follows a passed gate only feeds the sums: the two Jacobians and the geometric residual may use
@@ -346,16 +383,27 @@ __device__ __forceinline__ Terms stage_d(const LevelDesc& d, const Gates& gt, co
   const float value = bilerp(m.t00, m.t10, m.t01, m.t11, uf, vf);  // exact: the colour gate reads it
   const float Hh = 0.005f, H_INV = 1.0f / 0.005f;
   const float u2 = px.u + Hh, v2 = px.v + Hh;
-  // the shifted samples share the cell except within 0.005 of a texel boundary: those (rare) lanes resample
-  // from memory, behind ONE wave-uniform branch so that the common path has no per-lane branches
+  // the shifted samples share the cell except within 0.005 of a texel boundary: those lanes (one in a hundred, but a
+  // third of the waves holds one) sample the next cell, behind ONE wave-uniform branch so that the common path has no
+  // per-lane branches
   // (uh, vh like `value`, operation for operation: du = (uh - value) / H amplifies a last-bit difference between the
   // two by value / (H * slope), three to four decimal orders)
   float uh = bilerp(m.t00, m.t10, m.t01, m.t11, u2 - (float)m.ui, vf);
   float vh = bilerp(m.t00, m.t10, m.t01, m.t11, uf, v2 - (float)m.vi);
-  const bool u_leaves = f32_as_usize(u2) != m.ui, v_leaves = f32_as_usize(v2) != m.vi;
-  if (__builtin_expect(__builtin_amdgcn_ballot_w64(u_leaves | v_leaves) != 0ull, 0)) {
-    if (u_leaves) uh = bilinear_at(d.imap, mw, u2, px.v);
-    if (v_leaves) vh = bilinear_at(d.imap, mw, px.u, v2);
+  if (sh) {
+    // pixel_pass decided and requested at the top of the step (Shifted): the shifted cells are one column to the right
+    // and one row down, half of each is held already — bilinear_at's texels and operands, with no load here
+    // (the lanes here passed the gates: a subset of those that loaded)
+    if (__builtin_expect((sh->leaving & __builtin_amdgcn_ballot_w64(true)) != 0ull, 0)) {
+      if (sh->u_leaves) uh = bilerp(m.t10, sh->c0, m.t11, sh->c1, u2 - (float)(m.ui + 1u), vf);
+      if (sh->v_leaves) vh = bilerp(m.t01, m.t11, sh->r.x, sh->r.y, uf, v2 - (float)(m.vi + 1u));
+    }
+  } else {
+    const bool u_leaves = f32_as_usize(u2) != m.ui, v_leaves = f32_as_usize(v2) != m.vi;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(u_leaves | v_leaves) != 0ull, 0)) {
+      if (u_leaves) uh = bilinear_at(d.imap, mw, u2, px.v);
+      if (v_leaves) vh = bilinear_at(d.imap, mw, px.u, v2);
+    }
   }
   const float du = (uh - value) * H_INV;
   const float dv = (vh - value) * H_INV;
@@ -553,12 +601,16 @@ __global__ void __launch_bounds__(256)
 // grid = (tiles, pairs); block = 256.  A thread visits `ppt` source pixels, 256 apart (coalesced), through a
 // three-deep software pipeline: the source record of pixel k+2 and every target-side load of pixel k+1 — the gathers
 // AND the intensity-map cell, whose address needs only the projection — are in flight while pixel k is consumed (58
-// per-thread f32 accumulators, wave reduce-scatter at the end).  One step: issue A(k+2); wait for the source record of
+// per-thread f32 accumulators, wave reduce-scatter at the end).  One step: decide which lanes of k sample their shifted
+// intensity in the next texel and, if any does, request the texels the held cell lacks (request_shifted: the step's oldest
+// loads, so the wait below covers them and stage D loads nothing — when stage D loaded them itself, as the wave's youngest
+// loads, a third of the level-0 steps drained the whole pipeline twice; that form is LATE, A3D_ICP_RESAMPLE=late of the
+// diagnostics build); issue A(k+2); wait for the source record of
 // k+1; B(k+1) with its four (masks read: five) loads back to back; then the step's one stall point, the wait for the
 // loads of k, which were requested a whole step (C(k-1) + D(k-1) + B(k+1), ~320 instructions) earlier; C(k), D(k) and the
 // accumulation.  (Before, C(k) came first and requested the cell of k behind its gates, ~115 instructions ahead of its
 // use, with a second wait per pixel; that order is CLASSIC, kept in the diagnostics build as a cross-check:
-// A3D_ICP_STEP_ORDER=classic.)  The cell travels in ProjPx: 112 VGPRs (116 with the masks read, and with DEPTH16's stride constants), four waves per SIMD.
+// A3D_ICP_STEP_ORDER=classic.)  The cell travels in ProjPx: 117 VGPRs (121 with the masks read, and with DEPTH16's stride constants), four waves per SIMD.
 // The pipeline is unrolled by two with the buffers swapping roles, so that the rotation cur <- nxt, s1 <- s2 costs no
 // register copies.  Reading the loop's s_waitcnt's in the ISA is part of maintaining this code
 // (profiles/steporder_isa_stats.txt): a short-circuit `&&` around a load, a u8 -> f32 conversion next to its load, a
@@ -573,7 +625,7 @@ __device__ __forceinline__ SrcPx pixel_source_at(const LevelDesc& d, uint32_t ba
   const uint32_t i = base + (uint32_t)k0 * 256u;
   return stage_a<ZMASK, D16>(d, i, (k0 < ppt) && (i < d.src_n), prev, stride);
 }
-template <bool ZMASK, int D16 = 0, bool CLASSIC = false, bool SHORT = false>
+template <bool ZMASK, int D16 = 0, bool CLASSIC = false, bool SHORT = false, bool LATE = false>
 __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, const Pose& T, uint32_t base, int ppt,
                                            const SrcPx& s0, SrcPx sa, float (&acc)[GN_PARTIAL]) {
   const uint32_t mw = d.tw + 2;
@@ -589,6 +641,10 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
   // one step: `cur` holds the projected pixel k, `s_next` the source record of pixel k+1 (consumed here); leaves the
   // projected pixel k+1 in `nxt` and the source record of pixel k+2 in `s_new`
   auto step = [&](ProjPx& cur, uint8_t cur_i, ProjPx& nxt, uint8_t& nxt_i, const SrcPx& s_next, SrcPx& s_new, int k0) {
+    // which lanes' shifted intensity samples leave the cell of k, and the request for their missing texels: the step's
+    // oldest loads, landed behind stage C's counted wait (LATE, diagnostics build only: stage D loads them itself)
+    Shifted sh;
+    if constexpr (!CLASSIC && !LATE) sh = request_shifted(d, cur, mw);
     s_new = pixel_source_at<ZMASK, D16>(d, base, ppt, k0 + 2, &s_next, &stride);  // issue source record k+2
     if constexpr (!CLASSIC) {
       // (the barriers pin the order A(k+2), B(k+1), C(k): left alone, the scheduler sinks stage B below stage C's wait
@@ -597,9 +653,9 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
       nxt = stage_b<ZMASK, D16, false, SHORT>(d, T, s_next, twf, thf, bp);  // source record k+1 lands; issue gathers and map cell(k+1)
       nxt_i = s_next.intensity;
       __builtin_amdgcn_sched_barrier(0);
-      const MapPx mp = stage_c<ZMASK, D16, false, SHORT>(d, gt, cur, mw, bp);  // the loads of k land: the step's one wait for them
+      const MapPx mp = stage_c<ZMASK, D16, false, SHORT>(d, gt, cur, mw, bp, LATE ? nullptr : &sh);  // the loads of k land: the step's one wait for them
       if (cur.live) {
-        const Terms t = stage_d(d, gt, cur, mp, cur_i, mw);
+        const Terms t = stage_d(d, gt, cur, mp, cur_i, mw, LATE ? nullptr : &sh);
         gn_step(acc, t.rg, t.Jg);  // the geometric term counts even when the colour term is rejected
         if (t.color) gn_step(acc + GN_ACC, t.rc, t.Jc);
       }
@@ -635,7 +691,7 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
 // CLASSIC (diagnostics build only): the step order of pixel_pass before B(k+1) moved ahead of C(k), as a cross-check.
 // SHORT (with DEPTH16): every focal length of the batch's level-0 images passes short_division_proven too, and the
 // rebuilt points divide by them in three operations (div_short) instead of five.
-template <bool ZMASK, bool DEPTH16, bool CLASSIC = false, bool SHORT = false>
+template <bool ZMASK, bool DEPTH16, bool CLASSIC = false, bool SHORT = false, bool LATE = false>
 __global__ void __launch_bounds__(256, 1)
     image_icp_head_kernel(const LevelDesc* __restrict__ descs, const JobState* __restrict__ states_in,
                           JobState* __restrict__ states_out, Gates gt, const float* __restrict__ partials_in,
@@ -670,7 +726,7 @@ __global__ void __launch_bounds__(256, 1)
   if ((int)s_state[15] == A3D_OK) {  // a failed job stays frozen: its blocks contribute nothing
     auto uni = [&](int k) { return __uint_as_float(__builtin_amdgcn_readfirstlane(s_state[k])); };
     const Pose T{{uni(0), uni(1), uni(2)}, {uni(3), uni(4), uni(5), uni(6)}};
-    pixel_pass<ZMASK, D16, CLASSIC, SHORT>(d, gt, T, base, ppt, s0, s1, acc);
+    pixel_pass<ZMASK, D16, CLASSIC, SHORT, LATE>(d, gt, T, base, ppt, s0, s1, acc);
   }
   A3D_HEAD_STAMP(3);  // pixel pass done
   block_reduce_store<GN_PARTIAL, false>(acc, partials_out + (size_t)pair * job_stride + (size_t)tile * GN_PARTIAL);
@@ -1486,6 +1542,25 @@ a3d_status launch_head_kernel(a3d_multiscale_batch* b, uint32_t level, uint32_t 
     else
       hipLaunchKernelGGL((image_icp_head_kernel<false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
                          st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    A3D_HIP_TRY(hipGetLastError());
+    return A3D_OK;
+  }
+  // A3D_ICP_RESAMPLE=late: the shifted intensity samples loaded by stage D itself, as before they were requested at the
+  // top of the step: the same bits
+  const char* renv = A3D_DIAG_ENV("A3D_ICP_RESAMPLE");
+  if (renv && strcmp(renv, "late") == 0) {
+    if (b->depth16 && level == 0 && b->short_div)
+      hipLaunchKernelGGL((image_icp_head_kernel<true, true, false, true, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
+                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    else if (b->depth16 && level == 0)
+      hipLaunchKernelGGL((image_icp_head_kernel<true, true, false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
+                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    else if (b->zmask)
+      hipLaunchKernelGGL((image_icp_head_kernel<true, false, false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
+                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    else
+      hipLaunchKernelGGL((image_icp_head_kernel<false, false, false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
+                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
     A3D_HIP_TRY(hipGetLastError());
     return A3D_OK;
   }
