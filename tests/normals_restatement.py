@@ -55,14 +55,16 @@ def cells(points, radius):
     return kept, np.where(kept[:, None], c, F(0)).astype(np.int64)
 
 
-def moments(points, radius, chunk=256, slab=True, rows=None):
+def moments(points, radius, chunk=256, slab=True, rows=None, rint=np.rint):
     """Steps 1-3: (kept [n] bool, N [n] int64, S [n, 3] int64, M [n, 3, 3] int64); zeros for dropped rows.
     rows: compute only these rows (against every candidate, as always) and leave the others zero: a subset of a cloud
     whose full pair count is out of reach.
     Brute force over all pairs of a chunk of rows and the candidate columns.  slab=True only leaves out columns that step
     2 refuses anyway: the rows are visited in the order of their x cell, and the candidates of a chunk are the kept points
     whose x cell lies within 1 of the chunk's range (a restriction the rule's own cell condition implies; slab=False
-    takes every kept point as a candidate and gives the same integers)."""
+    takes every kept point as a candidate and gives the same integers).
+    rint: the rounding of step 3, f32 array to f32 array.  The rule's is np.rint (ties to even); the edge-case tests pass
+    another one to show that their inputs tell the two apart."""
     p = np.ascontiguousarray(points, F).reshape(-1, 3)
     n = len(p)
     r = F(radius)
@@ -91,7 +93,7 @@ def moments(points, radius, chunk=256, slab=True, rows=None):
                 nb &= np.abs(cc[None, :, k] - cr[:, None, k]) <= 1
             # the pairs that are neighbours, row by row (a kept point is its own neighbour: no row is empty)
             ri, ci = np.nonzero(nb)
-            q = np.rint((pc[ci] - pr[ri]) * s).astype(np.int64)  # (the same subtraction again: the same bits as d)
+            q = rint((pc[ci] - pr[ri]) * s).astype(np.int64)  # (the same subtraction again: the same bits as d)
         count = nb.sum(axis=1)
         assert count.min() >= 1 and (np.diff(ri) >= 0).all()
         first = np.concatenate([[0], np.cumsum(count)[:-1]])
@@ -140,12 +142,13 @@ def jacobi(B):
     return np.stack([a[:, 0, 0], a[:, 1, 1], a[:, 2, 2]], axis=1), V
 
 
-def estimate_normals(points, radius, min_neighbors=3, viewpoint=None, old_normals=None, chunk=256, slab=True, rows=None):
+def estimate_normals(points, radius, min_neighbors=3, viewpoint=None, old_normals=None, chunk=256, slab=True, rows=None,
+                     rint=np.rint):
     """(normals [n, 3] f32, curvature [n] f32, counts [n] uint32, valid [n] bool).  old_normals: orient_by_normals.
     rows: only these rows are computed (see moments); the others come back as zeros and mean nothing."""
     p = np.ascontiguousarray(points, F).reshape(-1, 3)
     n = len(p)
-    kept, N, S, M = moments(p, radius, chunk, slab, rows)
+    kept, N, S, M = moments(p, radius, chunk, slab, rows, rint)
     A, mx = scatter_matrix(N, S, M)
     valid = kept & (N >= min_neighbors) & (mx > 0)
     normals, curvature = np.zeros((n, 3), F), np.zeros(n, F)

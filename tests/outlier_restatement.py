@@ -41,11 +41,12 @@ NONE = 0xFFFFFFFF
 FAR = np.int64(1) << 40  # what a candidate that is no other counts as among the lattice distances
 
 
-def knn_distance(points, radius, k, chunk=256, slab=True, rows=None):
+def knn_distance(points, radius, k, chunk=256, slab=True, rows=None, rint=np.rint):
     """(counts [n] uint32, qsum [n] uint32 or None when k == 0, stats (m, sum Q, sum Q^2 & 0xFFFFFFFF, sum Q^2 >> 32) as
     Python ints).  rows: compute only these rows (against every candidate, as always); the others come back as count 0 and
     qsum NONE and mean nothing, and the statistics are those of the computed rows.  slab: as normals_restatement.moments
-    (only columns that step 2 refuses anyway are left out)."""
+    (only columns that step 2 refuses anyway are left out).  rint: the rounding of step 4 (the rule's is np.rint, ties to
+    even; the edge-case tests pass another one to show that their inputs tell the two apart)."""
     assert 0 <= k <= 32
     p = np.ascontiguousarray(points, F).reshape(-1, 3)
     n = len(p)
@@ -77,7 +78,7 @@ def knn_distance(points, radius, k, chunk=256, slab=True, rows=None):
             counts[these] = nb.sum(axis=1)
             if k:
                 other = nb & (cols[None, :] != these[:, None])
-                lattice = np.rint(np.sqrt(np.where(other, d2, F(0))) * s)
+                lattice = rint(np.sqrt(np.where(other, d2, F(0))) * s)
                 assert lattice.dtype == F
                 t = np.where(other, lattice.astype(np.int64), FAR)
         if k:

@@ -121,8 +121,9 @@ def counts(points, triples, t, chunk=64):
     return out, best, (n, a, good)
 
 
-def moments(points, flags, point, t):
-    """Step 5: the record as 16 Python ints (S and Hi signed)."""
+def moments(points, flags, point, t, rint=np.rint):
+    """Step 5: the record as 16 Python ints (S and Hi signed).  rint: the rounding of q_k (the rule's is np.rint, ties to
+    even; the edge-case tests pass another one to show that their inputs tell the two apart)."""
     p = np.ascontiguousarray(points, F).reshape(-1, 3)
     a = np.asarray(point, F)
     s = F(64.0) / F(t)
@@ -131,7 +132,7 @@ def moments(points, flags, point, t):
         f = (p - a[None, :]) * s
         assert f.dtype == F
         part = np.asarray(flags, bool) & (np.abs(f) <= F(1048576.0)).all(axis=1)
-        q = np.rint(f[part]).astype(np.int64)
+        q = rint(f[part]).astype(np.int64)
     rec = [int(part.sum())] + [int(q[:, k].sum()) for k in range(3)]
     prods = [q[:, k] * q[:, l] for k, l in KL]
     rec += [int((P & 0x7FFFFFFF).sum()) for P in prods]
@@ -168,8 +169,8 @@ def plane_from_moments(rec, point, t, fallback):
     return plane, valid, c
 
 
-def segment(points, triples, t, refine=0):
-    """The whole rule for one cloud."""
+def segment(points, triples, t, refine=0, rint=np.rint):
+    """The whole rule for one cloud (rint: see moments)."""
     p = np.ascontiguousarray(points, F).reshape(-1, 3)
     triples = np.asarray(triples, np.int64).reshape(-1, 3)
     count, best, (n, a, _) = counts(p, triples, t)
@@ -179,7 +180,7 @@ def segment(points, triples, t, refine=0):
     records = []
     for _ in range(refine + 1):
         flags = inliers(p, cur_n, cur_a, t)
-        rec = moments(p, flags, cur_a, t)
+        rec = moments(p, flags, cur_a, t, rint)
         records.append(rec)
         plane, _, c = plane_from_moments(rec, cur_a, t, cur_n)
         cur_n, cur_a = plane[:3].astype(F), c.astype(F)
