@@ -53,6 +53,13 @@ class Context:
     def synchronize(self):
         _abi.check(self.lib.a3d_context_synchronize(self.handle))
 
+    def selftest_fill_scratch(self, byte):
+        """a3d_selftest_fill_scratch (test hook): every idle byte of the context (scratch regions, pooled image arenas,
+        spare kd-tree / Icp blocks) becomes `byte`.  Returns the bytes filled: [0..5] regions, [6] arenas, [7] blocks."""
+        out = (C.c_uint64 * 8)()
+        _abi.check(self.lib.a3d_selftest_fill_scratch(self.handle, int(byte), out), "a3d_selftest_fill_scratch")
+        return [int(v) for v in out]
+
     def timer_start(self):
         _abi.check(self.lib.a3d_timer_start(self.handle))
 

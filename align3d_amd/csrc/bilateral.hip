@@ -1033,10 +1033,13 @@ a3d_status bilateral_filter_device(a3d_context* ctx, const uint16_t* d_img, uint
     // (and grids whose cells 32-bit offsets can address: the fused kernels index them so)
     const bool fused = n < (1u << PACK_SHIFT) && grid_fits_idx32(g.gh, g.gw, g.gd) && !(mode && !strcmp(mode, "unfused"));
     // (growing the region synchronises; the stream is idle here anyway after the min/max read-back)
+    const size_t size_before = ctx->scratch_size[1];
     if (ctx_scratch(ctx, 1, 256 + 2 * grid_bytes, &scratch) != A3D_OK) {
       st = A3D_HIP_ERROR;
     } else {
-      if ((uint32_t*)scratch != d_scal) {  // the region moved: restore the flag word
+      // the region grew (a new allocation, possibly at the old address: the size tells, the pointer does not): restore
+      // the flag word that the upload above put into the old one
+      if (ctx->scratch_size[1] != size_before) {
         d_scal = (uint32_t*)scratch;
         if (hipMemsetAsync(d_scal, 0, 12, s) != hipSuccess) fail("flag reset");
       }

@@ -489,6 +489,39 @@ a3d_status a3d_context_synchronize(a3d_context* ctx) {
   return A3D_OK;
 }
 
+a3d_status a3d_selftest_fill_scratch(a3d_context* ctx, uint32_t byte, uint64_t out_bytes[8]) {
+  A3D_REQUIRE(ctx && out_bytes && byte <= 0xFF, A3D_INVALID_PARAMETER, "bad argument");
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  for (int k = 0; k < 8; ++k) out_bytes[k] = 0;
+  // everything enqueued on the context is done before idle memory changes under it
+  A3D_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  A3D_HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
+  {
+    std::lock_guard<std::mutex> lock(ctx->stream_mutex);
+    for (hipStream_t st : ctx->side_streams) A3D_HIP_TRY(hipStreamSynchronize(st));
+  }
+  for (int which = 0; which < 6; ++which)
+    if (ctx->scratch[which] && ctx->scratch_size[which]) {
+      A3D_HIP_TRY(hipMemset(ctx->scratch[which], (int)byte, ctx->scratch_size[which]));
+      out_bytes[which] = ctx->scratch_size[which];
+    }
+  // what region 1 held is gone, exactly as when it grows (ctx_scratch): the next filter enqueue clears its layout once
+  ctx->grid_clean = a3d_context::GridLayoutKey{};
+  {  // idle arenas (slab slices among them) and spare kd-tree / Icp blocks: nothing live points into either list
+    std::lock_guard<std::mutex> lock(ctx->pool_mutex);
+    for (const auto& a : ctx->arena_pool) {
+      A3D_HIP_TRY(hipMemset(a.first, (int)byte, a.second));
+      out_bytes[6] += a.second;
+    }
+    for (const auto& b : ctx->spare_blocks) {
+      A3D_HIP_TRY(hipMemset(b.p, (int)byte, b.bytes));
+      out_bytes[7] += b.bytes;
+    }
+  }
+  A3D_HIP_TRY(hipDeviceSynchronize());
+  return A3D_OK;
+}
+
 void* a3d_context_stream(a3d_context* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int32_t a3d_context_device(a3d_context* ctx) { return ctx ? (int32_t)ctx->device : -1; }
 int32_t a3d_context_num_cus(a3d_context* ctx) { return ctx ? (int32_t)ctx->num_cus : 0; }

@@ -409,6 +409,16 @@ a3d_status a3d_selftest_transform(a3d_context* ctx, const float* updates6, const
  * (numerator, denominator) pairs on the device and counts results that differ from IEEE `/`. */
 a3d_status a3d_selftest_division(a3d_context* ctx, const float* numerators, const float* denominators,
                                  uint64_t n, uint64_t* out_mismatches);
+/* Instrumentation: fills every byte of the context's memory that is idle between calls with `byte` (0 .. 255), so a test
+ * can show that a result does not depend on what an earlier call left there.  Host-synchronous: waits for the context's
+ * stream, copy stream and side streams, then fills each allocated scratch region over its whole size, every pooled image
+ * arena (slab slices included) and every spare kd-tree / Icp block, and forgets that the bilateral grid region is
+ * clean, as a growth of that region does.  Live images, cached tables, voxel maps, trees and whatever else a handle
+ * owns are not touched.  The contents of that memory between calls are unspecified anyway (growth discards them).
+ * Not thread-safe against the context: the regions and the grid key are changed with no lock held, so no other call on
+ * this context may run at the same time (image and handle frees from other threads, which take the pool's lock, may).
+ * out_bytes: the bytes filled, [0..5] the scratch regions, [6] pooled arenas, [7] spare blocks. */
+a3d_status a3d_selftest_fill_scratch(a3d_context* ctx, uint32_t byte, uint64_t out_bytes[8]);
 
 /* ---- MultiscaleAlign (src/icp/multiscale.rs:7-68) ---------------------------------------- */
 
