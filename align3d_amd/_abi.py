@@ -284,6 +284,24 @@ SIGNATURES = {
         _ST,
         [_P, C.POINTER(PoseC), C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_float, _P, _PP],
     ),
+    "a3d_tsdf_volume_new": (
+        _ST,
+        [_P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_float, C.POINTER(C.c_float), C.c_float, C.c_uint64, C.c_int, _PP],
+    ),
+    "a3d_tsdf_volume_free": (None, [_P]),
+    "a3d_tsdf_volume_clear": (_ST, [_P]),
+    "a3d_tsdf_volume_info": (
+        _ST,
+        [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64),
+         C.POINTER(C.c_int32)],
+    ),
+    "a3d_tsdf_volume_integrate": (_ST, [_P, _PP, C.POINTER(PoseC), C.c_uint64]),
+    "a3d_tsdf_volume_raycast": (
+        _ST,
+        [_P, C.POINTER(PoseC), C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
+         C.c_float, _PP],
+    ),
+    "a3d_tsdf_volume_download": (_ST, [_P, _P, _P]),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

@@ -130,8 +130,10 @@ SplatForm splat_setting() {
   return v == 0 ? SplatForm::ATOMIC : v == 1 ? SplatForm::CHECKED : RD_SPLAT;
 }
 
-// What both entries decide about the camera before anything is allocated or launched.
-a3d_status check_camera(double fx, double fy, double cx, double cy, uint64_t width, uint64_t height, float radius) {
+}  // namespace
+
+// What the render entries (and the TSDF raycast, tsdf.hip) decide about the camera before anything is allocated or launched.
+a3d_status a3d::check_camera(double fx, double fy, double cx, double cy, uint64_t width, uint64_t height, float radius) {
   A3D_REQUIRE(width >= 1 && height >= 1 && width < (1ull << 31) && height < (1ull << 31) && width * height < (1ull << 31),
               A3D_INVALID_PARAMETER, "render: the image has at least one pixel and fewer than 2^31");
   A3D_REQUIRE(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy), A3D_INVALID_PARAMETER,
@@ -142,6 +144,8 @@ a3d_status check_camera(double fx, double fy, double cx, double cy, uint64_t wid
   A3D_REQUIRE(std::isfinite(radius) && radius >= 0.0f, A3D_INVALID_PARAMETER, "render: the radius is finite and >= 0");
   return A3D_OK;
 }
+
+namespace {
 
 // The image's arena, the three launches and the one wait.  `zbuf`: [h][w] u64 of the context's scratch.  The cloud's
 // arrays may lie in that scratch region too (the map form).

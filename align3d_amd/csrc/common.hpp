@@ -85,6 +85,8 @@ a3d_status upload_pyramid(a3d_context* ctx, const a3d_range_image_view* views, u
 // RangeImage::compute_normals on device-resident arrays (image.hip).
 a3d_status compute_normals_device(a3d_context* ctx, const float* d_points, const uint8_t* d_mask, float* d_normals,
                                   uint32_t w, uint32_t h);
+// The camera refusals of a3d_point_cloud_render_device (cloud_render.hip), shared with the TSDF raycast (tsdf.hip).
+a3d_status check_camera(double fx, double fy, double cx, double cy, uint64_t width, uint64_t height, float radius);
 }  // namespace a3d
 
 namespace a3d {

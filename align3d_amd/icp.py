@@ -1536,6 +1536,117 @@ class DeviceVoxelMap:
             pass
 
 
+class DeviceTsdfVolume:
+    """A dense truncated signed distance volume in HBM (a3d_tsdf_volume_*): dims = (nx, ny, nz) voxels of pitch voxel_size,
+    the centre of voxel (0, 0, 0) at `origin` in the world.  Resident range images are fused into it along their viewing
+    rays (integrate: a running mean of the truncated projective distance, capped at max_weight observations; colors=True
+    keeps a running mean colour and every image must have colours), and raycast() gives the dense model image a camera
+    sees: points, normals from the distance field's gradient, colours, an ordinary DeviceRangeImage for pyramid(),
+    MultiscaleAlign and DevicePointCloud.from_range_image.  truncation defaults to 4 voxel sizes.  The rules are stated
+    in include/align3d_hip.h; every result is the same bits on every run."""
+
+    def __init__(self, ctx, dims, voxel_size, origin, truncation=None, max_weight=64, colors=False):
+        try:
+            nx, ny, nz = (int(d) for d in dims)
+        except (TypeError, ValueError):
+            raise TypeError("DeviceTsdfVolume: dims is (nx, ny, nz)") from None
+        o = np.ascontiguousarray(origin, np.float32).reshape(-1)
+        if o.size != 3:
+            raise _abi.InvalidParameter("DeviceTsdfVolume: the origin has three coordinates")
+        if min(nx, ny, nz) < 0 or int(max_weight) < 0:
+            raise _abi.InvalidParameter("DeviceTsdfVolume: dimensions and max_weight are positive")
+        self.ctx = ctx
+        self.dims = (nx, ny, nz)
+        self.voxel_size = float(voxel_size)
+        self.truncation = float(np.float32(4.0) * np.float32(voxel_size)) if truncation is None else float(truncation)
+        self.origin = o.copy()
+        self.max_weight = int(max_weight)
+        self.colors = bool(colors)
+        self.handle = C.c_void_p()
+        _abi.check(ctx.lib.a3d_tsdf_volume_new(ctx.handle, nx, ny, nz, self.voxel_size, (C.c_float * 3)(*o.tolist()),
+                                               self.truncation, self.max_weight, int(self.colors), C.byref(self.handle)),
+                   "a3d_tsdf_volume_new")
+
+    def integrate_many(self, images, poses):
+        """Fuses resident images of the volume's context, image f seen from the camera pose poses[f] (camera_to_world, a
+        Transform), in order and in ONE call: one read and at most one write of the volume per 64 frames."""
+        images, poses = list(images), list(poses)
+        for im in images:
+            if not isinstance(im, DeviceRangeImage):
+                raise TypeError(f"DeviceTsdfVolume.integrate takes DeviceRangeImages (got {type(im).__name__}); there is no host fallback")
+        for p in poses:
+            if not isinstance(p, Transform):
+                raise TypeError(f"DeviceTsdfVolume.integrate: camera_to_world is a Transform (got {type(p).__name__})")
+        if len(images) != len(poses):
+            raise _abi.InvalidParameter(f"DeviceTsdfVolume.integrate_many: {len(images)} images but {len(poses)} poses")
+        if not images:
+            return
+        w2c = (_abi.PoseC * len(poses))(*[p.inverse().to_c() for p in poses])
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_integrate(self.handle, _handle_array(images), w2c, len(images)),
+                   "a3d_tsdf_volume_integrate")
+
+    def integrate(self, image, camera_to_world):
+        """Fuses one resident image seen from camera_to_world."""
+        self.integrate_many([image], [camera_to_world])
+
+    def raycast(self, intrinsics, camera_to_world, z_near, z_far, step=None):
+        """The model image the camera `intrinsics` (a CameraIntrinsics: its width and height are the image's size) at
+        camera_to_world sees: every ray is sampled from z_near to z_far every `step` (default: half the truncation) and
+        stops at the first crossing from in front of a surface to behind it.  A new DeviceRangeImage with normals, with
+        colours iff the volume keeps them; the volume is not changed."""
+        if not isinstance(intrinsics, CameraIntrinsics):
+            raise TypeError(f"DeviceTsdfVolume.raycast takes a CameraIntrinsics (got {type(intrinsics).__name__})")
+        if not isinstance(camera_to_world, Transform):
+            raise TypeError(f"DeviceTsdfVolume.raycast: camera_to_world is a Transform (got {type(camera_to_world).__name__})")
+        k = intrinsics
+        if k.width < 0 or k.height < 0:
+            raise _abi.InvalidParameter(f"DeviceTsdfVolume.raycast: the camera's width and height are the image's size (got {k.width} x {k.height})")
+        if step is None:
+            step = float(np.float32(0.5) * np.float32(self.truncation))
+        pose = camera_to_world.to_c()
+        handle = C.c_void_p()
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_raycast(self.handle, C.byref(pose), k.fx, k.fy, k.cx, k.cy, k.width, k.height,
+                                                        float(z_near), float(z_far), float(step), C.byref(handle)),
+                   "a3d_tsdf_volume_raycast")
+        return DeviceRangeImage(self.ctx, handle=handle)
+
+    def download(self):
+        """(D, W, colours): host arrays [nz, ny, nx] float32 of the fused distance in units of the truncation and of the
+        observation count, and [nz, ny, nx, 3] uint8 of the colours (None for a volume without)."""
+        nx, ny, nz = self.dims
+        rec = np.empty((nz, ny, nx, 2), np.float32)
+        col = np.empty((nz, ny, nx), np.uint32) if self.colors else None
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_download(self.handle, _abi.ptr(rec), _abi.ptr(col)), "a3d_tsdf_volume_download")
+        rgb = None
+        if col is not None:
+            rgb = np.stack([col & 0xFF, (col >> 8) & 0xFF, (col >> 16) & 0xFF], -1).astype(np.uint8)
+        return np.ascontiguousarray(rec[..., 0]), np.ascontiguousarray(rec[..., 1]), rgb
+
+    def info(self):
+        """{dims, voxel_size, truncation, origin, max_weight, colors} as the library holds them (a3d_tsdf_volume_info)."""
+        dims, v, tau, o = (C.c_uint64 * 3)(), C.c_float(), C.c_float(), (C.c_float * 3)()
+        mw, col = C.c_uint64(), C.c_int32()
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_info(self.handle, dims, C.byref(v), C.byref(tau), o, C.byref(mw), C.byref(col)),
+                   "a3d_tsdf_volume_info")
+        return {"dims": tuple(int(d) for d in dims), "voxel_size": v.value, "truncation": tau.value,
+                "origin": tuple(float(x) for x in o), "max_weight": int(mw.value), "colors": bool(col.value)}
+
+    def clear(self):
+        """Back to "never observed" everywhere; the allocation stays."""
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_clear(self.handle), "a3d_tsdf_volume_clear")
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.a3d_tsdf_volume_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Icp:
     """Icp (src/icp/pcl_icp.rs:15-108): point-to-plane ICP with kd-tree correspondences.  `target` / `source` may be
     PointCloud (host arrays, as in the reference) or DevicePointCloud (already resident)."""

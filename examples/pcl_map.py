@@ -3,7 +3,7 @@
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
         [--voxel V [--mean] [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
         [--estimate-normals R] [--remove-plane T] [--radius-outliers R N] [--stat-outliers R K A] [--clusters R M S]
-        [--out map.npy]
+        [--tsdf-track V] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -47,7 +47,11 @@ floating clumps: the rows that are noise or belong to a cluster of fewer than S 
 min_points M (DevicePointCloud.remove_small_clusters_many; M = 1 is PCL's Euclidean cluster extraction with a minimum size).
 --remove-plane T runs before all of them: each frame's dominant plane (the floor, a wall or a table top: the rows within T
 metres of the best of 1000 candidate planes, DevicePointCloud.remove_plane_many, one segment call and one select call for
-all frames) stays out of the map, and the cluster filter then sees objects instead of one connected room.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+all frames) stays out of the map, and the cluster filter then sees objects instead of one connected room.  --tsdf-track V
+runs the --render-track loop against a dense model instead, on its own (no --voxel needed): every frame is fused into a
+DeviceTsdfVolume of voxel size V (truncation 4 V, with colours) that encloses the first frame's cloud with half a metre to
+spare, the model image is raycast from it at the predicted pose (samples every 2 V), and the same mean-trajectory-error
+line is printed; the map that follows is built from the odometry poses as without it.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -57,8 +61,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from align3d_amd import (A3dError, Context, DevicePointCloud, DeviceVoxelMap, Icp, IcpBatch, IcpParams,  # noqa: E402
-                         MsIcpParams, MultiscaleAlign, RangeImageBuilder, SlamTbDataset, Transform, TrajectoryBuilder)
+from align3d_amd import (A3dError, Context, DevicePointCloud, DeviceTsdfVolume, DeviceVoxelMap, Icp, IcpBatch,  # noqa: E402
+                         IcpParams, MsIcpParams, MultiscaleAlign, RangeImageBuilder, SlamTbDataset, Transform, TrajectoryBuilder)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("dataset", nargs="?", default=os.path.join(ROOT, "tests", "golden", "rgbd", "sample1"))
@@ -91,6 +95,8 @@ ap.add_argument("--stat-outliers", nargs=3, type=float, default=None, metavar=("
 ap.add_argument("--clusters", nargs=3, type=float, default=None, metavar=("R", "M", "S"),
                 help="before a frame's cloud goes into the map, drop the noise and the clusters of fewer than S rows of DBSCAN "
                      "with radius R metres and min_points M")
+ap.add_argument("--tsdf-track", type=float, default=None, metavar="V",
+                help="correct each frame's pose against a raycast of a TSDF volume of voxel size V that the frames are fused into")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
 args = ap.parse_args()
 if args.online and not args.voxel:
@@ -117,7 +123,7 @@ ds = SlamTbDataset.load(args.dataset)
 frames = [ds.get(i) for i in range(min(ds.len(), args.max_frames or ds.len()))]
 cam, _, _, depth_scale = frames[0]
 builder = RangeImageBuilder(ctx).pyramid_levels(1).with_intensity(False)
-if args.render_track:  # the frames are also the sources of the frame-to-model alignment: three levels, with intensities
+if args.render_track or args.tsdf_track is not None:  # the frames are also the sources of the frame-to-model alignment: three levels, with intensities
     builder = RangeImageBuilder(ctx).pyramid_levels(3)
 built = builder.build_many(cam, [(f[1], f[2]) for f in frames], depth_scale)
 images = [pyramid[0] for pyramid in built]
@@ -137,6 +143,44 @@ for k, (now_to_previous, st) in enumerate(zip(poses, status)):
     else:
         traj.accumulate(now_to_previous, float(k + 1))
     camera_to_world.append(traj.current_camera_to_world())
+
+
+
+def mean_error(truth, estimate):
+    """Mean distance of the estimated camera positions from the dataset's trajectory, frame 0 as the world."""
+    origin = truth.camera_to_world[0].inverse()
+    return float(np.mean([np.linalg.norm(e.t - (origin * truth.camera_to_world[i]).t) for i, e in enumerate(estimate)]))
+
+
+if args.tsdf_track is not None:  # frame-to-model tracking against a dense model: fuse, raycast, align, fuse
+    first = clouds[0].download()[0]
+    first = first[np.isfinite(first).all(axis=1)]
+    lo, hi = first.min(axis=0) - 0.5, first.max(axis=0) + 0.5  # frame 0 is the world
+    dims = np.clip(np.ceil((hi - lo) / args.tsdf_track).astype(np.int64) + 1, 2, 1024)
+    volume = DeviceTsdfVolume(ctx, dims, args.tsdf_track, lo, colors=True)
+    z_far = float(hi[2])
+    corrected = []
+    for k, image in enumerate(images):
+        pose = camera_to_world[0]
+        if k > 0:
+            pose = corrected[-1] * poses[k - 1] if status[k - 1] == 0 else corrected[-1]  # the odometry's prediction
+            model = volume.raycast(cam, pose, 0.3, z_far).pyramid(3)
+            try:
+                aligner = MultiscaleAlign.new(ctx, MsIcpParams.default(), model)
+                pose = pose * aligner.align(built[k])
+                aligner.free()
+            except A3dError as e:
+                print(f"frame {k}: no correction against the raycast volume ({e})")
+            for level in model:
+                level.free()
+        corrected.append(pose)
+        volume.integrate(image, pose)
+    print(f"tsdf volume {tuple(int(d) for d in dims)} voxels of {args.tsdf_track} m")
+    truth = ds.trajectory()
+    if truth is not None:
+        print(f"mean trajectory error over {len(corrected)} frames: odometry alone {mean_error(truth, camera_to_world):.4e} m, "
+              f"corrected against the raycast volume {mean_error(truth, corrected):.4e} m")
+    volume.free()
 
 # what goes into the map: the frames' clouds, cleaned if asked for (one plane, knn or cluster call and one select call per filter,
 # all frames)
@@ -224,11 +268,8 @@ if args.online:
     if args.render_track:
         truth = ds.trajectory()
         if truth is not None:
-            def mean_error(estimate):
-                origin = truth.camera_to_world[0].inverse()
-                return float(np.mean([np.linalg.norm(e.t - (origin * truth.camera_to_world[i]).t) for i, e in enumerate(estimate)]))
-            print(f"mean trajectory error over {len(corrected)} frames: odometry alone {mean_error(camera_to_world):.4e} m, "
-                  f"corrected against the rendered map {mean_error(corrected):.4e} m")
+            print(f"mean trajectory error over {len(corrected)} frames: odometry alone {mean_error(truth, camera_to_world):.4e} m, "
+                  f"corrected against the rendered map {mean_error(truth, corrected):.4e} m")
     # frame to map against the LIVE map: no extract, no kd-tree, and the frame stays in its own coordinates: the map's
     # association (DeviceVoxelMap.nearest) takes the tree's place and the alignment starts from the odometry pose
     aligned = online.align(clouds[-1], IcpParams.default(), initial=camera_to_world[-1])

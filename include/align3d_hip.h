@@ -1092,6 +1092,85 @@ a3d_status a3d_voxel_map_render(a3d_voxel_map* map, const a3d_pose* world_to_cam
                                 double cy, uint64_t width, uint64_t height, float radius, uint32_t* d_out_index,
                                 a3d_device_image** out_image);
 
+/* ---- Dense TSDF volume: fuse resident range images, raycast a model image ------------------- */
+
+/* A truncated signed distance volume of nx x ny x nz voxels of pitch v, the centre of voxel (0, 0, 0) at `origin` in the
+ * world, owned by its context like a voxel map.  Storage, x fastest: one 8-byte record {f32 D, f32 W} per voxel (D: the
+ * fused distance in units of the truncation tau, W: the number of observations, an integer held exactly in f32) and, with
+ * colours, a plane of one u32 r | g << 8 | b << 16 per voxel.  A new or cleared volume is all zero bytes (clearing is one
+ * fill); W == 0 is "never observed".  All device arithmetic below is f32 with every operation rounded on its own; poses go
+ * through Transform::transform_vector / transform_normal (src/transform.rs:138-153), the quaternion form.  Every call is
+ * host-synchronous and ordered on the context's stream; results depend neither on launch geometry nor on how often a call
+ * runs.  Hashed or sparse volumes, mesh extraction, along-ray distances, weights by angle or depth and de-integration are
+ * NOT built.
+ * a3d_tsdf_volume_new: decided on the host before anything is allocated (A3D_INVALID_PARAMETER, *out untouched): a NULL
+ * ctx, origin or out; a dimension outside [2, 1024]; voxel_size, truncation or an origin component that is not finite;
+ * voxel_size <= 0 or truncation <= 0; max_weight outside [1, 2^24].  Device memory: 8 (+ 4 with colours) bytes per voxel. */
+typedef struct a3d_tsdf_volume a3d_tsdf_volume;
+a3d_status a3d_tsdf_volume_new(a3d_context* ctx, uint64_t nx, uint64_t ny, uint64_t nz, float voxel_size,
+                               const float origin[3], float truncation, uint64_t max_weight, int with_colors,
+                               a3d_tsdf_volume** out);
+void a3d_tsdf_volume_free(a3d_tsdf_volume* volume);
+/* Every record and colour back to zero bytes; the allocation stays. */
+a3d_status a3d_tsdf_volume_clear(a3d_tsdf_volume* volume);
+/* What the volume was made with (any output may be NULL). */
+a3d_status a3d_tsdf_volume_info(const a3d_tsdf_volume* volume, uint64_t out_dims[3], float* out_voxel_size,
+                                float* out_truncation, float out_origin[3], uint64_t* out_max_weight,
+                                int32_t* out_with_colors);
+/* Fuses n >= 1 resident images, image f seen from world_to_camera_host[f] (PinholeCamera's world_to_camera), in order.
+ * The rule, per voxel (i, j, k), for f = 0 ... n-1 in that order (fx, fy, cx, cy: image f's intrinsics cast to f32 once):
+ *   1. pw = (ox + (float)i * v, oy + (float)j * v, oz + (float)k * v).
+ *   2. pc = transform_vector(world_to_camera[f], pw); z = pc.z; the frame is skipped unless z > 0 and z < +inf.
+ *   3. u = pc.x * fx / z + cx, v_ = pc.y * fy / z + cy; ui = round(u), vi = round(v_), halves away from zero; skipped unless
+ *      0 <= ui < width and 0 <= vi < height compared as f32: steps 3-4 of a3d_point_cloud_render_device
+ *      (src/camera.rs:177-202).
+ *   4. skipped if mask[vi][ui] == 0; dz = points[vi][ui].z; skipped unless dz > 0 and dz < +inf.
+ *   5. sdf = dz - z; skipped if sdf < -tau; d = min(1, sdf / tau).
+ *   6. Wn = W + 1; D = (D * W + d) / Wn; W = min(Wn, max_weight).
+ *   7. with colours, per channel c of the voxel and c_in of colors[vi][ui]: c = (u8)floor((c * W_old + c_in) / Wn + 0.5),
+ *      W_old the W step 6 started from.
+ * One thread per voxel keeps the record in registers over the frames of a launch: a call costs one read and at most one
+ * write of the volume per 64 frames (the host cuts n into chunks of at most 64, in order; the result is the rule's
+ * whatever the cut), and a voxel no frame touched is not written.
+ * Decided on the host before anything is launched, and then the volume is unchanged: a NULL volume, images, poses or
+ * image, n == 0, an image of another context -> A3D_INVALID_PARAMETER; an image without colours offered to a volume with
+ * colours -> A3D_MISSING_FIELD. */
+a3d_status a3d_tsdf_volume_integrate(a3d_tsdf_volume* volume, const a3d_device_image* const* images,
+                                     const a3d_pose* world_to_camera_host, uint64_t n);
+/* The model image a pinhole camera at camera_to_world_host sees: one ray per pixel, sampled at fixed depths.  The rule, per
+ * pixel (row, col), with the intrinsics cast to f32 once, g(p) = (transform_vector(camera_to_world, p) - origin) / v per
+ * component, and world_to_camera = (q* = (-i, -j, -k, w), -(q* rotating t)) computed once on the host in f32:
+ *   1. xn = ((float)col - cx) / fx, yn = ((float)row - cy) / fy.
+ *   2. sample k = 0 ... K-1 is at z_k = z_near + (float)k * step (not accumulated), at g_k = g((xn * z_k, yn * z_k, z_k));
+ *      K = floor((z_far - z_near) / step) + 1, computed on the host in f64 from the f32 values.
+ *   3. tri(g), the trilinear sample: i0 = floor(g.x), j0, k0 likewise; valid iff 0 <= i0 and i0 + 1 <= nx - 1, the same
+ *      for j0 and k0, tested in f32 (a NaN fails), AND all eight corner voxels have W > 0; its value is
+ *      lerp(a, b, t) = a + t * (b - a) over the corners' D along x first, then y, then z, with t = g - floor(g).
+ *   4. walking k upwards, an invalid sample forgets the previous one; a valid sample D after a valid sample D_prev:
+ *      D_prev > 0 and D <= 0 is a HIT; D_prev <= 0 and D > 0 ends the ray without one (it left a surface from behind); a
+ *      first valid sample with D <= 0 is never a hit.
+ *   5. on a hit: s = D_prev / (D_prev - D), z* = z_prev + (z_k - z_prev) * s; the pixel gets mask 1 and the point
+ *      p* = (xn * z*, yn * z*, z*).
+ *   6. the normal: g* = g(p*), G = (tri(g* + ex) - tri(g* - ex), the same with ey, with ez) at unit voxel offsets,
+ *      len = sqrt(Gx * Gx + Gy * Gy + Gz * Gz) summed left to right; +0 if one of the six samples is invalid or len is 0 or
+ *      not finite (every aligner's angle gate rejects it; the mask stays 1), else transform_normal(world_to_camera, G / len).
+ *      D grows towards the camera: a wall seen head-on gets (0, 0, -1), RangeImage::compute_normals' sign
+ *      (src/range_image/structure.rs:250).
+ *   7. the colour is that of voxel round(g*), halves away from zero, clamped into the volume; 0, 0, 0 without colours.
+ *   8. a pixel without a hit gets mask 0, +0 points and normals and colour 0, 0, 0.
+ * There is no empty-space skipping: it would change which samples a ray sees.  *out_image: an ordinary image on the
+ * volume's context (a3d_range_image_free) that carries fx, fy, cx, cy as given, always has normals, has colours iff the
+ * volume has them and no intensities.  One thread per pixel, one launch.
+ * Decided on the host before anything is launched or allocated (A3D_INVALID_PARAMETER, *out_image untouched): a NULL
+ * volume, pose or out_image; the camera refusals of a3d_point_cloud_render_device; z_near, z_far or step not finite,
+ * z_near <= 0, z_far <= z_near, step <= 0; K > 4096. */
+a3d_status a3d_tsdf_volume_raycast(a3d_tsdf_volume* volume, const a3d_pose* camera_to_world_host, double fx, double fy,
+                                   double cx, double cy, uint64_t width, uint64_t height, float z_near, float z_far,
+                                   float step, a3d_device_image** out_image);
+/* The volume to HOST memory, for tests: out_records [nz][ny][nx][2] f32 (D, W), out_colors [nz][ny][nx] u32 (NULL ok; non-NULL
+ * on a volume without colours -> A3D_MISSING_FIELD).  A NULL volume or out_records is A3D_INVALID_PARAMETER. */
+a3d_status a3d_tsdf_volume_download(a3d_tsdf_volume* volume, float* out_records, uint32_t* out_colors);
+
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
 /* R3dTree::new(&points): `points` [n][3] f32 in host memory are uploaded and the tree is built ON THE DEVICE
