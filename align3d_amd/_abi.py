@@ -302,6 +302,11 @@ SIGNATURES = {
          C.c_float, _PP],
     ),
     "a3d_tsdf_volume_download": (_ST, [_P, _P, _P]),
+    "a3d_tsdf_volume_upload": (_ST, [_P, _P, _P]),
+    "a3d_tsdf_volume_extract_surface": (
+        _ST,
+        [_P, C.c_uint64, C.c_int, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    ),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

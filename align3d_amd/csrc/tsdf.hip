@@ -15,36 +15,17 @@
 #include <cmath>
 #include <vector>
 
-#include "cloud_batch.hpp"
+#include "tsdf.hpp"
 
 using namespace a3d;
-
-struct a3d_tsdf_volume {
-  a3d_context* ctx = nullptr;
-  uint32_t nx = 0, ny = 0, nz = 0, max_weight = 0;
-  float v = 0.f, tau = 0.f, ox = 0.f, oy = 0.f, oz = 0.f;
-  bool with_colors = false;
-  void* block = nullptr;  // records | colours, one block of the context's
-  size_t block_bytes = 0, used_bytes = 0;
-  float2* records = nullptr;   // [nz][ny][nx] {D, W}
-  uint32_t* colors = nullptr;  // [nz][ny][nx] r | g << 8 | b << 16, or null
-};
 
 namespace {
 
 constexpr uint32_t TS_THREADS = 256;
 constexpr uint32_t TS_MIN_DIM = 2, TS_MAX_DIM = 1024;  // 2^30 voxels at most: a voxel's number fits 32 bits
-constexpr uint64_t TS_MAX_WEIGHT = 1ull << 24;         // integers up to here are exact in f32
 constexpr uint64_t TS_CHUNK = 64;                      // frames per launch
 constexpr double TS_MAX_SAMPLES = 4096.0;
 constexpr size_t TS_COLOR_SLACK = 16;  // bytes readable past a colour plane's end, as a3d_range_image_set_colors leaves
-
-struct TsdfGrid {
-  float2* records;
-  uint32_t* colors;
-  uint32_t nx, ny, nz, total;
-  float v, tau, ox, oy, oz, max_weight;
-};
 
 struct TsdfFrame {
   const float* points;    // [h][w][3], the camera's frame
@@ -111,36 +92,10 @@ struct RayJob {
   uint32_t width, height, samples;
 };
 
-__device__ __forceinline__ float lerp(float a, float b, float t) { return a + t * (b - a); }
-
-// Step 3 of the raycast rule.  Every index it loads from is inside the volume: 0 <= i0 and i0 + 1 <= nx - 1 on each axis.
-__device__ __forceinline__ bool tri(const TsdfGrid& g, V3 p, float* out) {
-  const float fx0 = floorf(p.x), fy0 = floorf(p.y), fz0 = floorf(p.z);
-  if (!(fx0 >= 0.0f && fx0 + 1.0f <= (float)(g.nx - 1) && fy0 >= 0.0f && fy0 + 1.0f <= (float)(g.ny - 1) && fz0 >= 0.0f &&
-        fz0 + 1.0f <= (float)(g.nz - 1)))
-    return false;  // (NaN and the infinities fail)
-  const size_t sx = 1, sy = g.nx, sz = (size_t)g.nx * g.ny;
-  const float2* c = g.records + ((size_t)(uint32_t)fz0 * sz + (size_t)(uint32_t)fy0 * sy + (uint32_t)fx0);
-  const float2 c000 = c[0], c100 = c[sx], c010 = c[sy], c110 = c[sy + sx];
-  const float2 c001 = c[sz], c101 = c[sz + sx], c011 = c[sz + sy], c111 = c[sz + sy + sx];
-  if (!(c000.y > 0.0f && c100.y > 0.0f && c010.y > 0.0f && c110.y > 0.0f && c001.y > 0.0f && c101.y > 0.0f &&
-        c011.y > 0.0f && c111.y > 0.0f))
-    return false;
-  const float tx = p.x - fx0, ty = p.y - fy0, tz = p.z - fz0;
-  const float c00 = lerp(c000.x, c100.x, tx), c10 = lerp(c010.x, c110.x, tx);
-  const float c01 = lerp(c001.x, c101.x, tx), c11 = lerp(c011.x, c111.x, tx);
-  *out = lerp(lerp(c00, c10, ty), lerp(c01, c11, ty), tz);
-  return true;
-}
-
 // g(p) of the rule: a camera-frame point in voxel coordinates.
 __device__ __forceinline__ V3 voxel_coordinate(const TsdfGrid& g, const RayJob& j, V3 pc) {
   const V3 pw = transform_vector(j.camera_to_world, pc);
   return V3{(pw.x - g.ox) / g.v, (pw.y - g.oy) / g.v, (pw.z - g.oz) / g.v};
-}
-
-__device__ __forceinline__ uint32_t clamped_voxel(float coordinate, uint32_t n) {
-  return (uint32_t)fminf(fmaxf(roundf(coordinate), 0.0f), (float)(n - 1));
 }
 
 __global__ void __launch_bounds__(TS_THREADS)
@@ -195,14 +150,6 @@ __global__ void __launch_bounds__(TS_THREADS)
   out_mask[px] = hit ? 1 : 0;
   *(f32x3_u*)(out_normals + 3 * (size_t)px) = n;
   if (out_colors) store_color(out_colors, px, rgb);
-}
-
-TsdfGrid grid_of(const a3d_tsdf_volume* vol) {
-  TsdfGrid g{};
-  g.records = vol->records, g.colors = vol->colors;
-  g.nx = vol->nx, g.ny = vol->ny, g.nz = vol->nz, g.total = vol->nx * vol->ny * vol->nz;
-  g.v = vol->v, g.tau = vol->tau, g.ox = vol->ox, g.oy = vol->oy, g.oz = vol->oz, g.max_weight = (float)vol->max_weight;
-  return g;
 }
 
 // Transform::inverse in f32: q* = (-i, -j, -k, w), t' = -(q* rotating t).
@@ -402,6 +349,19 @@ a3d_status a3d_tsdf_volume_download(a3d_tsdf_volume* volume, float* out_records,
   const size_t total = (size_t)volume->nx * volume->ny * volume->nz;
   A3D_HIP_TRY(hipMemcpyAsync(out_records, volume->records, total * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
   if (out_colors) A3D_HIP_TRY(hipMemcpyAsync(out_colors, volume->colors, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+  A3D_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return A3D_OK;
+}
+
+a3d_status a3d_tsdf_volume_upload(a3d_tsdf_volume* volume, const float* records, const uint32_t* colors) {
+  A3D_REQUIRE(volume && records, A3D_INVALID_PARAMETER, "null argument");
+  A3D_REQUIRE(!colors || volume->with_colors, A3D_MISSING_FIELD, "a3d_tsdf_volume_upload: the volume has no colours");
+  a3d_context* ctx = volume->ctx;
+  A3D_HIP_TRY(hipSetDevice(ctx->device));
+  const size_t total = (size_t)volume->nx * volume->ny * volume->nz;
+  A3D_HIP_TRY(hipMemcpyAsync(volume->records, records, total * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+  if (colors) A3D_HIP_TRY(hipMemcpyAsync(volume->colors, colors, total * 4, hipMemcpyHostToDevice, ctx->stream));
+  // host-synchronous: the caller's arrays may go right after
   A3D_HIP_TRY(hipStreamSynchronize(ctx->stream));
   return A3D_OK;
 }

@@ -1536,6 +1536,43 @@ class DeviceVoxelMap:
             pass
 
 
+class DeviceTriangleMesh:
+    """A triangle mesh resident in HBM, the reference's Geometry (src/io/geometry.rs) with faces: `vertices` is a
+    DevicePointCloud with normals (and colours iff the source had them), `d_faces` [len_faces][3] u32 vertex indices in
+    device memory.  Made by DeviceTsdfVolume.extract_triangle_mesh; it owns its buffers (`free()`)."""
+
+    def __init__(self, vertices, d_faces, len_faces):
+        self.ctx = vertices.ctx
+        self.vertices = vertices
+        self.d_faces = d_faces
+        self.len_faces = int(len_faces)
+
+    @property
+    def len_vertices(self):
+        return self.vertices.len()
+
+    def download(self):
+        """{points [V, 3] f32, normals [V, 3] f32, colors [V, 3] u8 or None, faces [F, 3] u32} on the host: Geometry's
+        field names."""
+        points, normals = self.vertices.download()
+        faces = (self.ctx.to_host(self.d_faces, np.empty((self.len_faces, 3), np.uint32)) if self.len_faces
+                 else np.empty((0, 3), np.uint32))
+        return {"points": points, "normals": normals, "colors": self.vertices.download_colors(), "faces": faces}
+
+    def free(self):
+        if self.vertices is not None:
+            self.vertices.free()
+        if self.d_faces is not None and self.ctx.handle:
+            self.ctx.free(self.d_faces)
+        self.d_faces = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class DeviceTsdfVolume:
     """A dense truncated signed distance volume in HBM (a3d_tsdf_volume_*): dims = (nx, ny, nz) voxels of pitch voxel_size,
     the centre of voxel (0, 0, 0) at `origin` in the world.  Resident range images are fused into it along their viewing
@@ -1621,6 +1658,61 @@ class DeviceTsdfVolume:
         if col is not None:
             rgb = np.stack([col & 0xFF, (col >> 8) & 0xFF, (col >> 16) & 0xFF], -1).astype(np.uint8)
         return np.ascontiguousarray(rec[..., 0]), np.ascontiguousarray(rec[..., 1]), rgb
+
+    def upload(self, D, W, colors=None):
+        """The inverse of download(): every voxel's D and W ([nz, ny, nx] float32, any bit pattern) and, with `colors`
+        ([nz, ny, nx, 3] uint8), every colour; colors=None leaves the colours as they are.  Restores a saved volume."""
+        nx, ny, nz = self.dims
+        D, W = np.asarray(D, np.float32), np.asarray(W, np.float32)
+        if D.shape != (nz, ny, nx) or W.shape != (nz, ny, nx):
+            raise _abi.InvalidParameter(f"DeviceTsdfVolume.upload: D and W are [nz, ny, nx] = {(nz, ny, nx)} arrays")
+        rec = np.empty((nz, ny, nx, 2), np.float32)
+        rec.view(np.uint32)[..., 0], rec.view(np.uint32)[..., 1] = D.view(np.uint32), W.view(np.uint32)  # (NaN payloads too)
+        col = None
+        if colors is not None:
+            c = np.asarray(colors, np.uint8)
+            if c.shape != (nz, ny, nx, 3):
+                raise _abi.InvalidParameter("DeviceTsdfVolume.upload: colors is a [nz, ny, nx, 3] uint8 array")
+            c = c.astype(np.uint32)
+            col = np.ascontiguousarray(c[..., 0] | c[..., 1] << 8 | c[..., 2] << 16)
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_upload(self.handle, _abi.ptr(rec), _abi.ptr(col)), "a3d_tsdf_volume_upload")
+
+    def _extract(self, min_weight, want_faces, normals, colors):
+        """Count-only first, then exactly sized buffers: (vertices: DevicePointCloud, d_faces or None, faces)."""
+        ctx, lib = self.ctx, self.ctx.lib
+        nv, nf = C.c_uint64(), C.c_uint64()
+        _abi.check(lib.a3d_tsdf_volume_extract_surface(self.handle, int(min_weight), int(want_faces), None, None, None, 0, None, 0,
+                                                       C.byref(nv), C.byref(nf)), "a3d_tsdf_volume_extract_surface")
+        cloud = DevicePointCloud._allocate(ctx, nv.value, normals, colors)
+        d_faces = None
+        try:
+            if want_faces:
+                d_faces = ctx.malloc(max(1, nf.value) * 12)
+            _abi.check(lib.a3d_tsdf_volume_extract_surface(self.handle, int(min_weight), int(want_faces), cloud.d_points,
+                                                           cloud.d_normals, cloud.d_colors, nv.value, d_faces, nf.value,
+                                                           C.byref(nv), C.byref(nf)), "a3d_tsdf_volume_extract_surface")
+        except BaseException:
+            cloud.free()
+            if d_faces is not None:
+                ctx.free(d_faces)
+            raise
+        return cloud, d_faces, int(nf.value)
+
+    def extract_point_cloud(self, min_weight=1, normals=True, colors=None):
+        """The surface as a new DevicePointCloud that depends on no viewpoint: one point on every axis edge of the voxel
+        grid whose ends are both observed at least min_weight times and lie on different sides of the surface (Open3D's
+        extract_point_cloud), in voxel order, in the world frame, with the field's gradient as the normal (pointing out of
+        the surface; zero beside unobserved voxels) and the nearest voxel's colour.  colors=None: iff the volume keeps
+        colours; colors=True on a volume without raises A3D_MISSING_FIELD.  The same bits on every run."""
+        colors = self.colors if colors is None else bool(colors)
+        return self._extract(min_weight, False, bool(normals), colors)[0]
+
+    def extract_triangle_mesh(self, min_weight=1):
+        """The surface as a new DeviceTriangleMesh: marching tetrahedra on the Kuhn split of every cell whose eight
+        corners are observed at least min_weight times (about twice the triangles of marching cubes, no ambiguous case),
+        wound counter-clockwise seen from outside; the vertices carry normals, and colours iff the volume keeps them."""
+        cloud, d_faces, faces = self._extract(min_weight, True, True, self.colors)
+        return DeviceTriangleMesh(cloud, d_faces, faces)
 
     def info(self):
         """{dims, voxel_size, truncation, origin, max_weight, colors} as the library holds them (a3d_tsdf_volume_info)."""

@@ -3,7 +3,7 @@
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
         [--voxel V [--mean] [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
         [--estimate-normals R] [--remove-plane T] [--radius-outliers R N] [--stat-outliers R K A] [--clusters R M S]
-        [--tsdf-track V] [--out map.npy]
+        [--tsdf-track V [--tsdf-mesh FILE]] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -51,7 +51,10 @@ all frames) stays out of the map, and the cluster filter then sees objects inste
 runs the --render-track loop against a dense model instead, on its own (no --voxel needed): every frame is fused into a
 DeviceTsdfVolume of voxel size V (truncation 4 V, with colours) that encloses the first frame's cloud with half a metre to
 spare, the model image is raycast from it at the predicted pose (samples every 2 V), and the same mean-trajectory-error
-line is printed; the map that follows is built from the odometry poses as without it.  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
+line is printed; the map that follows is built from the odometry poses as without it.  --tsdf-mesh FILE then takes the
+fused volume's surface out as a triangle mesh (DeviceTsdfVolume.extract_triangle_mesh, observed at least twice) and as a
+point cloud (extract_point_cloud), prints their counts and saves points, normals, colors and faces to FILE as an .npz (file
+formats such as PLY are out of scope).  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
 import argparse
 import collections
 import os
@@ -97,6 +100,8 @@ ap.add_argument("--clusters", nargs=3, type=float, default=None, metavar=("R", "
                      "with radius R metres and min_points M")
 ap.add_argument("--tsdf-track", type=float, default=None, metavar="V",
                 help="correct each frame's pose against a raycast of a TSDF volume of voxel size V that the frames are fused into")
+ap.add_argument("--tsdf-mesh", default=None, metavar="FILE",
+                help="with --tsdf-track: save the fused volume's surface (points, normals, colors, faces) to this .npz file")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
 args = ap.parse_args()
 if args.online and not args.voxel:
@@ -116,6 +121,8 @@ if args.render_track and not args.online:
     ap.error("--render-track needs --online")
 if args.render_track and args.check_batch:
     ap.error("--check-batch compares maps built under the same poses: not with --render-track")
+if args.tsdf_mesh and args.tsdf_track is None:
+    ap.error("--tsdf-mesh needs --tsdf-track")
 args.colors = args.colors or args.render_track  # (the intensity term reads the map's colours)
 
 ctx = Context(0)
@@ -180,6 +187,12 @@ if args.tsdf_track is not None:  # frame-to-model tracking against a dense model
     if truth is not None:
         print(f"mean trajectory error over {len(corrected)} frames: odometry alone {mean_error(truth, camera_to_world):.4e} m, "
               f"corrected against the raycast volume {mean_error(truth, corrected):.4e} m")
+    if args.tsdf_mesh:  # the surface of what was fused, independent of any viewpoint
+        mesh, surface = volume.extract_triangle_mesh(min_weight=2), volume.extract_point_cloud(min_weight=2)
+        print(f"tsdf surface (observed at least twice): mesh of {mesh.len_vertices} vertices and {mesh.len_faces} triangles, "
+              f"point cloud of {surface.len()} points")
+        np.savez(args.tsdf_mesh, **mesh.download())
+        mesh.free(), surface.free()
     volume.free()
 
 # what goes into the map: the frames' clouds, cleaned if asked for (one plane, knn or cluster call and one select call per filter,

@@ -1101,8 +1101,8 @@ a3d_status a3d_voxel_map_render(a3d_voxel_map* map, const a3d_pose* world_to_cam
  * fill); W == 0 is "never observed".  All device arithmetic below is f32 with every operation rounded on its own; poses go
  * through Transform::transform_vector / transform_normal (src/transform.rs:138-153), the quaternion form.  Every call is
  * host-synchronous and ordered on the context's stream; results depend neither on launch geometry nor on how often a call
- * runs.  Hashed or sparse volumes, mesh extraction, along-ray distances, weights by angle or depth and de-integration are
- * NOT built.
+ * runs.  The surface leaves the volume as a triangle mesh or a point cloud through a3d_tsdf_volume_extract_surface below.
+ * Hashed or sparse volumes, marching cubes, along-ray distances, weights by angle or depth and de-integration are NOT built.
  * a3d_tsdf_volume_new: decided on the host before anything is allocated (A3D_INVALID_PARAMETER, *out untouched): a NULL
  * ctx, origin or out; a dimension outside [2, 1024]; voxel_size, truncation or an origin component that is not finite;
  * voxel_size <= 0 or truncation <= 0; max_weight outside [1, 2^24].  Device memory: 8 (+ 4 with colours) bytes per voxel. */
@@ -1170,6 +1170,57 @@ a3d_status a3d_tsdf_volume_raycast(a3d_tsdf_volume* volume, const a3d_pose* came
 /* The volume to HOST memory, for tests: out_records [nz][ny][nx][2] f32 (D, W), out_colors [nz][ny][nx] u32 (NULL ok; non-NULL
  * on a volume without colours -> A3D_MISSING_FIELD).  A NULL volume or out_records is A3D_INVALID_PARAMETER. */
 a3d_status a3d_tsdf_volume_download(a3d_tsdf_volume* volume, float* out_records, uint32_t* out_colors);
+/* The inverse of a3d_tsdf_volume_download: every record (and, with `colors`, every colour) of the volume from HOST memory,
+ * bit for bit, NaN included: records [nz][ny][nx][2] f32 (D, W), colors [nz][ny][nx] u32 (NULL: the colours stay as they
+ * are; non-NULL on a volume without colours -> A3D_MISSING_FIELD).  A NULL volume or records is A3D_INVALID_PARAMETER.  It
+ * restores a saved volume, and lets a test set any field: exact zeros, -0, ties, holes. */
+a3d_status a3d_tsdf_volume_upload(a3d_tsdf_volume* volume, const float* records, const uint32_t* colors);
+/* The volume's surface, independent of any viewpoint: a vertex on every crossing edge, with the field's gradient as its
+ * normal and a voxel's colour, and (want_faces != 0) triangles by marching TETRAHEDRA on the Kuhn split of every cell, not
+ * marching cubes: the split matches across neighbouring cells, has no ambiguous case and its table is derived from the
+ * paragraph below, at the price of about twice the triangles.  The rule, all of it f32, every operation rounded on its own:
+ *   1. Voxel (i, j, k) is VALID iff W >= min_weight and |D| < +inf (a NaN fails both); a valid voxel is INSIDE iff D <= 0
+ *      (-0 is inside: the side the raycast's hit test uses).
+ *   2. Edge class c = 1 ... 7 has the offset e_c = (c & 1, c >> 1 & 1, c >> 2 & 1).  Voxel a OWNS the edges from a to
+ *      b = a + e_c for every c whose b lies in the volume: three axis edges, three face diagonals, one body diagonal.  An
+ *      edge CROSSES iff both ends are valid and exactly one is inside.
+ *   3. The vertex of a crossing edge: t = Da / (Da - Db); the voxel coordinate g* = ((float)i + t * ex, (float)j + t * ey,
+ *      (float)k + t * ez) with e_c as floats; the point is origin + g* * v per component, in the WORLD frame.  The normal is
+ *      step 6 of the raycast rule taken at g* directly with no pose applied: G from six tri() samples at unit voxel
+ *      offsets (tri unchanged, its W > 0 test included), len = sqrt(Gx * Gx + Gy * Gy + Gz * Gz) summed left to right, the
+ *      normal G / len, or +0 where a sample is invalid or len is 0 or not finite; it points towards growing D, out of the
+ *      surface.  The colour is that of voxel round(g*), halves away from zero, clamped into the volume (step 7 there).
+ *   4. Vertices are ordered by ascending (voxel number with x fastest, class); a vertex's rank is its index.  The point-cloud
+ *      form (want_faces == 0) keeps classes 1, 2 and 4 only, the axis edges (Open3D's extract_point_cloud points), in the
+ *      same relative order; the mesh form keeps all seven.
+ *   5. Triangles.  A cell a (0 <= i < nx - 1, likewise j and k) gives triangles iff all eight corners are valid.  Its six
+ *      tetrahedra come from the axis permutations (p, q, r) in the order xyz, xzy, yxz, yzx, zxy, zyx: v0 = a, v1 = a + e_p,
+ *      v2 = v1 + e_q, v3 = a + (1, 1, 1) (e_p: the unit step along axis p).  Every tetrahedron edge is an owned edge of its
+ *      lower end, so a triangle corner is (owner voxel, class).  With S the set of inside vertices: |S| = 0 or 4 gives no
+ *      triangle; |S| = 1 or 3: the lone vertex L and the others A < B < C (local numbers) give the triangle on the edges
+ *      LA, LB, LC; |S| = 2: inside P < Q and outside A < B give the quad PA, PB, QB, QA, split into (PA, PB, QB) and
+ *      (PA, QB, QA).  Winding: with the crossings put at the edge midpoints of the unit cell, if
+ *      (p1 - p0) x (p2 - p0) . (centroid of the outside vertices - centroid of the inside vertices) is negative the last
+ *      two corners are swapped, each triangle of a quad by the same test: counter-clockwise seen from outside.  The 6 x 16
+ *      table this gives is plain data in tsdf_surface.hip.  Triangles are ordered by ascending (cell's voxel number,
+ *      tetrahedron, triangle); degenerate ones (t is 0 or 1 where a D is exactly 0) are kept.
+ * Outputs, DEVICE memory on the volume's context: d_out_points [vertex_capacity][3] f32, d_out_normals the same or NULL,
+ * d_out_colors [vertex_capacity][3] u8 or NULL (non-NULL on a volume without colours -> A3D_MISSING_FIELD), d_out_faces
+ * [face_capacity][3] u32 vertex indices; with want_faces == 0 the face arguments are ignored and *out_faces is 0.
+ * *out_vertices / *out_faces: the counts.  NULL d_out_points and d_out_faces with capacities 0 is a COUNT-ONLY call: only
+ * the counting passes run and the status is A3D_OK.  Otherwise, if either count exceeds its capacity the call returns
+ * A3D_INVALID_PARAMETER with both counts set and NOTHING written; a count of 2^32 - 1 or more is refused the same way (in
+ * a count-only call too).  Decided on the host before any launch (A3D_INVALID_PARAMETER, the counts untouched): a NULL
+ * volume or count pointer; min_weight outside [1, 2^24]; a NULL d_out_points with a vertex capacity above 0 or with
+ * another vertex output; a NULL d_out_faces with a face capacity above 0; outputs (taken at their capacities) that overlap
+ * each other or the volume.  Host-synchronous; four launches at most whatever the volume's size (count, one block's scan
+ * of the block sums, vertices, triangles) and two waits; 5 bytes of context scratch per voxel (a mask byte and two 16-bit
+ * offsets inside the voxel's block of 256) plus 12 bytes per block.  Neither result depends on launch geometry, on
+ * scheduling, on what scratch holds or on how often the call runs; the volume is never changed. */
+a3d_status a3d_tsdf_volume_extract_surface(a3d_tsdf_volume* volume, uint64_t min_weight, int want_faces, float* d_out_points,
+                                           float* d_out_normals /* NULL ok */, uint8_t* d_out_colors /* NULL ok */,
+                                           uint64_t vertex_capacity, uint32_t* d_out_faces, uint64_t face_capacity,
+                                           uint64_t* out_vertices, uint64_t* out_faces);
 
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
