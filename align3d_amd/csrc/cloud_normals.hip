@@ -41,14 +41,9 @@
 // One upload, one fill and four launches over every tile of every cloud of a batch, whatever the batch size (the job
 // table of cloud_batch.hpp); no block waits on another block.  The grid is a hash table per cloud that, unlike the
 // downsample's, keeps ALL points of a cell: a counting sort by cell.
-//  1. normals_count_kernel: a thread per point claims the slot of its key (load, then 64-bit atomicCAS: the table has at
-//     least two slots per point; the key word holds key + 1, so that one fill with zeros empties keys and counts alike)
-//     and adds 1 to the slot's count.  Dropped points count themselves per job.
-//  2. normals_place_kernel: a thread per slot; a wave sums its occupied slots' counts and takes its run of the job's
-//     cursor with one atomicAdd.  The order of the cells in memory is free: the moments do not depend on it.  The slot's
-//     second word becomes fill position << 32 | count.
-//  3. normals_scatter_kernel: each kept point takes the next position of its cell's run (atomicAdd on the slot's high
-//     half) and writes x, y, z and its index as one 16-byte record; each dropped point writes its zeros.
+//  1.-3. cell_count_kernel, cell_place_kernel, cell_scatter_kernel of cell_sort.hpp: the counting sort, shared with the
+//     knn and cluster entries of cloud_outliers.hip.  The order of the cells in memory is free: the moments do not depend
+//     on it.  Each dropped point gets its zeros in the scatter (NormalsJob::drop_row).
 //  4. normals_estimate_kernel, the hot path: a thread per record IN CELL ORDER, so that a wave's 64 lanes belong to the
 //     same or adjacent cells and the 27 slot lookups and the candidate loads are largely the same addresses across the
 //     wave.  It sums the ten integers (one v_mad_i64_i32 per product term), does steps 4-7 in registers and stores to the
@@ -62,24 +57,13 @@
 #include <cstring>
 #include <vector>
 
-#include "voxel_grid.hpp"  // VoxelGrid, voxel_key, slot_hash, VoxelSlot
+#include "cell_sort.hpp"  // the hash grid, the counting sort by cell, cell_run, consume_run
 
 using namespace a3d;
 
 namespace {
 
-constexpr uint32_t CN_THREADS = 256;
-constexpr uint32_t CN_CHUNK = 4 * CN_THREADS;  // points per chunk
-constexpr uint32_t CN_MAX_TILES = 4096;        // tiles per cloud at most
 constexpr int CN_SWEEPS = 6;
-constexpr uint32_t CN_AHEAD = 4;  // candidates whose loads the estimate kernel issues together
-
-struct CnRecord {  // a kept point in cell order
-  float x, y, z;
-  uint32_t index;
-};
-static_assert(sizeof(CnRecord) == 16, "CnRecord layout");
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One non-empty cloud of a batch as the kernels see it (uploaded per call).
 struct NormalsJob {
@@ -89,11 +73,18 @@ struct NormalsJob {
   float* out_curvature;  // null: not written
   uint32_t* out_counts;  // null: not written
   VoxelSlot* table;      // slot_mask + 1 slots, zeroed before the count: key word 0 = empty, else key + 1
-  CnRecord* sorted;      // len records, the first `kept` of them written
+  CellRecord* sorted;    // len records, the first `kept` of them written
   unsigned long long slot_mask;
   uint32_t len, first_tile, chunks_per_tile, n_tiles;
   float ex, ey, ez;
   uint32_t pad;
+
+  __device__ void drop_row(uint32_t p) const {  // (cell_scatter_kernel) step 1's zeros
+    const f32x3 zero = {0.f, 0.f, 0.f};
+    *(f32x3_u*)(out_normals + 3 * (size_t)p) = zero;
+    if (out_curvature) out_curvature[p] = 0.f;
+    if (out_counts) out_counts[p] = 0u;
+  }
 };
 static_assert(sizeof(NormalsJob) == 96, "NormalsJob layout");
 
@@ -101,127 +92,6 @@ struct CnParams {
   float r, r2, s;
   uint32_t min_neighbors;
 };
-
-// The slot that holds `tag` (key + 1), or ~0 if the table has none (the walk stops at the first empty slot).
-__device__ __forceinline__ unsigned long long find_slot(const VoxelSlot* __restrict__ table, unsigned long long mask,
-                                                        unsigned long long tag) {
-  unsigned long long s = slot_hash(tag - 1) & mask;
-  for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
-    const unsigned long long k = table[s].key;
-    if (k == tag) return s;
-    if (k == 0) break;
-  }
-  return ~0ull;
-}
-
-// Pass 1.  dropped[job] += dropped points; *fault is set if a table were ever full (it cannot be).
-__global__ void __launch_bounds__(CN_THREADS)
-    normals_count_kernel(const NormalsJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid,
-                         unsigned long long* __restrict__ dropped, unsigned long long* __restrict__ fault) {
-  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
-  const NormalsJob& j = jobs[ji];
-  const float* __restrict__ points = j.points;
-  VoxelSlot* table = j.table;
-  const unsigned long long mask = j.slot_mask;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CN_CHUNK;
-  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (len < 2^32 - span: checked by the host)
-  uint32_t n_dropped = 0;
-  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += CN_THREADS) {
-    const f32x3 pt = *(const f32x3_u*)(points + 3 * (size_t)p);
-    unsigned long long key;
-    if (!voxel_key(pt, grid, &key, nullptr)) {
-      ++n_dropped;
-      continue;
-    }
-    const unsigned long long tag = key + 1;
-    unsigned long long s = slot_hash(key) & mask;
-    bool placed = false;
-    for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
-      unsigned long long k = VX_LOAD_AGENT(&table[s].key);
-      if (k == 0) k = atomicCAS(&table[s].key, 0ull, tag);
-      if (k == 0 || k == tag) {
-        placed = true;
-        break;
-      }
-    }
-    if (!placed) {
-      atomicMax(fault, 1ull);
-      continue;
-    }
-    atomicAdd(&table[s].best, 1ull);
-  }
-  n_dropped = wave_sum(n_dropped);
-  if ((threadIdx.x & 63u) == 0 && n_dropped) atomicAdd(&dropped[ji], (unsigned long long)n_dropped);
-}
-
-// Pass 2: every occupied slot's second word = start << 32 | count, the starts handed out from cursor[job] (zeroed by the
-// upload; it ends as the job's kept count).  Tile t of a job takes slots [t * per, (t + 1) * per), per = ceil(slots / tiles).
-__global__ void __launch_bounds__(CN_THREADS)
-    normals_place_kernel(const NormalsJob* __restrict__ jobs, uint32_t n_jobs, unsigned long long* __restrict__ cursor) {
-  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
-  const NormalsJob& j = jobs[ji];
-  VoxelSlot* table = j.table;
-  const unsigned long long slots = j.slot_mask + 1, per = (slots + j.n_tiles - 1) / j.n_tiles;
-  const unsigned long long s0 = (unsigned long long)(tile - j.first_tile) * per, s_end = min(slots, s0 + per);
-  const uint32_t lane = threadIdx.x & 63u;
-  for (unsigned long long base = s0 + (threadIdx.x & ~63u); base < s_end; base += CN_THREADS) {  // wave-uniform
-    const unsigned long long s = base + lane;
-    const bool occupied = s < s_end && table[s].key != 0;
-    const uint32_t cnt = occupied ? (uint32_t)table[s].best : 0u;
-    uint32_t incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(incl, o, 64);
-      if (lane >= (uint32_t)o) incl += up;
-    }
-    const uint32_t total = __shfl(incl, 63, 64);
-    if (total == 0) continue;  // wave-uniform
-    unsigned long long start = 0;
-    if (lane == 0) start = atomicAdd(&cursor[ji], (unsigned long long)total);
-    start = __shfl(start, 0, 64);
-    if (occupied) table[s].best = (start + (incl - cnt)) << 32 | cnt;
-  }
-}
-
-// Pass 3: kept points into their cells' runs; dropped points' zeros.
-__global__ void __launch_bounds__(CN_THREADS)
-    normals_scatter_kernel(const NormalsJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid,
-                           unsigned long long* __restrict__ fault) {
-  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
-  const NormalsJob& j = jobs[ji];
-  const float* __restrict__ points = j.points;
-  VoxelSlot* table = j.table;
-  CnRecord* sorted = j.sorted;
-  float* out_normals = j.out_normals;
-  float* out_curvature = j.out_curvature;
-  uint32_t* out_counts = j.out_counts;
-  const unsigned long long mask = j.slot_mask;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CN_CHUNK;
-  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);
-  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += CN_THREADS) {
-    const f32x3 pt = *(const f32x3_u*)(points + 3 * (size_t)p);
-    unsigned long long key;
-    if (!voxel_key(pt, grid, &key, nullptr)) {
-      const f32x3 zero = {0.f, 0.f, 0.f};
-      *(f32x3_u*)(out_normals + 3 * (size_t)p) = zero;
-      if (out_curvature) out_curvature[p] = 0.f;
-      if (out_counts) out_counts[p] = 0u;
-      continue;
-    }
-    const unsigned long long s = find_slot(table, mask, key + 1);
-    if (s == ~0ull) {  // (cannot happen: pass 1 placed every kept point)
-      atomicMax(fault, 2ull);
-      continue;
-    }
-    const unsigned long long pos = atomicAdd(&table[s].best, 1ull << 32) >> 32;
-    if (pos >= len) {  // (cannot happen: the runs partition the kept points; a bound on every store)
-      atomicMax(fault, 3ull);
-      continue;
-    }
-    const f32x4 rec = {pt.x, pt.y, pt.z, __uint_as_float(p)};
-    *(f32x4*)(sorted + pos) = rec;
-  }
-}
 
 // One Jacobi rotation of step 5 on the pair (p, q) with third index o.
 __device__ __forceinline__ void jacobi_rotate(float& app, float& aqq, float& apq, float& aop, float& aoq, float& v0p,
@@ -243,25 +113,25 @@ __device__ __forceinline__ void jacobi_rotate(float& app, float& aqq, float& apq
 }
 
 // Pass 4.  SORTED: a thread per record, in cell order; else a thread per point of the cloud, in input order (diagnostics).
-// AHEAD: CN_AHEAD; 1 is the plain candidate loop (diagnostics).  LDS: a wave stages the runs its lanes share in LDS
+// AHEAD: CELL_AHEAD; 1 is the plain candidate loop (diagnostics).  LDS: a wave stages the runs its lanes share in LDS
 // (diagnostics).
 // valid[job] += valid rows.
 template <bool SORTED, uint32_t AHEAD, bool LDS>
-__global__ void __launch_bounds__(CN_THREADS)
+__global__ void __launch_bounds__(CELL_THREADS)
     normals_estimate_kernel(const NormalsJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, CnParams prm,
                             const unsigned long long* __restrict__ cursor, unsigned long long* __restrict__ valid) {
-  __shared__ f32x4 s_stage[LDS ? CN_THREADS / 64 : 1][LDS ? 64 : 1];
+  __shared__ f32x4 s_stage[LDS ? CELL_THREADS / 64 : 1][LDS ? 64 : 1];
   const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
   const NormalsJob& j = jobs[ji];
   const VoxelSlot* __restrict__ table = j.table;
-  const CnRecord* __restrict__ sorted = j.sorted;
+  const CellRecord* __restrict__ sorted = j.sorted;
   const unsigned long long mask = j.slot_mask;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CN_CHUNK;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK;
   const uint32_t kept = (uint32_t)min(cursor[ji], (unsigned long long)len);
   const uint32_t rows = SORTED ? kept : len;
   const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(rows, p0 + span);
   uint32_t n_valid = 0;
-  for (uint32_t base = p0; base < p_end; base += CN_THREADS) {  // block-uniform
+  for (uint32_t base = p0; base < p_end; base += CELL_THREADS) {  // block-uniform
     const uint32_t t = base + threadIdx.x;
     bool is_valid = false;
     f32x3 pi = {0.f, 0.f, 0.f};
@@ -293,18 +163,8 @@ __global__ void __launch_bounds__(CN_THREADS)
     };
     for (int c = 0; c < 27; ++c) {  // (LDS: every lane of the wave walks the 27 cells, a dead lane with an empty run)
       if (!LDS && !live) break;
-      const int nx = kx + c / 9 - 1, ny = ky + c / 3 % 3 - 1, nz = kz + c % 3 - 1;
       uint32_t begin = 0, end = 0;  // the run of the cell's records
-      if (live && (unsigned)nx < (1u << 21) && (unsigned)ny < (1u << 21) && (unsigned)nz < (1u << 21)) {
-        const unsigned long long nkey = (unsigned long long)nx << 42 | (unsigned long long)ny << 21 | (unsigned long long)nz;
-        const unsigned long long s = find_slot(table, mask, nkey + 1);
-        if (s != ~0ull) {
-          const unsigned long long word = table[s].best;  // after pass 3: run end << 32 | count
-          const uint32_t cnt = (uint32_t)word;
-          end = min((uint32_t)(word >> 32), kept);
-          begin = end >= cnt ? end - cnt : 0u;
-        }
-      }
+      if (live) cell_run(table, mask, kept, kx, ky, kz, c, &begin, &end);
       if (LDS) {
         // The lanes of a wave that ask for the same run (in cell order: most of them) get it through LDS: the wave loads
         // 64 records of the run with one coalesced load, and the lanes whose run it is read them back one by one.
@@ -328,16 +188,7 @@ __global__ void __launch_bounds__(CN_THREADS)
           }
         }
       } else {
-        // AHEAD candidates a trip: their loads are issued together (the index is clamped into the run, the sums take only
-        // the candidates that exist), so a thread waits for memory once per AHEAD candidates instead of once per candidate
-        for (uint32_t q = begin; q < end; q += AHEAD) {
-          f32x4 rec[AHEAD];
-#pragma unroll
-          for (uint32_t u = 0; u < AHEAD; ++u) rec[u] = *(const f32x4*)(sorted + min(q + u, end - 1));
-#pragma unroll
-          for (uint32_t u = 0; u < AHEAD; ++u)
-            if (q + u < end) consume(rec[u]);
-        }
+        consume_run<AHEAD>(sorted, begin, end, consume);
       }
     }
     if (live) {
@@ -413,8 +264,7 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
   std::vector<uint64_t> cloud_of_job;
   std::vector<ByteRange> ranges;
   jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(5 * n);
-  uint64_t tiles = 0;
-  size_t table_bytes = 0, sorted_bytes = 0;  // offsets of a job's arrays inside their parts of the scratch region, for now
+  CellSortPlan plan;
   for (uint64_t i = 0; i < n; ++i) {
     const a3d_point_cloud_view& c = d_clouds[i];
     A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
@@ -427,18 +277,8 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
     j.out_normals = d_out_normals[i];
     j.out_curvature = d_out_curvature ? d_out_curvature[i] : nullptr;
     j.out_counts = d_out_counts ? d_out_counts[i] : nullptr;
-    j.len = (uint32_t)c.len;
     if (viewpoints_host) j.ex = viewpoints_host[3 * i], j.ey = viewpoints_host[3 * i + 1], j.ez = viewpoints_host[3 * i + 2];
-    A3D_TRY(plan_tiles(c.len, CN_CHUNK, CN_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
-    j.n_tiles = (uint32_t)tiles - j.first_tile;
-    // the kernels' 32-bit point positions run up to one tile span past len
-    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * CN_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
-                "a3d_point_clouds_estimate_normals_device: a cloud within one tile of 2^32 points");
-    uint64_t slots = 2;
-    while (slots < 2 * c.len) slots <<= 1;
-    j.slot_mask = slots - 1;
-    j.table = (VoxelSlot*)table_bytes, j.sorted = (CnRecord*)sorted_bytes;
-    table_bytes += slots * sizeof(VoxelSlot), sorted_bytes += pad256(c.len * sizeof(CnRecord));
+    A3D_TRY(cell_sort_plan(&plan, c.len, "a3d_point_clouds_estimate_normals_device: a cloud within one tile of 2^32 points", &j));
     jobs.push_back(j), cloud_of_job.push_back(i);
     const uintptr_t bytes = (uintptr_t)c.len * 12;
     ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + bytes, false});
@@ -459,13 +299,9 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   BatchScratch scratch;  // the words: cursors (kept counts), dropped, valid, fault; the tail: hash tables | records
-  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(NormalsJob), 3 * n_jobs + 1, 0, table_bytes + sorted_bytes, &scratch));
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(NormalsJob), 3 * n_jobs + 1, 0, plan.table_bytes + plan.sorted_bytes, &scratch));
   char* d_tables = scratch.tail;
-  char* d_sorted = scratch.tail + table_bytes;
-  for (NormalsJob& j : jobs) {
-    j.table = (VoxelSlot*)(d_tables + (size_t)j.table);
-    j.sorted = (CnRecord*)(d_sorted + (size_t)j.sorted);
-  }
+  for (NormalsJob& j : jobs) cell_sort_rebase(&j, d_tables, d_tables + plan.table_bytes);
   const NormalsJob* d_jobs = (const NormalsJob*)scratch.jobs;
   unsigned long long* d_cursor = scratch.words;
   unsigned long long* d_dropped = d_cursor + n_jobs;
@@ -473,29 +309,24 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
   unsigned long long* d_fault = d_cursor + 3 * n_jobs;
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, jobs.data(), s));
-  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, table_bytes, s));  // every key word empty, every count 0
-  const dim3 grid_dim((uint32_t)tiles), block(CN_THREADS);
+  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, plan.table_bytes, s));  // every key word empty, every count 0
+  const dim3 grid_dim((uint32_t)plan.tiles), block(CELL_THREADS);
   const uint32_t nj = (uint32_t)n_jobs;
-  hipLaunchKernelGGL(normals_count_kernel, grid_dim, block, 0, s, d_jobs, nj, grid, d_dropped, d_fault);
-  A3D_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(normals_place_kernel, grid_dim, block, 0, s, d_jobs, nj, d_cursor);
-  A3D_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(normals_scatter_kernel, grid_dim, block, 0, s, d_jobs, nj, grid, d_fault);
-  A3D_HIP_TRY(hipGetLastError());
+  A3D_TRY(cell_sort_launch(d_jobs, nj, plan.tiles, grid, d_cursor, d_dropped, d_fault, s));
   const unsigned long long* d_kept = d_cursor;
 #ifdef A3D_DIAGNOSTICS  // the forms that were measured slower (scripts/cloud_normals_probe.py)
   const char* order = getenv("A3D_NORMALS_ORDER");
   const char* ahead = getenv("A3D_NORMALS_AHEAD");
   const char* lds = getenv("A3D_NORMALS_LDS");
   if (order && !strcmp(order, "input"))
-    hipLaunchKernelGGL((normals_estimate_kernel<false, CN_AHEAD, false>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_valid);
+    hipLaunchKernelGGL((normals_estimate_kernel<false, CELL_AHEAD, false>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_valid);
   else if (lds && !strcmp(lds, "1"))
     hipLaunchKernelGGL((normals_estimate_kernel<true, 1, true>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_valid);
   else if (ahead && !strcmp(ahead, "1"))
     hipLaunchKernelGGL((normals_estimate_kernel<true, 1, false>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_valid);
   else
 #endif
-    hipLaunchKernelGGL((normals_estimate_kernel<true, CN_AHEAD, false>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_valid);
+    hipLaunchKernelGGL((normals_estimate_kernel<true, CELL_AHEAD, false>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_valid);
   A3D_HIP_TRY(hipGetLastError());
   std::vector<unsigned long long> words(3 * n_jobs + 1);
   A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_cursor, words.size() * 8, hipMemcpyDeviceToHost, s));

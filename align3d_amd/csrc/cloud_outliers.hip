@@ -26,11 +26,10 @@
 //  k == 0 is the count-only form: no distances, no qsum, statistics all zero.
 //
 // The knn call: one upload, one fill and four launches over every tile of every cloud of a batch, whatever the batch
-// size (the job table of cloud_batch.hpp).  knn_count_kernel, knn_place_kernel and knn_scatter_kernel are the counting
-// sort by cell of cloud_normals.hip (normals_count_kernel, normals_place_kernel, normals_scatter_kernel: KEEP EACH PAIR
-// ALIKE; they are private twins so that the normals' code, scratch and launches stay exactly what they were).  The
-// fourth, knn_distance_kernel, is the hot path: a thread per record in cell order, 27 slot lookups, the candidates of a
-// cell loaded four at a time as normals_estimate_kernel does.  The k smallest d2 (as bit patterns: d2 >= 0, so they order
+// size (the job table of cloud_batch.hpp).  The first three are the counting sort by cell of cell_sort.hpp over a
+// KnnJob table (cell_count_kernel, cell_place_kernel, cell_scatter_kernel), the one the normals entry runs.  The fourth,
+// knn_distance_kernel, is the hot path: a thread per record in cell order, 27 slot lookups (cell_run), the candidates
+// of a cell loaded four at a time as normals_estimate_kernel does.  The k smallest d2 (as bit patterns: d2 >= 0, so they order
 // like the values) live in K registers as a sorted array, K in {8, 16, 32} chosen on the host from k; an insertion is an
 // unrolled min / max chain that is skipped when the candidate is not below the current K-th; the lattice distance is
 // computed for the k survivors only, after the walk.  No register array is indexed by a runtime value.  k == 0 has an
@@ -66,11 +65,10 @@
 //     row_sizes[i] = sizes[labels[i]], and 0 for noise.
 // Every output is integers decided on integers or on d2 bits: the same on every run.
 //
-// The cluster call: one upload, one fill and eight launches, whatever the batch size.  The first three are
-// knn_count_kernel, knn_place_kernel and knn_scatter_kernel AS THEY ARE (this entry lives in this translation unit for
-// that: no third set of twins, and the knn entry's code, scratch and launches stay what they were); the scatter's
-// "qsum of a dropped row = 0xFFFFFFFF" store is pointed at parent[], which makes every dropped row a non-core row for
-// free.  Then cluster_walk_kernel twice, the K = 0 shape of knn_distance_kernel: the count pass writes parent[row] = row
+// The cluster call: one upload, one fill and eight launches, whatever the batch size.  The first three are the same
+// sort over a KnnJob table of the call's own; KnnJob::drop_row's "qsum of a dropped row = 0xFFFFFFFF" is pointed at
+// parent[]: every dropped row a non-core row for free.  Then cluster_walk_kernel twice, the K = 0 shape of
+// knn_distance_kernel: the count pass writes parent[row] = row
 // for a core row and 0xFFFFFFFF otherwise; the link pass (a second walk: whether j is core is only known after the
 // first) unions a core row with each core neighbour of LOWER row index (each edge is seen from both ends, half is
 // enough), and keeps for a non-core row the minimum key of rule 4, stored as owner[row] = winner + 1 (0 from the fill =
@@ -98,29 +96,18 @@
 #include <cstring>
 #include <vector>
 
-#include "voxel_grid.hpp"  // VoxelGrid, voxel_key, slot_hash, VoxelSlot
+#include "cell_sort.hpp"  // the hash grid, the counting sort by cell, cell_run, consume_run
 
 using namespace a3d;
 
 namespace {
 
-constexpr uint32_t CO_THREADS = 256;
-constexpr uint32_t CO_WAVES = CO_THREADS / 64;
-constexpr uint32_t CO_ROUNDS = 4;
-constexpr uint32_t CO_CHUNK = CO_ROUNDS * CO_THREADS;  // points per chunk: a multiple of 64, so a ballot word never straddles tiles
-constexpr uint32_t CO_GROUPS = CO_CHUNK / 64;          // ballot words per chunk
-constexpr uint32_t CO_MAX_TILES = 4096;                // tiles per cloud at most
-constexpr uint32_t CO_AHEAD = 4;                       // candidates whose loads the distance kernel issues together
+constexpr uint32_t CO_WAVES = CELL_THREADS / 64;
+constexpr uint32_t CO_ROUNDS = CELL_CHUNK / CELL_THREADS;  // rounds of a block over a chunk
+constexpr uint32_t CO_GROUPS = CELL_CHUNK / 64;            // ballot words per chunk
 constexpr uint32_t CO_MAX_K = 32;
 constexpr uint32_t CO_NONE = 0xFFFFFFFFu;  // the qsum of a row without k others
 static_assert(CO_GROUPS <= 64, "a wave's lanes hold the chunk's ballot words");
-
-struct CoRecord {  // a kept point in cell order
-  float x, y, z;
-  uint32_t index;
-};
-static_assert(sizeof(CoRecord) == 16, "CoRecord layout");
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One non-empty cloud of a knn batch as the kernels see it (uploaded per call).
 struct KnnJob {
@@ -128,9 +115,14 @@ struct KnnJob {
   uint32_t* out_counts;  // null: not written
   uint32_t* out_qsum;    // null: not written (k == 0)
   VoxelSlot* table;      // slot_mask + 1 slots, zeroed before the count: key word 0 = empty, else key + 1
-  CoRecord* sorted;      // len records, the first `kept` of them written
+  CellRecord* sorted;    // len records, the first `kept` of them written
   unsigned long long slot_mask;
   uint32_t len, first_tile, chunks_per_tile, n_tiles;
+
+  __device__ void drop_row(uint32_t p) const {  // (cell_scatter_kernel) step 1's count 0 and qsum NONE
+    if (out_counts) out_counts[p] = 0u;
+    if (out_qsum) out_qsum[p] = CO_NONE;
+  }
 };
 static_assert(sizeof(KnnJob) == 64, "KnnJob layout");
 
@@ -138,125 +130,6 @@ struct KnnParams {
   float r, r2, s;
   uint32_t k;
 };
-
-// The slot that holds `tag` (key + 1), or ~0 if the table has none (the walk stops at the first empty slot).
-__device__ __forceinline__ unsigned long long knn_find_slot(const VoxelSlot* __restrict__ table, unsigned long long mask,
-                                                            unsigned long long tag) {
-  unsigned long long s = slot_hash(tag - 1) & mask;
-  for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
-    const unsigned long long k = table[s].key;
-    if (k == tag) return s;
-    if (k == 0) break;
-  }
-  return ~0ull;
-}
-
-// Pass 1 (normals_count_kernel's twin).  dropped[job] += dropped points; *fault is set if a table were ever full (it
-// cannot be).
-__global__ void __launch_bounds__(CO_THREADS)
-    knn_count_kernel(const KnnJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid,
-                     unsigned long long* __restrict__ dropped, unsigned long long* __restrict__ fault) {
-  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
-  const KnnJob& j = jobs[ji];
-  const float* __restrict__ points = j.points;
-  VoxelSlot* table = j.table;
-  const unsigned long long mask = j.slot_mask;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK;
-  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (len < 2^32 - span: checked by the host)
-  uint32_t n_dropped = 0;
-  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += CO_THREADS) {
-    const f32x3 pt = *(const f32x3_u*)(points + 3 * (size_t)p);
-    unsigned long long key;
-    if (!voxel_key(pt, grid, &key, nullptr)) {
-      ++n_dropped;
-      continue;
-    }
-    const unsigned long long tag = key + 1;
-    unsigned long long s = slot_hash(key) & mask;
-    bool placed = false;
-    for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
-      unsigned long long k = VX_LOAD_AGENT(&table[s].key);
-      if (k == 0) k = atomicCAS(&table[s].key, 0ull, tag);
-      if (k == 0 || k == tag) {
-        placed = true;
-        break;
-      }
-    }
-    if (!placed) {
-      atomicMax(fault, 1ull);
-      continue;
-    }
-    atomicAdd(&table[s].best, 1ull);
-  }
-  n_dropped = wave_sum(n_dropped);
-  if ((threadIdx.x & 63u) == 0 && n_dropped) atomicAdd(&dropped[ji], (unsigned long long)n_dropped);
-}
-
-// Pass 2 (normals_place_kernel's twin): every occupied slot's second word = start << 32 | count, the starts handed out
-// from cursor[job] (zeroed by the upload; it ends as the job's kept count).
-__global__ void __launch_bounds__(CO_THREADS)
-    knn_place_kernel(const KnnJob* __restrict__ jobs, uint32_t n_jobs, unsigned long long* __restrict__ cursor) {
-  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
-  const KnnJob& j = jobs[ji];
-  VoxelSlot* table = j.table;
-  const unsigned long long slots = j.slot_mask + 1, per = (slots + j.n_tiles - 1) / j.n_tiles;
-  const unsigned long long s0 = (unsigned long long)(tile - j.first_tile) * per, s_end = min(slots, s0 + per);
-  const uint32_t lane = threadIdx.x & 63u;
-  for (unsigned long long base = s0 + (threadIdx.x & ~63u); base < s_end; base += CO_THREADS) {  // wave-uniform
-    const unsigned long long s = base + lane;
-    const bool occupied = s < s_end && table[s].key != 0;
-    const uint32_t cnt = occupied ? (uint32_t)table[s].best : 0u;
-    uint32_t incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(incl, o, 64);
-      if (lane >= (uint32_t)o) incl += up;
-    }
-    const uint32_t total = __shfl(incl, 63, 64);
-    if (total == 0) continue;  // wave-uniform
-    unsigned long long start = 0;
-    if (lane == 0) start = atomicAdd(&cursor[ji], (unsigned long long)total);
-    start = __shfl(start, 0, 64);
-    if (occupied) table[s].best = (start + (incl - cnt)) << 32 | cnt;
-  }
-}
-
-// Pass 3 (normals_scatter_kernel's twin): kept points into their cells' runs; a dropped point's count 0 and qsum NONE.
-__global__ void __launch_bounds__(CO_THREADS)
-    knn_scatter_kernel(const KnnJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid,
-                       unsigned long long* __restrict__ fault) {
-  const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
-  const KnnJob& j = jobs[ji];
-  const float* __restrict__ points = j.points;
-  VoxelSlot* table = j.table;
-  CoRecord* sorted = j.sorted;
-  uint32_t* out_counts = j.out_counts;
-  uint32_t* out_qsum = j.out_qsum;
-  const unsigned long long mask = j.slot_mask;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK;
-  const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);
-  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += CO_THREADS) {
-    const f32x3 pt = *(const f32x3_u*)(points + 3 * (size_t)p);
-    unsigned long long key;
-    if (!voxel_key(pt, grid, &key, nullptr)) {
-      if (out_counts) out_counts[p] = 0u;
-      if (out_qsum) out_qsum[p] = CO_NONE;
-      continue;
-    }
-    const unsigned long long s = knn_find_slot(table, mask, key + 1);
-    if (s == ~0ull) {  // (cannot happen: pass 1 placed every kept point)
-      atomicMax(fault, 2ull);
-      continue;
-    }
-    const unsigned long long pos = atomicAdd(&table[s].best, 1ull << 32) >> 32;
-    if (pos >= len) {  // (cannot happen: the runs partition the kept points; a bound on every store)
-      atomicMax(fault, 3ull);
-      continue;
-    }
-    const f32x4 rec = {pt.x, pt.y, pt.z, __uint_as_float(p)};
-    *(f32x4*)(sorted + pos) = rec;
-  }
-}
 
 __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
 #pragma unroll
@@ -272,19 +145,19 @@ __device__ __forceinline__ uint32_t lattice_distance(float d2, float s) {
 // Pass 4.  K: the length of the sorted register array, >= the call's k; 0: counts only.  ON_T: the array holds lattice
 // distances instead of d2 bits (diagnostics).  stats[4 * job ...] += the job's four sums.
 template <uint32_t K, bool ON_T>
-__global__ void __launch_bounds__(CO_THREADS)
+__global__ void __launch_bounds__(CELL_THREADS)
     knn_distance_kernel(const KnnJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, KnnParams prm,
                         const unsigned long long* __restrict__ cursor, unsigned long long* __restrict__ stats) {
   const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
   const KnnJob& j = jobs[ji];
   const VoxelSlot* __restrict__ table = j.table;
-  const CoRecord* __restrict__ sorted = j.sorted;
+  const CellRecord* __restrict__ sorted = j.sorted;
   const unsigned long long mask = j.slot_mask;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK;
   const uint32_t kept = (uint32_t)min(cursor[ji], (unsigned long long)len);
   const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(kept, p0 + span);
   unsigned long long st_m = 0, st_q = 0, st_lo = 0, st_hi = 0;
-  for (uint32_t base = p0; base < p_end; base += CO_THREADS) {  // block-uniform
+  for (uint32_t base = p0; base < p_end; base += CELL_THREADS) {  // block-uniform
     const uint32_t t = base + threadIdx.x;
     f32x3 pi = {0.f, 0.f, 0.f};
     uint32_t row = t;
@@ -321,26 +194,16 @@ __global__ void __launch_bounds__(CO_THREADS)
     };
     for (int c = 0; c < 27; ++c) {
       if (!live) break;
-      const int nx = kx + c / 9 - 1, ny = ky + c / 3 % 3 - 1, nz = kz + c % 3 - 1;
-      uint32_t begin = 0, end = 0;  // the run of the cell's records
-      if ((unsigned)nx < (1u << 21) && (unsigned)ny < (1u << 21) && (unsigned)nz < (1u << 21)) {
-        const unsigned long long nkey = (unsigned long long)nx << 42 | (unsigned long long)ny << 21 | (unsigned long long)nz;
-        const unsigned long long s = knn_find_slot(table, mask, nkey + 1);
-        if (s != ~0ull) {
-          const unsigned long long word = table[s].best;  // after pass 3: run end << 32 | count
-          const uint32_t cnt = (uint32_t)word;
-          end = min((uint32_t)(word >> 32), kept);
-          begin = end >= cnt ? end - cnt : 0u;
-        }
-      }
-      // CO_AHEAD candidates a trip: their loads are issued together (the index is clamped into the run, only the
-      // candidates that exist are consumed), so a thread waits for memory once per CO_AHEAD candidates
-      for (uint32_t q = begin; q < end; q += CO_AHEAD) {
-        f32x4 rec[CO_AHEAD];
+      uint32_t begin, end;  // the run of the cell's records
+      cell_run(table, mask, kept, kx, ky, kz, c, &begin, &end);
+      // consume_run of cell_sort.hpp, written out (KEEP ALIKE): through the helper this kernel is compiled to other code
+      // (K = 0: 38 VGPRs for 36), which the timing gate cannot tell from this one either way; the reasons are in the header
+      for (uint32_t q = begin; q < end; q += CELL_AHEAD) {
+        f32x4 rec[CELL_AHEAD];
 #pragma unroll
-        for (uint32_t u = 0; u < CO_AHEAD; ++u) rec[u] = *(const f32x4*)(sorted + min(q + u, end - 1));
+        for (uint32_t u = 0; u < CELL_AHEAD; ++u) rec[u] = *(const f32x4*)(sorted + min(q + u, end - 1));
 #pragma unroll
-        for (uint32_t u = 0; u < CO_AHEAD; ++u)
+        for (uint32_t u = 0; u < CELL_AHEAD; ++u)
           if (q + u < end) consume(rec[u]);
       }
     }
@@ -392,7 +255,7 @@ static_assert(sizeof(SelectJob) == 104, "SelectJob layout");
 
 // Pass 1 (voxel_flag_kernel's twin): flags[p / 64] bit p % 64 = row p is kept; tile_counts[tile] = kept rows of the tile;
 // lens[job] += the same (zeroed by the host upload).
-__global__ void __launch_bounds__(CO_THREADS)
+__global__ void __launch_bounds__(CELL_THREADS)
     select_flag_kernel(const SelectJob* __restrict__ jobs, uint32_t n_jobs, uint32_t* __restrict__ tile_counts,
                        unsigned long long* __restrict__ lens) {
   __shared__ uint32_t s_wave[CO_WAVES];
@@ -401,11 +264,11 @@ __global__ void __launch_bounds__(CO_THREADS)
   const uint32_t* __restrict__ values = j.values;
   unsigned long long* __restrict__ flags = j.flags;
   const uint32_t lo = j.lo, hi = j.hi;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK;
   const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (len < 2^32 - span: checked by the host)
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t c = 0;  // wave-uniform
-  for (uint32_t base = p0 + wave * 64u; base < p_end; base += CO_THREADS) {  // wave-uniform
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += CELL_THREADS) {  // wave-uniform
     const uint32_t p = base + lane;
     bool win = false;
     if (p < p_end) {
@@ -428,7 +291,7 @@ __global__ void __launch_bounds__(CO_THREADS)
 
 // Pass 2 (voxel_compact_kernel's twin): every kept row of the tile to out[offset + rank].  Nothing is written anywhere if
 // any cloud of the batch keeps more rows than its capacity (the host then returns A3D_INVALID_PARAMETER).
-__global__ void __launch_bounds__(CO_THREADS)
+__global__ void __launch_bounds__(CELL_THREADS)
     select_compact_kernel(const SelectJob* __restrict__ jobs, uint32_t n_jobs, const uint32_t* __restrict__ tile_counts,
                           const unsigned long long* __restrict__ lens) {
   __shared__ uint32_t s_base, s_over;
@@ -456,10 +319,10 @@ __global__ void __launch_bounds__(CO_THREADS)
   const uint8_t* __restrict__ colors = j.colors;
   uint8_t* __restrict__ out_colors = j.out_colors;
   const unsigned long long capacity = j.capacity;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK, n_groups = (len + 63u) >> 6;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK, n_groups = (len + 63u) >> 6;
   const uint32_t p0 = t * span, p_end = min(len, p0 + span);
   uint32_t base = s_base;  // kept rows of the cloud before this chunk
-  for (uint32_t px0 = p0; px0 < p_end; px0 += CO_CHUNK) {
+  for (uint32_t px0 = p0; px0 < p_end; px0 += CELL_CHUNK) {
     // lane g < CO_GROUPS of every wave holds the ballot word of the chunk's group g (rows px0 + 64 g ...), their
     // exclusive prefix gives every group's offset: no LDS, no block barrier
     const uint32_t g = (px0 >> 6) + lane;
@@ -485,7 +348,7 @@ __global__ void __launch_bounds__(CO_THREADS)
     for (uint32_t r = 0; r < CO_ROUNDS; ++r) {
       const uint64_t ballot = ballots[r];
       if (!((ballot >> lane) & 1ull)) continue;
-      const uint32_t p = px0 + r * CO_THREADS + threadIdx.x;
+      const uint32_t p = px0 + r * CELL_THREADS + threadIdx.x;
       const unsigned long long dst = (unsigned long long)offs[r] + lane_rank(ballot);
       if (p >= p_end || dst >= capacity) continue;  // (cannot happen: the bit is a row's, the total fits; a bound on every store)
       *(f32x3_u*)(out_points + 3 * dst) = *(const f32x3_u*)(points + 3 * (size_t)p);
@@ -508,7 +371,7 @@ struct ClusterJob {
   uint32_t* size;             // [len] by row, zeroed: rows of the cluster, at its root
   unsigned long long* flags;  // (len + 63) / 64 ballot words: row p is a root
   const VoxelSlot* table;
-  const CoRecord* sorted;
+  const CellRecord* sorted;
   unsigned long long slot_mask;
   uint32_t len, first_tile, chunks_per_tile, pad;
 };
@@ -551,23 +414,23 @@ __device__ __forceinline__ uint32_t cluster_union(uint32_t* parent, uint32_t a, 
   return min(a, b);
 }
 
-// Passes 4 and 5: the walk of knn_distance_kernel<0> (KEEP ALIKE).  LINK false: parent[row] = row if N >= m, else
+// Passes 4 and 5: the walk of knn_distance_kernel<0>.  LINK false: parent[row] = row if N >= m, else
 // CO_NONE.  LINK true: rule 3's unions for a core row (ALL: with every core neighbour, not only the lower rows) and
 // rule 4's winner for the others.
 template <bool LINK, bool ALL, bool HALVE>
-__global__ void __launch_bounds__(CO_THREADS)
+__global__ void __launch_bounds__(CELL_THREADS)
     cluster_walk_kernel(const ClusterJob* __restrict__ jobs, uint32_t n_jobs, VoxelGrid grid, float r2, uint32_t m,
                         const unsigned long long* __restrict__ cursor, unsigned long long* __restrict__ fault) {
   const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
   const ClusterJob& j = jobs[ji];
   const VoxelSlot* __restrict__ table = j.table;
-  const CoRecord* __restrict__ sorted = j.sorted;
+  const CellRecord* __restrict__ sorted = j.sorted;
   uint32_t* parent = j.parent;
   const unsigned long long mask = j.slot_mask;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK;
   const uint32_t kept = (uint32_t)min(cursor[ji], (unsigned long long)len);
   const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(kept, p0 + span);
-  for (uint32_t base = p0; base < p_end; base += CO_THREADS) {  // block-uniform
+  for (uint32_t base = p0; base < p_end; base += CELL_THREADS) {  // block-uniform
     const uint32_t t = base + threadIdx.x;
     f32x3 pi = {0.f, 0.f, 0.f};
     uint32_t row = t;
@@ -603,56 +466,41 @@ __global__ void __launch_bounds__(CO_THREADS)
     };
     for (int c = 0; c < 27; ++c) {
       if (!live) break;
-      const int nx = kx + c / 9 - 1, ny = ky + c / 3 % 3 - 1, nz = kz + c % 3 - 1;
-      uint32_t begin = 0, end = 0;  // the run of the cell's records
-      if ((unsigned)nx < (1u << 21) && (unsigned)ny < (1u << 21) && (unsigned)nz < (1u << 21)) {
-        const unsigned long long nkey = (unsigned long long)nx << 42 | (unsigned long long)ny << 21 | (unsigned long long)nz;
-        const unsigned long long s = knn_find_slot(table, mask, nkey + 1);
-        if (s != ~0ull) {
-          const unsigned long long word = table[s].best;  // after pass 3: run end << 32 | count
-          const uint32_t cnt = (uint32_t)word;
-          end = min((uint32_t)(word >> 32), kept);
-          begin = end >= cnt ? end - cnt : 0u;
-        }
-      }
+      uint32_t begin, end;  // the run of the cell's records
+      cell_run(table, mask, kept, kx, ky, kz, c, &begin, &end);
       if constexpr (!LINK) {
-        for (uint32_t q = begin; q < end; q += CO_AHEAD) {
-          f32x4 rec[CO_AHEAD];
-#pragma unroll
-          for (uint32_t u = 0; u < CO_AHEAD; ++u) rec[u] = *(const f32x4*)(sorted + min(q + u, end - 1));
-#pragma unroll
-          for (uint32_t u = 0; u < CO_AHEAD; ++u)
-            if (q + u < end && distance2(rec[u]) <= r2) ++N;
-        }
+        consume_run<CELL_AHEAD>(sorted, begin, end, [&](const f32x4 rec) {
+          if (distance2(rec) <= r2) ++N;
+        });
       } else if (begin < end) {
         // The same trips; a neighbour costs a second, dependent load (its parent), so the parents of a trip's neighbours
-        // are requested together and behind the NEXT trip's records: a thread still waits for memory once per CO_AHEAD
+        // are requested together and behind the NEXT trip's records: a thread still waits for memory once per CELL_AHEAD
         // candidates.  (Measured: 270 k rows in one cell 743 -> 675 ms a call, a frame at r = 0.01 3.33 -> 3.28 ms; what is
         // left of this pass's 4 to 5 times the count pass is the finds, two or three dependent agent-scope loads each.)  A
         // candidate that is no neighbour, or a higher row that the other end of the edge will see, loads parent[row]
         // instead, a line the thread has.  The wavefront-scope atomic load is an ordinary cached load that the compiler
         // may not tear or invent.
-        f32x4 rec[CO_AHEAD];
+        f32x4 rec[CELL_AHEAD];
 #pragma unroll
-        for (uint32_t u = 0; u < CO_AHEAD; ++u) rec[u] = *(const f32x4*)(sorted + min(begin + u, end - 1));
-        for (uint32_t q = begin; q < end; q += CO_AHEAD) {
-          f32x4 next[CO_AHEAD];
-          float d2[CO_AHEAD];
-          uint32_t other[CO_AHEAD], above[CO_AHEAD];
-          bool need[CO_AHEAD];
+        for (uint32_t u = 0; u < CELL_AHEAD; ++u) rec[u] = *(const f32x4*)(sorted + min(begin + u, end - 1));
+        for (uint32_t q = begin; q < end; q += CELL_AHEAD) {
+          f32x4 next[CELL_AHEAD];
+          float d2[CELL_AHEAD];
+          uint32_t other[CELL_AHEAD], above[CELL_AHEAD];
+          bool need[CELL_AHEAD];
 #pragma unroll
-          for (uint32_t u = 0; u < CO_AHEAD; ++u) next[u] = *(const f32x4*)(sorted + min(q + CO_AHEAD + u, end - 1));
+          for (uint32_t u = 0; u < CELL_AHEAD; ++u) next[u] = *(const f32x4*)(sorted + min(q + CELL_AHEAD + u, end - 1));
 #pragma unroll
-          for (uint32_t u = 0; u < CO_AHEAD; ++u) {
+          for (uint32_t u = 0; u < CELL_AHEAD; ++u) {
             d2[u] = distance2(rec[u]), other[u] = __float_as_uint(rec[u].w);
             need[u] = q + u < end && d2[u] <= r2 && other[u] != row && other[u] < len && !(core && !ALL && other[u] > row);
             above[u] = __hip_atomic_load(&parent[need[u] ? other[u] : row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           }
 #pragma unroll
-          for (uint32_t u = 0; u < CO_AHEAD; ++u)
+          for (uint32_t u = 0; u < CELL_AHEAD; ++u)
             if (need[u]) link(other[u], d2[u], above[u]);
 #pragma unroll
-          for (uint32_t u = 0; u < CO_AHEAD; ++u) rec[u] = next[u];
+          for (uint32_t u = 0; u < CELL_AHEAD; ++u) rec[u] = next[u];
         }
       }
     }
@@ -668,7 +516,7 @@ __global__ void __launch_bounds__(CO_THREADS)
 // Pass 6 (row order; its end is select_flag_kernel's: KEEP ALIKE): owner[p] = the root of row p's cluster or CO_NONE,
 // size[root] += 1, flags bit p = row p is a root, tile_counts[tile] = roots of the tile; clusters[job] += the same,
 // noise[job] += rows without a cluster.
-__global__ void __launch_bounds__(CO_THREADS)
+__global__ void __launch_bounds__(CELL_THREADS)
     cluster_flatten_kernel(const ClusterJob* __restrict__ jobs, uint32_t n_jobs, uint32_t* __restrict__ tile_counts,
                            unsigned long long* __restrict__ clusters, unsigned long long* __restrict__ noise,
                            unsigned long long* __restrict__ fault) {
@@ -679,12 +527,12 @@ __global__ void __launch_bounds__(CO_THREADS)
   uint32_t* __restrict__ owner = j.owner;
   uint32_t* __restrict__ size = j.size;
   unsigned long long* __restrict__ flags = j.flags;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK;
   const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);  // (len < 2^32 - span: checked by the host)
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t c = 0, lost = 0;                   // c: wave-uniform
   uint32_t run_root = CO_NONE, run_rows = 0;  // wave-uniform: rows of one root that size[] has not been given yet
-  for (uint32_t base = p0 + wave * 64u; base < p_end; base += CO_THREADS) {  // wave-uniform
+  for (uint32_t base = p0 + wave * 64u; base < p_end; base += CELL_THREADS) {  // wave-uniform
     const uint32_t p = base + lane;
     uint32_t root = CO_NONE;
     bool is_root = false;
@@ -730,7 +578,7 @@ __global__ void __launch_bounds__(CO_THREADS)
 
 // Pass 7 (its start and its prefix are select_compact_kernel's: KEEP ALIKE): the roots of a cloud ranked in row order.
 // labels[root] = rank, roots[rank] = root, sizes[rank] = size[root]; a noise row's label CO_NONE; every row's row_sizes.
-__global__ void __launch_bounds__(CO_THREADS)
+__global__ void __launch_bounds__(CELL_THREADS)
     cluster_rank_kernel(const ClusterJob* __restrict__ jobs, uint32_t n_jobs, const uint32_t* __restrict__ tile_counts) {
   __shared__ uint32_t s_base;
   const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
@@ -751,10 +599,10 @@ __global__ void __launch_bounds__(CO_THREADS)
   uint32_t* __restrict__ row_sizes = j.row_sizes;
   uint32_t* __restrict__ sizes = j.sizes;
   uint32_t* __restrict__ roots = j.roots;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK, n_groups = (len + 63u) >> 6;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK, n_groups = (len + 63u) >> 6;
   const uint32_t p0 = t * span, p_end = min(len, p0 + span);
   uint32_t base = s_base;  // roots of the cloud before this chunk
-  for (uint32_t px0 = p0; px0 < p_end; px0 += CO_CHUNK) {
+  for (uint32_t px0 = p0; px0 < p_end; px0 += CELL_CHUNK) {
     const uint32_t g = (px0 >> 6) + lane;
     const uint64_t word = lane < CO_GROUPS && g < n_groups ? flags[g] : 0ull;
     const uint32_t cnt = (uint32_t)__builtin_popcountll(word);
@@ -776,7 +624,7 @@ __global__ void __launch_bounds__(CO_THREADS)
     base += __shfl(incl, (int)CO_GROUPS - 1, 64);
 #pragma unroll
     for (uint32_t r = 0; r < CO_ROUNDS; ++r) {
-      const uint32_t p = px0 + r * CO_THREADS + threadIdx.x;
+      const uint32_t p = px0 + r * CELL_THREADS + threadIdx.x;
       if (p >= p_end) continue;
       const uint32_t root = owner[p];
       if (root >= len) {  // noise
@@ -797,14 +645,14 @@ __global__ void __launch_bounds__(CO_THREADS)
 }
 
 // Pass 8: the label of every row that is in a cluster and is not its root (no root's label is written here).
-__global__ void __launch_bounds__(CO_THREADS) cluster_label_kernel(const ClusterJob* __restrict__ jobs, uint32_t n_jobs) {
+__global__ void __launch_bounds__(CELL_THREADS) cluster_label_kernel(const ClusterJob* __restrict__ jobs, uint32_t n_jobs) {
   const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
   const ClusterJob& j = jobs[ji];
   const uint32_t* __restrict__ owner = j.owner;
   uint32_t* labels = j.labels;
-  const uint32_t len = j.len, span = j.chunks_per_tile * CO_CHUNK;
+  const uint32_t len = j.len, span = j.chunks_per_tile * CELL_CHUNK;
   const uint32_t p0 = (tile - j.first_tile) * span, p_end = min(len, p0 + span);
-  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += CO_THREADS) {
+  for (uint32_t p = p0 + threadIdx.x; p < p_end; p += CELL_THREADS) {
     const uint32_t root = owner[p];
     if (root < len && root != p) labels[p] = labels[root];
   }
@@ -846,9 +694,9 @@ a3d_status a3d_point_clouds_select_device(a3d_context* ctx, const a3d_point_clou
     j.colors = colors, j.out_colors = out_colors;
     j.capacity = capacities[i];
     j.len = (uint32_t)c.len;
-    A3D_TRY(plan_tiles(c.len, CO_CHUNK, CO_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
+    A3D_TRY(plan_tiles(c.len, CELL_CHUNK, CELL_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
     // the kernels' 32-bit row positions run up to one tile span past len
-    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * CO_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
+    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * CELL_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
                 "a3d_point_clouds_select_device: a cloud within one tile of 2^32 points");
     j.flags = (unsigned long long*)flag_bytes;
     flag_bytes += pad256((c.len + 63) / 64 * 8);
@@ -880,7 +728,7 @@ a3d_status a3d_point_clouds_select_device(a3d_context* ctx, const a3d_point_clou
   uint32_t* d_tile_counts = scratch.tile_counts;
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, jobs.data(), s));
-  const dim3 grid_dim((uint32_t)tiles), block(CO_THREADS);
+  const dim3 grid_dim((uint32_t)tiles), block(CELL_THREADS);
   hipLaunchKernelGGL(select_flag_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, d_tile_counts, d_lens);
   A3D_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(select_compact_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, (const uint32_t*)d_tile_counts,
@@ -917,8 +765,7 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
   std::vector<uint64_t> cloud_of_job;
   std::vector<ByteRange> ranges;
   jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(3 * n);
-  uint64_t tiles = 0;
-  size_t table_bytes = 0, sorted_bytes = 0;  // offsets of a job's arrays inside their parts of the scratch region, for now
+  CellSortPlan plan;
   for (uint64_t i = 0; i < n; ++i) {
     const a3d_point_cloud_view& c = d_clouds[i];
     A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
@@ -928,17 +775,7 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
     j.points = c.points;
     j.out_counts = d_out_counts ? d_out_counts[i] : nullptr;
     j.out_qsum = k ? d_out_qsum[i] : nullptr;
-    j.len = (uint32_t)c.len;
-    A3D_TRY(plan_tiles(c.len, CO_CHUNK, CO_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
-    j.n_tiles = (uint32_t)tiles - j.first_tile;
-    // the kernels' 32-bit point positions run up to one tile span past len
-    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * CO_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
-                "a3d_point_clouds_knn_distance_device: a cloud within one tile of 2^32 points");
-    uint64_t slots = 2;
-    while (slots < 2 * c.len) slots <<= 1;
-    j.slot_mask = slots - 1;
-    j.table = (VoxelSlot*)table_bytes, j.sorted = (CoRecord*)sorted_bytes;
-    table_bytes += slots * sizeof(VoxelSlot), sorted_bytes += pad256(c.len * sizeof(CoRecord));
+    A3D_TRY(cell_sort_plan(&plan, c.len, "a3d_point_clouds_knn_distance_device: a cloud within one tile of 2^32 points", &j));
     jobs.push_back(j), cloud_of_job.push_back(i);
     ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + (uintptr_t)c.len * 12, false});
     if (j.out_counts) ranges.push_back({(uintptr_t)j.out_counts, (uintptr_t)j.out_counts + (uintptr_t)c.len * 4, true});
@@ -954,13 +791,9 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   BatchScratch scratch;  // the words: cursors (kept counts), dropped, 4 sums per job, fault; the tail: hash tables | records
-  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(KnnJob), 6 * n_jobs + 1, 0, table_bytes + sorted_bytes, &scratch));
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(KnnJob), 6 * n_jobs + 1, 0, plan.table_bytes + plan.sorted_bytes, &scratch));
   char* d_tables = scratch.tail;
-  char* d_sorted = scratch.tail + table_bytes;
-  for (KnnJob& j : jobs) {
-    j.table = (VoxelSlot*)(d_tables + (size_t)j.table);
-    j.sorted = (CoRecord*)(d_sorted + (size_t)j.sorted);
-  }
+  for (KnnJob& j : jobs) cell_sort_rebase(&j, d_tables, d_tables + plan.table_bytes);
   const KnnJob* d_jobs = (const KnnJob*)scratch.jobs;
   unsigned long long* d_cursor = scratch.words;
   unsigned long long* d_dropped = d_cursor + n_jobs;
@@ -968,15 +801,10 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
   unsigned long long* d_fault = d_cursor + 6 * n_jobs;
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, jobs.data(), s));
-  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, table_bytes, s));  // every key word empty, every count 0
-  const dim3 grid_dim((uint32_t)tiles), block(CO_THREADS);
+  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, plan.table_bytes, s));  // every key word empty, every count 0
+  const dim3 grid_dim((uint32_t)plan.tiles), block(CELL_THREADS);
   const uint32_t nj = (uint32_t)n_jobs;
-  hipLaunchKernelGGL(knn_count_kernel, grid_dim, block, 0, s, d_jobs, nj, grid, d_dropped, d_fault);
-  A3D_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(knn_place_kernel, grid_dim, block, 0, s, d_jobs, nj, d_cursor);
-  A3D_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(knn_scatter_kernel, grid_dim, block, 0, s, d_jobs, nj, grid, d_fault);
-  A3D_HIP_TRY(hipGetLastError());
+  A3D_TRY(cell_sort_launch(d_jobs, nj, plan.tiles, grid, d_cursor, d_dropped, d_fault, s));
   const unsigned long long* d_kept = d_cursor;
 #define CO_LAUNCH(K, ON_T) \
   hipLaunchKernelGGL((knn_distance_kernel<K, ON_T>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_stats)
@@ -1033,9 +861,8 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
   std::vector<uint64_t> cloud_of_job;
   std::vector<ByteRange> ranges;
   sort_jobs.reserve(n), jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(6 * n);
-  uint64_t tiles = 0;
-  // offsets of a job's arrays inside their parts of the scratch region, for now
-  size_t table_bytes = 0, sorted_bytes = 0, row_bytes = 0, flag_bytes = 0;
+  CellSortPlan plan;
+  size_t row_bytes = 0, flag_bytes = 0;  // offsets of a job's arrays inside their parts of the scratch region, for now
   for (uint64_t i = 0; i < n; ++i) {
     const a3d_point_cloud_view& c = d_clouds[i];
     A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
@@ -1044,19 +871,9 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
     KnnJob k{};
     ClusterJob j{};
     k.points = c.points;
-    k.len = j.len = (uint32_t)c.len;
-    A3D_TRY(plan_tiles(c.len, CO_CHUNK, CO_MAX_TILES, &tiles, &k.first_tile, &k.chunks_per_tile));
-    k.n_tiles = (uint32_t)tiles - k.first_tile;
-    j.first_tile = k.first_tile, j.chunks_per_tile = k.chunks_per_tile;
-    // the kernels' 32-bit point positions run up to one tile span past len
-    A3D_REQUIRE(c.len + (uint64_t)k.chunks_per_tile * CO_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
-                "a3d_point_clouds_cluster_device: a cloud within one tile of 2^32 points");
-    uint64_t slots = 2;
-    while (slots < 2 * c.len) slots <<= 1;
-    k.slot_mask = j.slot_mask = slots - 1;
-    k.table = (VoxelSlot*)table_bytes, k.sorted = (CoRecord*)sorted_bytes;
+    A3D_TRY(cell_sort_plan(&plan, c.len, "a3d_point_clouds_cluster_device: a cloud within one tile of 2^32 points", &k));
+    j.len = k.len, j.first_tile = k.first_tile, j.chunks_per_tile = k.chunks_per_tile, j.slot_mask = k.slot_mask;
     j.parent = (uint32_t*)row_bytes, j.flags = (unsigned long long*)flag_bytes;
-    table_bytes += slots * sizeof(VoxelSlot), sorted_bytes += pad256(c.len * sizeof(CoRecord));
     row_bytes += pad256(c.len * 4), flag_bytes += pad256((c.len + 63) / 64 * 8);
     j.labels = d_out_labels[i];
     j.row_sizes = d_out_row_sizes ? d_out_row_sizes[i] : nullptr;
@@ -1080,21 +897,22 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   // the table: the sort's jobs, then the cluster jobs; the words: cursors (kept counts), dropped, clusters, noise per job,
   // fault; the tail: hash tables | size | owner (these three zeroed by the one fill) | parent | records | ballot words
-  const size_t sort_table = n_jobs * sizeof(KnnJob), zeroed = table_bytes + 2 * row_bytes;
+  const size_t sort_table = n_jobs * sizeof(KnnJob), zeroed = plan.table_bytes + 2 * row_bytes;
   std::vector<char> both(sort_table + n_jobs * sizeof(ClusterJob));
   BatchScratch scratch;
-  A3D_TRY(batch_scratch(ctx, both.size(), 4 * n_jobs + 1, tiles, zeroed + row_bytes + sorted_bytes + flag_bytes, &scratch));
+  A3D_TRY(batch_scratch(ctx, both.size(), 4 * n_jobs + 1, plan.tiles, zeroed + row_bytes + plan.sorted_bytes + flag_bytes,
+                        &scratch));
   char* d_tables = scratch.tail;
-  char* d_size = d_tables + table_bytes;
+  char* d_size = d_tables + plan.table_bytes;
   char* d_owner = d_size + row_bytes;
   char* d_parent = d_owner + row_bytes;
   char* d_sorted = d_parent + row_bytes;
-  char* d_flags = d_sorted + sorted_bytes;
+  char* d_flags = d_sorted + plan.sorted_bytes;
   for (size_t q = 0; q < n_jobs; ++q) {
     KnnJob& k = sort_jobs[q];
     ClusterJob& j = jobs[q];
     const size_t rows_at = (size_t)j.parent;
-    k.table = (VoxelSlot*)(d_tables + (size_t)k.table), k.sorted = (CoRecord*)(d_sorted + (size_t)k.sorted);
+    cell_sort_rebase(&k, d_tables, d_sorted);
     j.table = k.table, j.sorted = k.sorted;
     j.size = (uint32_t*)(d_size + rows_at), j.owner = (uint32_t*)(d_owner + rows_at);
     j.parent = (uint32_t*)(d_parent + rows_at);
@@ -1114,14 +932,9 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, both.data(), s));
   A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, zeroed, s));  // every key word empty, every count, size and owner 0
-  const dim3 grid_dim((uint32_t)tiles), block(CO_THREADS);
+  const dim3 grid_dim((uint32_t)plan.tiles), block(CELL_THREADS);
   const uint32_t nj = (uint32_t)n_jobs;
-  hipLaunchKernelGGL(knn_count_kernel, grid_dim, block, 0, s, d_sort_jobs, nj, grid, d_dropped, d_fault);
-  A3D_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(knn_place_kernel, grid_dim, block, 0, s, d_sort_jobs, nj, d_cursor);
-  A3D_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(knn_scatter_kernel, grid_dim, block, 0, s, d_sort_jobs, nj, grid, d_fault);
-  A3D_HIP_TRY(hipGetLastError());
+  A3D_TRY(cell_sort_launch(d_sort_jobs, nj, plan.tiles, grid, d_cursor, d_dropped, d_fault, s));
   const unsigned long long* d_kept = d_cursor;
 #define CL_LAUNCH(LINK, ALL, HALVE) \
   hipLaunchKernelGGL((cluster_walk_kernel<LINK, ALL, HALVE>), grid_dim, block, 0, s, d_jobs, nj, grid, r2, min_points, d_kept, d_fault)

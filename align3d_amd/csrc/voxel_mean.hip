@@ -49,6 +49,7 @@
 #include <cmath>
 #include <vector>
 
+#include "cell_sort.hpp"   // CellRecord, f32x4, find_slot: shared with the neighbour walks (its sort passes are not: see there)
 #include "voxel_mean.hpp"  // the rule's arithmetic and the run combining: shared with voxel_map.hip (a map of means)
 
 using namespace a3d;
@@ -62,13 +63,6 @@ constexpr uint32_t VM_CHUNK = VM_ROUNDS * VM_THREADS;  // points per chunk: a mu
 constexpr uint32_t VM_GROUPS = VM_CHUNK / 64;          // ballot words per chunk
 constexpr uint32_t VM_MAX_TILES = 4096;
 static_assert(VM_GROUPS <= 64, "a wave's lanes hold the chunk's ballot words");
-
-struct VmRecord {  // a kept point in cell order; the first record of a cell's run is its representative
-  float x, y, z;
-  uint32_t index;
-};
-static_assert(sizeof(VmRecord) == 16, "VmRecord layout");
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct VmSpill {  // the sums of the one cell that starts in a group of 64 records and crosses its end (zero-filled)
   unsigned long long n;
@@ -91,7 +85,7 @@ struct MeanJob {
   uint32_t* out_counts;  // null: no counts are written
   VoxelSlot* table;      // slot_mask + 1 slots, zeroed before the count: key word 0 = empty, else key + 1
   unsigned long long* flags;  // (len + 63) / 64 ballot words
-  VmRecord* sorted;           // len records, the first `kept` of them written
+  CellRecord* sorted;         // len records, the first `kept` of them written; a run's first record is its representative
   uint32_t* row_at;           // len row numbers, written at the first position of every run
   VmSpill* spill;             // (len + 63) / 64 accumulators, zeroed
   unsigned long long slot_mask;
@@ -102,18 +96,6 @@ static_assert(sizeof(MeanJob) == 136, "MeanJob layout");
 
 // The halves of a slot's second word (little-endian: [0] the count, [1] ~lowest index, later the run's start).
 __device__ __forceinline__ uint32_t* slot_half(VoxelSlot* slot, int h) { return (uint32_t*)&slot->best + h; }
-
-// The slot that holds `tag` (key + 1), or ~0 if the table has none (the walk stops at the first empty slot).
-__device__ __forceinline__ unsigned long long find_slot(const VoxelSlot* __restrict__ table, unsigned long long mask,
-                                                        unsigned long long tag) {
-  unsigned long long s = slot_hash(tag - 1) & mask;
-  for (unsigned long long tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
-    const unsigned long long k = table[s].key;
-    if (k == tag) return s;
-    if (k == 0) break;
-  }
-  return ~0ull;
-}
 
 // Pass 1.  dropped[job] += dropped points (zeroed by the host upload); *fault is set if a table were ever full (it cannot
 // be: it has at least two slots per point).
@@ -265,7 +247,7 @@ __global__ void __launch_bounds__(VM_THREADS)
   const float* __restrict__ points = j.points;
   const unsigned long long* __restrict__ flags = j.flags;
   VoxelSlot* table = j.table;
-  VmRecord* sorted = j.sorted;
+  CellRecord* sorted = j.sorted;
   uint32_t* row_at = j.row_at;
   const unsigned long long mask = j.slot_mask;
   const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK, n_groups = (len + 63u) >> 6;
@@ -382,7 +364,7 @@ __global__ void __launch_bounds__(VM_THREADS)
   const uint32_t tile = blockIdx.x, ji = find_job(jobs, n_jobs, tile);
   if (vmean_any_over(jobs, n_jobs, lens, &s_over)) return;
   const MeanJob& j = jobs[ji];
-  const VmRecord* __restrict__ sorted = j.sorted;
+  const CellRecord* __restrict__ sorted = j.sorted;
   const float* __restrict__ normals = j.out_normals ? j.normals : nullptr;
   const uint8_t* __restrict__ colors = j.out_colors ? j.colors : nullptr;
   const uint32_t len = j.len, span = j.chunks_per_tile * VM_CHUNK;
@@ -531,9 +513,9 @@ a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_
     while (slots < 2 * c.len) slots <<= 1;
     j.slot_mask = slots - 1;
     const size_t groups = (c.len + 63) / 64;
-    j.flags = (unsigned long long*)flag_bytes, j.row_at = (uint32_t*)row_bytes, j.sorted = (VmRecord*)sorted_bytes;
+    j.flags = (unsigned long long*)flag_bytes, j.row_at = (uint32_t*)row_bytes, j.sorted = (CellRecord*)sorted_bytes;
     j.table = (VoxelSlot*)table_bytes, j.spill = (VmSpill*)spill_bytes;
-    flag_bytes += pad256(groups * 8), row_bytes += pad256(c.len * 4), sorted_bytes += pad256(c.len * sizeof(VmRecord));
+    flag_bytes += pad256(groups * 8), row_bytes += pad256(c.len * 4), sorted_bytes += pad256(c.len * sizeof(CellRecord));
     table_bytes += slots * sizeof(VoxelSlot), spill_bytes += pad256(groups * sizeof(VmSpill));
     jobs.push_back(j), cloud_of_job.push_back(i);
     // what the call may write is the first min(len, capacity) elements of each output
@@ -570,7 +552,7 @@ a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_
   for (MeanJob& j : jobs) {
     j.flags = (unsigned long long*)(d_flags + (size_t)j.flags);
     j.row_at = (uint32_t*)(d_rows + (size_t)j.row_at);
-    j.sorted = (VmRecord*)(d_sorted + (size_t)j.sorted);
+    j.sorted = (CellRecord*)(d_sorted + (size_t)j.sorted);
     j.table = (VoxelSlot*)(d_tables + (size_t)j.table);
     j.spill = (VmSpill*)(d_spill + (size_t)j.spill);
   }

@@ -1,6 +1,6 @@
 """Clustering of resident clouds (a3d_point_clouds_cluster_device) against the thing it is judged by.  Prints one JSON
 line (and writes it to argv[1] if given: profiles/cloud_cluster_probe.json).
-    python scripts/cloud_cluster_probe.py [out.json] [--parent DIR]
+    python scripts/cloud_cluster_probe.py [out.json] [--parent DIR [--gate-only]]
 
 Shapes, all from tests/golden/rgbd/sample1: (a) one frame's cloud at r = 0.01; (b) the same frame thinned at v = 0.02, at
 r = 0.06; (c) the extract of the v = 0.02 voxel map of every frame under its odometry pose, at r = 0.06; (d) 64 frame
@@ -13,9 +13,12 @@ every union on one root.  Per shape:
     child process; and the mapping record (examples/pcl_map.py --render-track with --clusters 0.02 1 50), a child as well;
   - on the diagnostics build, the product form beside the forms that build keeps (A3D_CLUSTER_LINK=all: union with every
     core neighbour, not the lower-indexed half; A3D_CLUSTER_HALVING=0: no path halving in the link pass).
---parent DIR (a directory that holds the align3d_amd package of the parent commit, built): neighbor_distances(k = 0),
-estimate_normals(counts), select and voxel_downsample are timed in child processes, this build and the parent's in turn,
-three times each (this, parent, parent, this, this, parent); this build's medians must lie inside the parent's own min-max range.
+--parent DIR (a directory that holds the align3d_amd package of the parent commit, built): every entry that walks the
+cell sort of cell_sort.hpp (neighbor_distances at k = 0, 8 and 32, estimate_normals counts only and in full, cluster at
+min_points 1 and 8) and two that do not (select, voxel_downsample) are timed on shapes (a) to (d) in child processes, this
+build and the parent's in turn, three times each (this, parent, parent, this, this, parent).  The gate: for every entry and
+shape, this build's median is at or below the parent's maximum (all_at_or_below_parent_max); whether it also lies inside
+the parent's own min-max range is recorded beside it.  --gate-only: nothing but the gate (profiles/cell_sort_gate.json).
 
 A figure is the time of a window of back-to-back host-synchronous calls between two device events on the context's stream,
 divided by the calls in it (so it includes each call's table upload, the fill and the synchronise, which is what a caller
@@ -101,7 +104,7 @@ class Case:
     def __init__(self, ctx, clouds, cluster=True):
         self.ctx, self.clouds, self.n = ctx, clouds, len(clouds)
         self.views = (_abi.PointCloudViewC * self.n)(*[c.view() for c in clouds])
-        names = ("counts", "normals", "out_points", "out_normals", "mask") + (("labels", "row_sizes", "sizes", "roots") if cluster else ())
+        names = ("counts", "qsum", "curvature", "normals", "out_points", "out_normals", "mask") + (("labels", "row_sizes", "sizes", "roots") if cluster else ())
         wide = ("normals", "out_points", "out_normals")
         self.bufs = {name: [ctx.malloc(max(4, (12 if name in wide else 4) * c.len())) for c in clouds] for name in names}
         for c, d in zip(clouds, self.bufs["mask"]):
@@ -117,6 +120,11 @@ class Case:
                                                                None, self.words, None)
         assert st == 0, st
 
+    def knn(self, radius, k):
+        st = self.ctx.lib.a3d_point_clouds_knn_distance_device(self.ctx.handle, self.views, self.n, radius, k, self.tables["counts"],
+                                                               self.tables["qsum"], self.words, None)
+        assert st == 0, st
+
     def cluster(self, radius, m, row_sizes=True):
         st = self.ctx.lib.a3d_point_clouds_cluster_device(self.ctx.handle, self.views, self.n, radius, m, self.tables["labels"],
                                                           self.tables["row_sizes"] if row_sizes else None, self.tables["sizes"],
@@ -127,6 +135,12 @@ class Case:
         st = self.ctx.lib.a3d_point_clouds_estimate_normals_device(self.ctx.handle, self.views, self.n, radius, 3, None, 0,
                                                                    self.tables["normals"], None, self.tables["counts"],
                                                                    self.words, None)
+        assert st == 0, st
+
+    def estimate_full(self, radius):
+        st = self.ctx.lib.a3d_point_clouds_estimate_normals_device(self.ctx.handle, self.views, self.n, radius, 3, None, 0,
+                                                                   self.tables["normals"], self.tables["curvature"],
+                                                                   self.tables["counts"], self.words, None)
         assert st == 0, st
 
     def downsample(self, voxel):
@@ -152,18 +166,29 @@ class Case:
 def existing_entries(ctx):
     """What a child of the gate measures: entries the parent build has too."""
     out = {}
-    shapes, _ = sample1_shapes(ctx)
-    for (name, radius), cloud in zip(SHAPES, shapes):
-        case = Case(ctx, [cloud], cluster=False)
+    shapes, frames = sample1_shapes(ctx)
+    batches = [[cloud] for cloud in shapes] + [[frames[i % len(frames)] for i in range(64)]]
+    for (name, radius), clouds in zip(GATE_SHAPES, batches):
+        print(name, file=sys.stderr, flush=True)
+        case = Case(ctx, clouds)
         out[name] = dict(measure(ctx, [("neighbor_distances_k0", lambda: case.knn_k0(radius)),
+                                       ("neighbor_distances_k8", lambda: case.knn(radius, 8)),
+                                       ("neighbor_distances_k32", lambda: case.knn(radius, 32)),
                                        ("estimate_normals_counts", lambda: case.estimate_counts(radius)),
+                                       ("estimate_normals_full", lambda: case.estimate_full(radius)),
+                                       ("cluster_m1", lambda: case.cluster(radius, 1)),
+                                       ("cluster_m8", lambda: case.cluster(radius, 8)),
                                        ("select_half", case.select_half),
-                                       ("voxel_downsample_v0.02", lambda: case.downsample(0.02))]), points=cloud.len())
+                                       ("voxel_downsample_v0.02", lambda: case.downsample(0.02))]),
+                         points=sum(c.len() for c in clouds))
         case.free()
     return out
 
 
-ENTRIES = ("neighbor_distances_k0", "estimate_normals_counts", "select_half", "voxel_downsample_v0.02")
+# (shape (e), every row in one cell, takes seconds a call: not gated, as the light path above)
+GATE_SHAPES = SHAPES + (("d_64_frames_one_call_r0.01", 0.01),)
+ENTRIES = ("neighbor_distances_k0", "neighbor_distances_k8", "neighbor_distances_k32", "estimate_normals_counts",
+           "estimate_normals_full", "cluster_m1", "cluster_m8", "select_half", "voxel_downsample_v0.02")
 
 
 def gate(parent):
@@ -176,10 +201,10 @@ def gate(parent):
             env = dict(os.environ, A3D_PROBE_PACKAGE_ROOT=root)
             env.pop("A3D_LIBRARY", None)
             line = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, check=True,
-                                  stdout=subprocess.PIPE, text=True, timeout=240).stdout.strip().splitlines()[-1]
+                                  stdout=subprocess.PIPE, text=True, timeout=480).stdout.strip().splitlines()[-1]
             runs[who].append(json.loads(line))
-    out = {"all_inside": True}
-    for shape, _ in SHAPES:
+    out = {"all_at_or_below_parent_max": True, "all_inside": True}
+    for shape, _ in GATE_SHAPES:
         res = {"points": runs["this"][0][shape]["points"]}
         for entry in ENTRIES:
             t_med = statistics.median(r[shape][entry]["median"] for r in runs["this"])
@@ -188,6 +213,7 @@ def gate(parent):
             p_med = statistics.median(r[shape][entry]["median"] for r in runs["parent"])
             res[entry] = {"this_median": round(t_med, 4), "parent_median": round(p_med, 4), "parent_min": p_min,
                           "parent_max": p_max, "inside": p_min <= t_med <= p_max, "at_or_below_parent_max": t_med <= p_max}
+            out["all_at_or_below_parent_max"] &= res[entry]["at_or_below_parent_max"]
             out["all_inside"] &= res[entry]["inside"]
         out[shape] = res
     return out
@@ -243,8 +269,9 @@ def kernel_times():
         rows = sqlite3.connect(found[0]).execute("select name, start, end from kernels order by start").fetchall()
     per = {}
     for name, start, end in rows:
-        short = name.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-        if short.startswith(("knn_", "cluster_")):
+        # (the sort's kernels are templates of cell_sort.hpp: a3d::cell_count_kernel<(anonymous namespace)::KnnJob>(...))
+        short = name.replace("(anonymous namespace)::", "").replace("void ", "").replace("a3d::", "").split("(")[0]
+        if short.startswith(("knn_", "cluster_", "cell_")):
             per.setdefault(short, []).append((end - start) / 1e3)
     out = {"calls_per_shape": TRACE_CALLS}
     for short, us in per.items():
@@ -282,6 +309,14 @@ def main():
         return
     parent = args[args.index("--parent") + 1] if "--parent" in args else None
     out_path = next((a for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or args[i - 1] != "--parent")), None)
+    if "--gate-only" in args:
+        assert parent, "--gate-only needs --parent DIR"
+        line = json.dumps({"probe": "cloud_cluster", "gate_against_the_parent_build": gate(parent)})
+        print(line)
+        if out_path:
+            with open(out_path, "w") as f:
+                f.write(line + "\n")
+        return
     ctx = Context(0)
     out = {"probe": "cloud_cluster", "launches_per_call": 8}  # (every figure carries its own number of windows)
     shapes, frames = sample1_shapes(ctx)
