@@ -1173,7 +1173,10 @@ a3d_status a3d_tsdf_volume_download(a3d_tsdf_volume* volume, float* out_records,
 /* The inverse of a3d_tsdf_volume_download: every record (and, with `colors`, every colour) of the volume from HOST memory,
  * bit for bit, NaN included: records [nz][ny][nx][2] f32 (D, W), colors [nz][ny][nx] u32 (NULL: the colours stay as they
  * are; non-NULL on a volume without colours -> A3D_MISSING_FIELD).  A NULL volume or records is A3D_INVALID_PARAMETER.  It
- * restores a saved volume, and lets a test set any field: exact zeros, -0, ties, holes. */
+ * restores a saved volume, and lets a test set any field: exact zeros, -0, ties, holes.  W is an integer count in
+ * [0, 2^24]: after an upload of a W that is negative, not an integer or not finite, the results of integrate and raycast
+ * are unspecified.  Any D, NaN and the infinities included, follows the rules as they are written; a hit whose D_prev is
+ * +inf has s = NaN, so its point is NaN and its colour is unspecified. */
 a3d_status a3d_tsdf_volume_upload(a3d_tsdf_volume* volume, const float* records, const uint32_t* colors);
 /* The volume's surface, independent of any viewpoint: a vertex on every crossing edge, with the field's gradient as its
  * normal and a voxel's colour, and (want_faces != 0) triangles by marching TETRAHEDRA on the Kuhn split of every cell, not

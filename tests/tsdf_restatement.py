@@ -31,6 +31,9 @@ class Volume:
         shape = (self.nz, self.ny, self.nx)
         self.D, self.W = np.zeros(shape, F), np.zeros(shape, F)
         self.C = np.zeros(shape + (3,), np.uint8) if colors else None
+        # for the tests' own checks, never read by a rule: the (voxel, row, col) of every update of the last frame, and the
+        # least and greatest colour channel any frame produced BEFORE its cast to u8
+        self.last_pixels, self.color_range = None, [np.inf, -np.inf]
         k, j, i = np.meshgrid(np.arange(self.nz), np.arange(self.ny), np.arange(self.nx), indexing="ij")
         # step 1: pw = origin + (float)index * v
         self.pw = np.stack([self.origin[0] + i.astype(F) * self.v, self.origin[1] + j.astype(F) * self.v,
@@ -41,6 +44,7 @@ class Volume:
         other.__dict__.update(self.__dict__)
         other.D, other.W = self.D.copy(), self.W.copy()
         other.C = None if self.C is None else self.C.copy()
+        other.color_range = list(self.color_range)
         return other
 
     # ---- integrate ---------------------------------------------------------------------------------------------------
@@ -65,6 +69,7 @@ class Volume:
             sdf = (dz - z[idx]).astype(F)  # step 5
             keep &= ~(sdf < -self.tau)
         idx, col, row, sdf = idx[keep], col[keep], row[keep], sdf[keep]
+        self.last_pixels = (idx, row, col)
         d = np.minimum(F(1), (sdf / self.tau).astype(F)).astype(F)
         D, W = self.D.reshape(-1), self.W.reshape(-1)  # (views)
         w_old = W[idx]
@@ -73,8 +78,12 @@ class Volume:
             C = self.C.reshape(-1, 3)
             c_in = np.asarray(colors, np.uint8)[row, col].astype(F)
             mixed = ((C[idx].astype(F) * w_old[:, None]).astype(F) + c_in).astype(F) / w_new[:, None]
-            C[idx] = np.floor((mixed.astype(F) + F(0.5)).astype(F)).astype(np.uint8)
-        D[idx] = (((D[idx] * w_old).astype(F) + d).astype(F) / w_new).astype(F)
+            whole = np.floor((mixed.astype(F) + F(0.5)).astype(F))
+            if whole.size:
+                self.color_range = [min(self.color_range[0], float(whole.min())), max(self.color_range[1], float(whole.max()))]
+            C[idx] = whole.astype(np.uint8)
+        with np.errstate(all="ignore"):  # (an uploaded D of 3e38 overflows D * W: the rule's result is the infinity)
+            D[idx] = (((D[idx] * w_old).astype(F) + d).astype(F) / w_new).astype(F)
         W[idx] = np.minimum(w_new, self.max_weight)
         return len(idx)
 
