@@ -307,6 +307,16 @@ SIGNATURES = {
         _ST,
         [_P, C.c_uint64, C.c_int, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     ),
+    "a3d_tsdf_volume_sample_device": (_ST, [_P, _P, C.c_uint64, C.POINTER(PoseC), _P, _P]),
+    "a3d_tsdf_volume_icp_align_device": (
+        _ST,
+        [_P, C.POINTER(IcpParamsC), C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.POINTER(PoseC)],
+    ),
+    "a3d_tsdf_volume_icp_accumulate_device": (
+        _ST,
+        [_P, C.POINTER(IcpParamsC), C.POINTER(PointCloudViewC), C.POINTER(PoseC), C.POINTER(GnStateC)],
+    ),
+    "a3d_tsdf_volume_icp_last_device_ms": (_ST, [_P, C.POINTER(C.c_float)]),
     "a3d_range_image_set_colors": (_ST, [_P, _P]),
     "a3d_range_image_compute_intensity": (_ST, [_PP, C.c_uint64]),
     "a3d_range_image_pyramids": (_ST, [_PP, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, _PP]),

@@ -1,6 +1,7 @@
-// What the TSDF translation units share (tsdf.hip: integrate, raycast; tsdf_surface.hip: surface extraction): the volume
-// handle, the grid the kernels take by value, and the raycast rule's trilinear sample and clamped rounding, which the
-// surface rule uses unchanged for its normals and colours.
+// What the TSDF translation units share (tsdf.hip: integrate, raycast; tsdf_surface.hip: surface extraction; tsdf_icp.hip:
+// the per-point field query and the point-to-SDF ICP): the volume handle, the grid the kernels take by value, and the
+// raycast rule's trilinear sample and clamped rounding, which the surface rule uses unchanged for its normals and colours
+// and the field query for its distance and direction.
 #pragma once
 #include "cloud_batch.hpp"
 
@@ -13,9 +14,19 @@ struct a3d_tsdf_volume {
   size_t block_bytes = 0, used_bytes = 0;
   float2* records = nullptr;   // [nz][ny][nx] {D, W}
   uint32_t* colors = nullptr;  // [nz][ny][nx] r | g << 8 | b << 16, or null
+  // the working buffers of the point-to-SDF ICP (tsdf_icp.hip): one block of the context's, taken by the first align or
+  // accumulate and released with the volume
+  void* icp_block = nullptr;
+  size_t icp_block_bytes = 0;
+  uint32_t icp_blocks = 0;  // block partials it has room for
+  hipEvent_t icp_ev0 = nullptr, icp_ev1 = nullptr;  // bracket the iteration launches of the last align
+  float icp_last_device_ms = 0.f;
 };
 
 namespace a3d {
+
+// Releases the ICP working buffers of a volume that is being freed (tsdf_icp.hip).
+void tsdf_icp_release(a3d_tsdf_volume* volume);
 
 constexpr uint64_t TS_MAX_WEIGHT = 1ull << 24;  // integers up to here are exact in f32
 

@@ -1579,8 +1579,10 @@ class DeviceTsdfVolume:
     rays (integrate: a running mean of the truncated projective distance, capped at max_weight observations; colors=True
     keeps a running mean colour and every image must have colours), and raycast() gives the dense model image a camera
     sees: points, normals from the distance field's gradient, colours, an ordinary DeviceRangeImage for pyramid(),
-    MultiscaleAlign and DevicePointCloud.from_range_image.  truncation defaults to 4 voxel sizes.  The rules are stated
-    in include/align3d_hip.h; every result is the same bits on every run."""
+    MultiscaleAlign and DevicePointCloud.from_range_image.  sample() answers how far a point is from the fused surface
+    and in which direction, and align() aligns a resident cloud against that field directly (point-to-SDF ICP: no
+    raycast, no camera).  truncation defaults to 4 voxel sizes.  The rules are stated in include/align3d_hip.h; every
+    result is the same bits on every run."""
 
     def __init__(self, ctx, dims, voxel_size, origin, truncation=None, max_weight=64, colors=False):
         try:
@@ -1713,6 +1715,76 @@ class DeviceTsdfVolume:
         wound counter-clockwise seen from outside; the vertices carry normals, and colours iff the volume keeps them."""
         cloud, d_faces, faces = self._extract(min_weight, True, True, self.colors)
         return DeviceTriangleMesh(cloud, d_faces, faces)
+
+    def _resident_source(self, cloud, what):
+        if not isinstance(cloud, DevicePointCloud):
+            raise TypeError(f"DeviceTsdfVolume.{what} takes a DevicePointCloud (got {type(cloud).__name__}); there is no host fallback")
+        if cloud.ctx is not self.ctx:
+            raise _abi.InvalidParameter(f"DeviceTsdfVolume.{what}: the cloud must live on the volume's context")
+        return cloud
+
+    def sample(self, queries, pose=None):
+        """The field at every point of `queries` (a3d_tsdf_volume_sample_device), a DevicePointCloud of the volume's
+        context or an [m, 3] float32 array (uploaded for the call), moved by `pose` first (None: as they are).  Returns
+        host arrays (distance [m] float32, normals [m, 3] float32): the signed metric distance to the fused surface,
+        positive in free space, and the unit direction of growing distance in the world frame.  NaN and a zero normal
+        where the field has no value (outside the volume, or beside a voxel never observed); the distance with a zero
+        normal where it has no direction (at the truncation, or beside a hole).  The volume is not changed."""
+        ctx = self.ctx
+        own = None
+        if isinstance(queries, DevicePointCloud):
+            d_q, m = self._resident_source(queries, "sample").d_points, queries.n
+        else:
+            q = np.ascontiguousarray(queries, np.float32)
+            if q.ndim != 2 or q.shape[1] != 3:
+                raise _abi.InvalidParameter("DeviceTsdfVolume.sample: queries is a DevicePointCloud or an [m, 3] array")
+            m = len(q)
+            d_q = own = ctx.to_device(q) if m else None
+        distance, normals = np.empty(m, np.float32), np.empty((m, 3), np.float32)
+        if m == 0:
+            return distance, normals
+        pose = None if pose is None else C.byref(pose.to_c())
+        d_dist = d_nrm = None
+        try:
+            d_dist, d_nrm = ctx.malloc(m * 4), ctx.malloc(m * 12)
+            _abi.check(ctx.lib.a3d_tsdf_volume_sample_device(self.handle, d_q, m, pose, d_dist, d_nrm),
+                       "a3d_tsdf_volume_sample_device")
+            ctx.to_host(d_dist, distance), ctx.to_host(d_nrm, normals)
+        finally:
+            for p in (own, d_dist, d_nrm):
+                if p is not None:
+                    ctx.free(p)
+        return distance, normals
+
+    def align(self, cloud, params, initial=None):
+        """Frame-to-model point-to-plane ICP against the field itself (a3d_tsdf_volume_icp_align_device): Icp.align's loop
+        with the field's distance and gradient in place of the kd-tree, started from `initial` (None: Transform.eye()).
+        Returns the Transform that maps `cloud` as given into the volume's world frame; no raycast, no pyramid, no
+        tree, and the volume is not changed.  The cloud needs normals."""
+        v = self._resident_source(cloud, "align").view()
+        p = params.to_c()
+        init = None if initial is None else C.byref(initial.to_c())
+        out = _abi.PoseC()
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_icp_align_device(self.handle, C.byref(p), C.byref(v), init, C.byref(out)),
+                   "a3d_tsdf_volume_icp_align_device")
+        return Transform.from_c(out)
+
+    def accumulate(self, cloud, params, pose=None):
+        """One pass of align's per-point loop under `pose` (None: the identity); test hook, as Icp.accumulate:
+        {H, g, ssq, count}."""
+        v = self._resident_source(cloud, "accumulate").view()
+        p = params.to_c()
+        t = None if pose is None else C.byref(pose.to_c())
+        g = _abi.GnStateC()
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_icp_accumulate_device(self.handle, C.byref(p), C.byref(v), t, C.byref(g)),
+                   "a3d_tsdf_volume_icp_accumulate_device")
+        return g.as_dict()
+
+    def last_device_ms(self):
+        """Device time (ms) of the iteration launches of the most recent align."""
+        ms = C.c_float()
+        _abi.check(self.ctx.lib.a3d_tsdf_volume_icp_last_device_ms(self.handle, C.byref(ms)))
+        return ms.value
 
     def info(self):
         """{dims, voxel_size, truncation, origin, max_weight, colors} as the library holds them (a3d_tsdf_volume_info)."""

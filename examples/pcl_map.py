@@ -3,7 +3,7 @@
     python examples/pcl_map.py [tests/golden/rgbd/sample1] [--max-frames N]
         [--voxel V [--mean] [--online [--check-batch | --window-box R | --window-frames W] [--render-track]]] [--colors]
         [--estimate-normals R] [--remove-plane T] [--radius-outliers R N] [--stat-outliers R K A] [--clusters R M S]
-        [--tsdf-track V [--tsdf-mesh FILE]] [--out map.npy]
+        [--tsdf-track V [--tsdf-direct] [--tsdf-mesh FILE]] [--out map.npy]
 examples/pcl_odometry.py plus the last step: frames -> RangeImageBuilder (one batched build) ->
 DevicePointCloud.from_range_images (one pass) -> IcpBatch over the consecutive pairs -> TrajectoryBuilder, and then the
 camera-to-world poses go into DevicePointCloud.merge(clouds, poses): every frame's cloud in world coordinates, back to
@@ -51,7 +51,10 @@ all frames) stays out of the map, and the cluster filter then sees objects inste
 runs the --render-track loop against a dense model instead, on its own (no --voxel needed): every frame is fused into a
 DeviceTsdfVolume of voxel size V (truncation 4 V, with colours) that encloses the first frame's cloud with half a metre to
 spare, the model image is raycast from it at the predicted pose (samples every 2 V), and the same mean-trajectory-error
-line is printed; the map that follows is built from the odometry poses as without it.  --tsdf-mesh FILE then takes the
+line is printed; the map that follows is built from the odometry poses as without it.  --tsdf-direct replaces the
+correction step by DeviceTsdfVolume.align(clouds[k], IcpParams.default(), initial=pose), the frame's cloud against the
+distance field itself: no raycast, no pyramid and no MultiscaleAlign, and the same line is printed for this route.
+--tsdf-mesh FILE then takes the
 fused volume's surface out as a triangle mesh (DeviceTsdfVolume.extract_triangle_mesh, observed at least twice) and as a
 point cloud (extract_point_cloud), prints their counts and saves points, normals, colors and faces to FILE as an .npz (file
 formats such as PLY are out of scope).  The map is downloaded once, for its bounding box; prints the point count and the box, and --out writes the points ([N, 3] f32)."""
@@ -100,6 +103,8 @@ ap.add_argument("--clusters", nargs=3, type=float, default=None, metavar=("R", "
                      "with radius R metres and min_points M")
 ap.add_argument("--tsdf-track", type=float, default=None, metavar="V",
                 help="correct each frame's pose against a raycast of a TSDF volume of voxel size V that the frames are fused into")
+ap.add_argument("--tsdf-direct", action="store_true",
+                help="with --tsdf-track: align each frame's cloud against the volume's distance field itself, without a raycast")
 ap.add_argument("--tsdf-mesh", default=None, metavar="FILE",
                 help="with --tsdf-track: save the fused volume's surface (points, normals, colors, faces) to this .npz file")
 ap.add_argument("--out", default=None, help="write the map's points to this .npy file (with --colors: and <out>_colors.npy)")
@@ -123,6 +128,8 @@ if args.render_track and args.check_batch:
     ap.error("--check-batch compares maps built under the same poses: not with --render-track")
 if args.tsdf_mesh and args.tsdf_track is None:
     ap.error("--tsdf-mesh needs --tsdf-track")
+if args.tsdf_direct and args.tsdf_track is None:
+    ap.error("--tsdf-direct needs --tsdf-track")
 args.colors = args.colors or args.render_track  # (the intensity term reads the map's colours)
 
 ctx = Context(0)
@@ -171,6 +178,12 @@ if args.tsdf_track is not None:  # frame-to-model tracking against a dense model
         pose = camera_to_world[0]
         if k > 0:
             pose = corrected[-1] * poses[k - 1] if status[k - 1] == 0 else corrected[-1]  # the odometry's prediction
+        if k > 0 and args.tsdf_direct:  # the frame's cloud against the field itself, from the predicted pose
+            try:
+                pose = volume.align(clouds[k], IcpParams.default(), initial=pose)
+            except A3dError as e:
+                print(f"frame {k}: no correction against the volume's field ({e})")
+        elif k > 0:
             model = volume.raycast(cam, pose, 0.3, z_far).pyramid(3)
             try:
                 aligner = MultiscaleAlign.new(ctx, MsIcpParams.default(), model)
@@ -185,8 +198,9 @@ if args.tsdf_track is not None:  # frame-to-model tracking against a dense model
     print(f"tsdf volume {tuple(int(d) for d in dims)} voxels of {args.tsdf_track} m")
     truth = ds.trajectory()
     if truth is not None:
+        route = "the volume's field" if args.tsdf_direct else "the raycast volume"
         print(f"mean trajectory error over {len(corrected)} frames: odometry alone {mean_error(truth, camera_to_world):.4e} m, "
-              f"corrected against the raycast volume {mean_error(truth, corrected):.4e} m")
+              f"corrected against {route} {mean_error(truth, corrected):.4e} m")
     if args.tsdf_mesh:  # the surface of what was fused, independent of any viewpoint
         mesh, surface = volume.extract_triangle_mesh(min_weight=2), volume.extract_point_cloud(min_weight=2)
         print(f"tsdf surface (observed at least twice): mesh of {mesh.len_vertices} vertices and {mesh.len_faces} triangles, "

@@ -1225,6 +1225,65 @@ a3d_status a3d_tsdf_volume_extract_surface(a3d_tsdf_volume* volume, uint64_t min
                                            uint64_t vertex_capacity, uint32_t* d_out_faces, uint64_t face_capacity,
                                            uint64_t* out_vertices, uint64_t* out_faces);
 
+/* ---- Aligning against the volume: the field query and point-to-SDF ICP ---------------------- */
+
+/* A signed distance field is an alignment target with no association step: it tells every point how far it is from the
+ * surface and in which direction (the frame-to-model tracker of Bylow et al. and Canelhas' SDF tracker).  The rule, for a
+ * query point q in the WORLD frame, after its optional pose (Transform::transform_vector); all of it f32, every operation
+ * rounded on its own:
+ *   1. g = (q - origin) / v per component: the raycast rule's g() without the camera.
+ *   2. D = tri(g), step 3 of the raycast rule unchanged: the inside-the-volume test in f32, all eight corners W > 0, the
+ *      lerp order x, y, z.  An invalid sample means NO VALUE.
+ *   3. The sample is NO CORRESPONDENCE unless |D| < 1: at the truncation the field is clamped and carries no direction.
+ *      A NaN fails.
+ *   4. The gradient is step 6 of the raycast rule at g: G = (tri(g + ex) - tri(g - ex), the same with ey, with ez) at unit
+ *      voxel offsets, len = sqrt(Gx * Gx + Gy * Gy + Gz * Gz) summed left to right; no correspondence if one of the six
+ *      samples is invalid or len is 0 or not finite; otherwise n = G / len, in the WORLD frame (nothing is rotated back).
+ *      D grows towards free space, so n points out of the surface, the way a frame cloud's normals do.
+ *   5. d = D * tau is the signed metric distance; the associated point is t = (q.x - d * n.x, q.y - d * n.y,
+ *      q.z - d * n.z), its normal is n and its squared distance is d2 = d * d.
+ * Where the volume was fused from range images D is the PROJECTIVE distance along the viewing rays, so d overstates the
+ * distance to a surface seen at a slant; near the surface the zero set and the direction are what the alignment uses.
+ * This is NOT Icp over a3d_tsdf_volume_extract_surface's point cloud, which associates by a kd-tree: there is no parity
+ * with it, only the rule above.  Weights by distance or angle, a robust kernel, colour terms, several sources per call, a
+ * coarse-to-fine schedule and an analytic one-cell gradient are NOT built.
+ * All entries are host-synchronous and ordered on the context's stream like the other volume calls; the volume is never
+ * written, so clear, upload and integrate may follow. */
+
+/* The field query of steps 1-5 for m resident points, one launch: d_queries [m][3] f32, pose_host NULL = the queries as
+ * they are, bit for bit; d_out_distance [m] f32 gets d and d_out_normals [m][3] f32 gets n.  A point with no value gets
+ * the distance bits 0x7FC00000 and the normal +0, +0, +0.  A point with a value but no direction (|D| >= 1 or a failure
+ * of step 4) keeps its d and gets the +0 normal; a d that is a NaN (an uploaded NaN or infinity among the corners) is
+ * written as 0x7FC00000 too, and d = -0 is kept as -0.  Clearance and collision queries against the fused model are this
+ * call.  m == 0 is A3D_OK and touches nothing.  Decided on the host before any launch: a NULL volume, or with m > 0 a NULL
+ * d_queries, d_out_distance or d_out_normals, m >= 2^31, and outputs that overlap each other or the queries are
+ * A3D_INVALID_PARAMETER. */
+a3d_status a3d_tsdf_volume_sample_device(a3d_tsdf_volume* volume, const float* d_queries, uint64_t m,
+                                         const a3d_pose* pose_host, float* d_out_distance, float* d_out_normals);
+/* Frame-to-model ICP: Icp::align's loop (src/icp/pcl_icp.rs:59-106) with the field query above in place of the kd-tree,
+ * started from initial_host (NULL = Transform::eye()): the returned pose maps the source AS GIVEN into the volume's world
+ * frame.  Per source point: p = q is the point under the pose, sn its normal under the pose (transform_normal), and the
+ * associated point t, its normal n and d2 of step 5 go through the per-point tail of a3d_pcl_icp_align_device as it is:
+ * the gate max_distance squared against d2 (reject iff d2 > it), the strict normal-angle gate on sn . n, the residual
+ * (t - p) . n, the Jacobian [n, p x n], the weight, max_iterations (0 returns the initial pose bit for bit), the best-pose
+ * rule and the solve-failure status: A3D_SOLVE_FAILED when no point passes, with the pose reached so far in out_pose.
+ * d_source: DEVICE pointers on the volume's context, read during the call.  The launch geometry follows the source length
+ * and the device only, never the volume's size.  The working buffers (two states, two partial sets, the out pose; a few
+ * hundred bytes per CU) belong to the volume: allocated on first use, freed with it.
+ * Decided on the host before any launch, in this order: a NULL volume, params, d_source, d_source->points or out_pose
+ * -> A3D_INVALID_PARAMETER; a source with len == 0 or len >= 2^31 -> A3D_INVALID_PARAMETER; a source without normals ->
+ * A3D_MISSING_FIELD. */
+a3d_status a3d_tsdf_volume_icp_align_device(a3d_tsdf_volume* volume, const a3d_icp_params* params,
+                                            const a3d_point_cloud_view* d_source, const a3d_pose* initial_host,
+                                            a3d_pose* out_pose);
+/* One pass of that per-point loop under `pose` (NULL = eye), summed in f64 as a3d_pcl_icp_accumulate: test hook.  The
+ * same refusals. */
+a3d_status a3d_tsdf_volume_icp_accumulate_device(a3d_tsdf_volume* volume, const a3d_icp_params* params,
+                                                 const a3d_point_cloud_view* d_source, const a3d_pose* pose,
+                                                 a3d_gn_state* out_state);
+/* Instrumentation: device time (ms) of the iteration launches of the most recent a3d_tsdf_volume_icp_align_device. */
+a3d_status a3d_tsdf_volume_icp_last_device_ms(a3d_tsdf_volume* volume, float* out_ms);
+
 /* ---- R3dTree (src/kdtree.rs:19-106) ------------------------------------------------------- */
 
 /* R3dTree::new(&points): `points` [n][3] f32 in host memory are uploaded and the tree is built ON THE DEVICE
