@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(256)
                            int32_t* __restrict__ status_out, float* __restrict__ matrices_out) {
   __shared__ uint32_t s_state[JOB_WORDS];
   const int j = blockIdx.x;
-  head_advance(states_in + j, nullptr, partials_in + (size_t)j * job_stride, head, j, s_state, true);
+  head_advance<256>(states_in + j, nullptr, partials_in + (size_t)j * job_stride, head, j, s_state, true);
   if (threadIdx.x == 0) {
     const float* f = (const float*)s_state;
     const Pose p{{f[0], f[1], f[2]}, {f[3], f[4], f[5], f[6]}};
@@ -63,6 +63,18 @@ __global__ void __launch_bounds__(256)
       for (int k = 0; k < 16; ++k) matrices_out[(size_t)j * 16 + k] = m[k];
     }
   }
+}
+
+// The solve of one iteration as a launch of its own (image ICP, a level that runs split: image_icp.hip): one block per
+// job sums the job's partials of the previous pixel launch and advances the state from states_in into states_out —
+// head_advance as every block of a head-form launch runs it, once per job.  It owns the job's trace row.
+// (256, 4): within 128 VGPRs, so that a block fits the slot that a departing pixel block frees.
+__global__ void __launch_bounds__(256, 4)
+    job_solve_head_kernel(const JobState* __restrict__ states_in, JobState* __restrict__ states_out,
+                          const float* __restrict__ partials_in, uint32_t job_stride, HeadArgs head) {
+  __shared__ uint32_t s_state[JOB_WORDS];
+  const int j = blockIdx.x;
+  head_advance<256>(states_in + j, states_out + j, partials_in + (size_t)j * job_stride, head, j, s_state, true);
 }
 
 // a3d_selftest_transform: item i -> T = exp(Se3(update_i)) * pose_i with the tail's own device functions
@@ -98,6 +110,15 @@ a3d_status launch_job_finish_head(hipStream_t stream, const JobState* states_in,
                                   int32_t* status_out, float* matrices_out, int n_jobs) {
   hipLaunchKernelGGL(job_finish_head_kernel, dim3(n_jobs), dim3(256), 0, stream, states_in, partials_in,
                      partials_job_stride, head, poses_out, status_out, matrices_out);
+  A3D_HIP_TRY(hipGetLastError());
+  return A3D_OK;
+}
+
+a3d_status launch_job_solve_head(hipStream_t stream, const JobState* states_in, JobState* states_out,
+                                 const float* partials_in, uint32_t partials_job_stride, const HeadArgs& head,
+                                 int n_jobs) {
+  hipLaunchKernelGGL(job_solve_head_kernel, dim3(n_jobs), dim3(256), 0, stream, states_in, states_out, partials_in,
+                     partials_job_stride, head);
   A3D_HIP_TRY(hipGetLastError());
   return A3D_OK;
 }

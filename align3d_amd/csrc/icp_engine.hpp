@@ -58,6 +58,10 @@ struct HeadArgs;
 a3d_status launch_job_finish_head(hipStream_t stream, const JobState* states_in, const float* partials_in,
                                   uint32_t partials_job_stride, const HeadArgs& head, Pose* poses_out,
                                   int32_t* status_out, float* matrices_out, int n_jobs);
+// The solve alone, one block per job: advances states_in into states_out from the partials of the last pixel launch.
+a3d_status launch_job_solve_head(hipStream_t stream, const JobState* states_in, JobState* states_out,
+                                 const float* partials_in, uint32_t partials_job_stride, const HeadArgs& head,
+                                 int n_jobs);
 // Converts the 58 f64 sums of launch_gn_readback into the ABI's two a3d_gn_state.
 void gn_states_from_sums(const double sums[GN_PARTIAL], a3d_gn_state* geom, a3d_gn_state* color);
 // Device self-test of the pose arithmetic (a3d_selftest_transform): device arrays, n items.
@@ -258,7 +262,7 @@ __device__ __forceinline__ Pose tail_exp_se3(const float update[6]) {
   return exp_se3_trig(update, tg);
 }
 
-// One wave (threads 0..63 of the block).  Lane k < 18 holds word k of the job's state in `state_bits`; `sums` = the
+// One wave of the block (head_advance picks which).  Lane k < 18 holds word k of the job's state in `state_bits`; `sums` = the
 // 58 f64 totals of the iteration being finished (LDS).  Leaves the job's new state in s_state[0..18) (LDS) and, when
 // st_out is given, in global memory.  Same operations as gn_finish_block, except that the Cholesky's column scaling
 // and the substitutions multiply by the refined 1 / sqrt(pivot) instead of dividing (f64 results within 1-2 ulp,
@@ -577,7 +581,7 @@ __device__ __forceinline__ bool block_publish_and_finish(float* __restrict__ job
 // Every thread of the block calls it (blocks of >= 256 threads).  Sums the job's `h.tiles` partials of the previous
 // launch — thread (component pair cg, slice s) adds tiles s, s + 8, ... in tile order, then the eight slices in a
 // fixed order: the same order as the last-block form above, so both forms give the same bits — runs the solve on
-// wave 0 and leaves the job's state in s_state (LDS, JOB_WORDS words) behind a block barrier.
+// wave `solver_wave` and leaves the job's state in s_state (LDS, JOB_WORDS words) behind a block barrier.
 // COHERENT: the partials were written by other blocks of the SAME launch (the persistent kernel): every load is an
 // agent-scope (sc1) load that bypasses this CU's L1.  Otherwise a kernel boundary published them: plain loads.
 template <bool COHERENT>
@@ -585,7 +589,7 @@ __device__ __forceinline__ unsigned long long ld_partial_pair(const unsigned lon
   if (COHERENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return *p;
 }
-// `state_bits`: lane k < JOB_WORDS of wave 0 holds word k of the job's current state.
+// `state_bits`: lane k < JOB_WORDS of wave `solver_wave` holds word k of the job's current state.
 template <bool COHERENT>
 __device__ __forceinline__ void head_sum_and_advance(uint32_t state_bits, const float* prev_partials, const HeadArgs& h,
                                                      int job, uint32_t* s_state, bool write_trace,
@@ -662,11 +666,23 @@ __device__ __forceinline__ void head_sum_and_advance(uint32_t state_bits, const 
 // block's other three waves wait: it runs at one wave's issue rate.  A CU holds up to four blocks of the batch kernel, and
 // the runtime places wave w of every block on SIMD w: with the solve always on wave 0, four resident blocks' solves queued
 // on one SIMD while three SIMDs idled.  The solving wave now rotates with the block's position in the grid.
+// The head stamps (A3D_HSTAMP) are taken by the block's thread 0, and slots 3..5 lie inside the solve: a stamping build
+// keeps the solve on wave 0.
 #ifndef A3D_HEAD_ROTATE
+#if defined(A3D_DIAGNOSTICS) && defined(A3D_TAIL_STAMPS)
+#define A3D_HEAD_ROTATE 0
+#else
 #define A3D_HEAD_ROTATE 1
 #endif
+#endif
+#if defined(A3D_DIAGNOSTICS) && defined(A3D_TAIL_STAMPS) && A3D_HEAD_ROTATE
+#error "A3D_TAIL_STAMPS needs A3D_HEAD_ROTATE=0: thread 0 takes the solve's stamps"
+#endif
+// BLOCK: the caller's block size; the rotation and the eight slices of the sum need four waves.
+template <int BLOCK>
 __device__ __forceinline__ void head_advance(const JobState* st_in, JobState* st_out, const float* prev_partials,
                                              const HeadArgs& h, int job, uint32_t* s_state, bool write_trace) {
+  static_assert(BLOCK >= 256 && BLOCK % 64 == 0, "head_advance needs at least four whole waves");
   const int solver_wave = A3D_HEAD_ROTATE ? (int)((blockIdx.x + blockIdx.y) & 3u) : 0;
   uint32_t state_bits = 0;
   const int lane = (int)threadIdx.x - 64 * solver_wave;

@@ -691,7 +691,11 @@ __device__ __forceinline__ void pixel_pass(const LevelDesc& d, const Gates& gt, 
 // CLASSIC (diagnostics build only): the step order of pixel_pass before B(k+1) moved ahead of C(k), as a cross-check.
 // SHORT (with DEPTH16): every focal length of the batch's level-0 images passes short_division_proven too, and the
 // rebuilt points divide by them in three operations (div_short) instead of five.
-template <bool ZMASK, bool DEPTH16, bool CLASSIC = false, bool SHORT = false, bool LATE = false>
+// NOHEAD: the level runs split (batch_enqueue): job_solve_head_kernel (icp_engine.hip) has finished the previous
+// iteration once per pair and left the state in states_in, so the block takes pose and status from there with
+// wave-uniform loads and goes straight to its pixel pass; states_out, partials_in and `head` are not used.  Same tiles,
+// same ppt, same partial layout as the head form: every partial has the same bits.
+template <bool ZMASK, bool DEPTH16, bool CLASSIC = false, bool SHORT = false, bool LATE = false, bool NOHEAD = false>
 __global__ void __launch_bounds__(256, 1)
     image_icp_head_kernel(const LevelDesc* __restrict__ descs, const JobState* __restrict__ states_in,
                           JobState* __restrict__ states_out, Gates gt, const float* __restrict__ partials_in,
@@ -720,13 +724,22 @@ __global__ void __launch_bounds__(256, 1)
   if (D16 & D16_SRC) stride = make_src_stride(d.src_w);
   const SrcPx s0 = pixel_source_at<ZMASK, D16>(d, base, ppt, 0), s1 = pixel_source_at<ZMASK, D16>(d, base, ppt, 1, &s0, &stride);
   A3D_HEAD_STAMP(1);  // descriptor loaded, first source pixels requested
-  head_advance(states_in + pair, tile == 0 ? states_out + pair : nullptr, partials_in + (size_t)pair * job_stride, head,
-               pair, s_state, tile == 0);
-  A3D_HEAD_STAMP(2);  // previous iteration finished: partials summed, solve, pose update
-  if ((int)s_state[15] == A3D_OK) {  // a failed job stays frozen: its blocks contribute nothing
-    auto uni = [&](int k) { return __uint_as_float(__builtin_amdgcn_readfirstlane(s_state[k])); };
-    const Pose T{{uni(0), uni(1), uni(2)}, {uni(3), uni(4), uni(5), uni(6)}};
-    pixel_pass<ZMASK, D16, CLASSIC, SHORT, LATE>(d, gt, T, base, ppt, s0, s1, acc);
+  if constexpr (NOHEAD) {
+    const JobState* st = states_in + pair;  // (uniform address, read-only for this launch: scalar loads)
+    A3D_HEAD_STAMP(2);
+    if (st->status == A3D_OK) {  // a failed job stays frozen: its blocks contribute nothing
+      const Pose T = st->pose;
+      pixel_pass<ZMASK, D16, CLASSIC, SHORT, LATE>(d, gt, T, base, ppt, s0, s1, acc);
+    }
+  } else {
+    head_advance<256>(states_in + pair, tile == 0 ? states_out + pair : nullptr, partials_in + (size_t)pair * job_stride,
+                      head, pair, s_state, tile == 0);
+    A3D_HEAD_STAMP(2);  // previous iteration finished: partials summed, solve, pose update
+    if ((int)s_state[15] == A3D_OK) {  // a failed job stays frozen: its blocks contribute nothing
+      auto uni = [&](int k) { return __uint_as_float(__builtin_amdgcn_readfirstlane(s_state[k])); };
+      const Pose T{{uni(0), uni(1), uni(2)}, {uni(3), uni(4), uni(5), uni(6)}};
+      pixel_pass<ZMASK, D16, CLASSIC, SHORT, LATE>(d, gt, T, base, ppt, s0, s1, acc);
+    }
   }
   A3D_HEAD_STAMP(3);  // pixel pass done
   block_reduce_store<GN_PARTIAL, false>(acc, partials_out + (size_t)pair * job_stride + (size_t)tile * GN_PARTIAL);
@@ -1520,28 +1533,31 @@ a3d_status launch_pixel_kernel(a3d_multiscale_batch* b, uint32_t level, const So
 #endif  // A3D_DIAGNOSTICS
 
 // One per-iteration launch (head-solve form) of pairs [p0, p0 + count) at `level`: launch number `seq` of the sequence.
+// NOHEAD: the level runs split — the solve launch of this iteration (launch_solve_kernel, below) has already written
+// the state buffer that the head form would write, and the pixel launch reads its pose from there.
+template <bool NOHEAD>
 a3d_status launch_head_kernel(a3d_multiscale_batch* b, uint32_t level, uint32_t seq, const HeadArgs& prev, uint32_t p0,
                               uint32_t count, hipStream_t s) {
   const uint32_t P = b->n_pairs;
   const uint32_t job_stride = b->max_tiles * GN_PARTIAL;
-  const JobState* st_in = b->d_states + (size_t)(seq & 1u) * P + p0;
+  const JobState* st_in = b->d_states + (size_t)((NOHEAD ? seq + 1u : seq) & 1u) * P + p0;
   JobState* st_out = b->d_states + (size_t)((seq + 1u) & 1u) * P + p0;
   const float* part_in = b->d_partials + (size_t)((seq + 1u) & 1u) * b->partials_half + (size_t)p0 * job_stride;
   float* part_out = b->d_partials + (size_t)(seq & 1u) * b->partials_half + (size_t)p0 * job_stride;
   const LevelDesc* descs = b->d_descs + (size_t)level * P + p0;
+#define A3D_LAUNCH_HEAD(ZM, D16, CL, SH, LT)                                                                            \
+  hipLaunchKernelGGL((image_icp_head_kernel<ZM, D16, CL, SH, LT, NOHEAD>), dim3(b->tiles[level], count), dim3(256), 0, s, \
+                     descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev)
 #ifdef A3D_DIAGNOSTICS
   // A3D_ICP_STEP_ORDER=classic: the pixel loop in its earlier order (the map cell requested by stage C): the same bits
   const char* oenv = A3D_DIAG_ENV("A3D_ICP_STEP_ORDER");
   if (oenv && strcmp(oenv, "classic") == 0) {
     if (b->depth16 && level == 0)
-      hipLaunchKernelGGL((image_icp_head_kernel<true, true, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
-                         st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+      A3D_LAUNCH_HEAD(true, true, true, false, false);
     else if (b->zmask)
-      hipLaunchKernelGGL((image_icp_head_kernel<true, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
-                         st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+      A3D_LAUNCH_HEAD(true, false, true, false, false);
     else
-      hipLaunchKernelGGL((image_icp_head_kernel<false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
-                         st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+      A3D_LAUNCH_HEAD(false, false, true, false, false);
     A3D_HIP_TRY(hipGetLastError());
     return A3D_OK;
   }
@@ -1550,35 +1566,39 @@ a3d_status launch_head_kernel(a3d_multiscale_batch* b, uint32_t level, uint32_t 
   const char* renv = A3D_DIAG_ENV("A3D_ICP_RESAMPLE");
   if (renv && strcmp(renv, "late") == 0) {
     if (b->depth16 && level == 0 && b->short_div)
-      hipLaunchKernelGGL((image_icp_head_kernel<true, true, false, true, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
-                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+      A3D_LAUNCH_HEAD(true, true, false, true, true);
     else if (b->depth16 && level == 0)
-      hipLaunchKernelGGL((image_icp_head_kernel<true, true, false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
-                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+      A3D_LAUNCH_HEAD(true, true, false, false, true);
     else if (b->zmask)
-      hipLaunchKernelGGL((image_icp_head_kernel<true, false, false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
-                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+      A3D_LAUNCH_HEAD(true, false, false, false, true);
     else
-      hipLaunchKernelGGL((image_icp_head_kernel<false, false, false, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s,
-                         descs, st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+      A3D_LAUNCH_HEAD(false, false, false, false, true);
     A3D_HIP_TRY(hipGetLastError());
     return A3D_OK;
   }
 #endif
   if (b->depth16 && level == 0 && b->short_div)
-    hipLaunchKernelGGL((image_icp_head_kernel<true, true, false, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs,
-                       st_in, st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    A3D_LAUNCH_HEAD(true, true, false, true, false);
   else if (b->depth16 && level == 0)
-    hipLaunchKernelGGL((image_icp_head_kernel<true, true>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
-                       st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    A3D_LAUNCH_HEAD(true, true, false, false, false);
   else if (b->zmask)
-    hipLaunchKernelGGL((image_icp_head_kernel<true, false>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
-                       st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    A3D_LAUNCH_HEAD(true, false, false, false, false);
   else
-    hipLaunchKernelGGL((image_icp_head_kernel<false, false>), dim3(b->tiles[level], count), dim3(256), 0, s, descs, st_in,
-                       st_out, b->gates[level], part_in, part_out, job_stride, prev);
+    A3D_LAUNCH_HEAD(false, false, false, false, false);
+#undef A3D_LAUNCH_HEAD
   A3D_HIP_TRY(hipGetLastError());
   return A3D_OK;
+}
+
+// The solve launch of a split level: launch number `seq` of the sequence finishes iteration seq - 1 (`prev`) once per
+// pair — state and partials read and written where the head of launch `seq` reads and writes them.
+a3d_status launch_solve_kernel(a3d_multiscale_batch* b, uint32_t seq, const HeadArgs& prev, uint32_t p0, uint32_t count,
+                               hipStream_t s) {
+  const uint32_t P = b->n_pairs;
+  const uint32_t job_stride = b->max_tiles * GN_PARTIAL;
+  return launch_job_solve_head(s, b->d_states + (size_t)(seq & 1u) * P + p0, b->d_states + (size_t)((seq + 1u) & 1u) * P + p0,
+                               b->d_partials + (size_t)((seq + 1u) & 1u) * b->partials_half + (size_t)p0 * job_stride,
+                               job_stride, prev, (int)count);
 }
 
 // (Re)derives tiling from h_descs and uploads the descriptors.
@@ -1701,6 +1721,9 @@ a3d_status batch_create(a3d_context* ctx, const a3d_icp_params* params, uint32_t
   *out = std::move(b);
   return A3D_OK;
 }
+
+// Level 0 of a batch on three stream groups runs split (batch_enqueue): +2.5 % on the headline, DESIGN.md §5.
+constexpr bool SOLVE_SPLIT_LEVEL0 = true;
 
 // Enqueues init -> levels (coarsest first) -> finish.  d_init: device Pose[P] or null (identity).
 a3d_status batch_enqueue(a3d_multiscale_batch* b, const Pose* d_init, uint32_t levels_to_run, float* d_matrices,
@@ -1830,18 +1853,35 @@ a3d_status batch_enqueue(a3d_multiscale_batch* b, const Pose* d_init, uint32_t l
     finished_in_kernel = plan.finish != 0;
   }
 #endif  // A3D_DIAGNOSTICS
+  // ---- which levels run split: one solve launch per iteration and stream group, then a pixel launch without a head
+  // (launch_solve_kernel).  Level 0 of a batch on three stream groups is short of issue slots, not of time between
+  // dependent launches: there the pair's 24 blocks no longer run the solve each.  Everywhere else the
+  // dependent chain binds and the head stays inside the launch: the coarser levels, fewer groups, the trace path, levels
+  // still being uploaded.  The diagnostics build's A3D_ICP_SOLVE_SPLIT=<level bitmask> forces any set of levels.
+  uint32_t split_mask = (SOLVE_SPLIT_LEVEL0 && S >= 3 && !d_trace && !b->level_ready[0]) ? 1u : 0u;
+  if (const char* env = A3D_DIAG_ENV("A3D_ICP_SOLVE_SPLIT")) split_mask = (uint32_t)strtoul(env, nullptr, 0);
   for (uint32_t l = first_per_iteration; l-- > 0;) {  // .rev(): coarsest level first (multiscale.rs:54-60)
     const a3d_icp_params& prm = b->params[l];
     profile_level = l;
     if (l < 16 && b->level_ready[l])  // the level's source arrays are still on their way (a3d_multiscale_align_host)
       for (uint32_t g = 0; g < S; ++g) A3D_HIP_TRY(hipStreamWaitEvent(g == 0 ? s : b->aux_streams[g - 1], b->level_ready[l], 0));
     if (head) {
+      const bool split_level = ((split_mask >> l) & 1u) != 0;
       for (uint64_t it = 0; it < prm.max_iterations; ++it) {
         for (uint32_t g = 0; g < S; ++g) {
           const uint32_t p0 = (uint32_t)((uint64_t)P * g / S), p1 = (uint32_t)((uint64_t)P * (g + 1) / S);
           hipStream_t gs = g == 0 ? s : b->aux_streams[g - 1];
+          if (split_level) {  // the solve once per pair, then the pixel launch without a head
+            A3D_TRY(profile_begin(gs));
+            A3D_TRY(launch_solve_kernel(b, seq, prev, p0, p1 - p0, gs));
+            A3D_TRY(profile_end(gs));
+            A3D_TRY(profile_begin(gs));
+            A3D_TRY(launch_head_kernel<true>(b, l, seq, prev, p0, p1 - p0, gs));
+            A3D_TRY(profile_end(gs));
+            continue;
+          }
           A3D_TRY(profile_begin(gs));
-          A3D_TRY(launch_head_kernel(b, l, seq, prev, p0, p1 - p0, gs));
+          A3D_TRY(launch_head_kernel<false>(b, l, seq, prev, p0, p1 - p0, gs));
           A3D_TRY(profile_end(gs));
         }
         prev.weight = prm.weight, prev.color_weight = prm.color_weight, prev.mode = SOLVE_IMAGE_ICP;
@@ -2122,7 +2162,13 @@ static a3d_status accumulate_pass(a3d_context* ctx, const a3d_icp_params* params
   if (st == A3D_OK && which == 0) {  // the per-iteration launch with nothing to finish at its head: partials in buffer 0
     HeadArgs none{};
     none.mode = SOLVE_NONE;
-    st = launch_head_kernel(b.get(), 0, 0, none, 0, 1, s);
+    const char* senv = A3D_DIAG_ENV("A3D_ICP_SOLVE_SPLIT");  // bit 0: the split form of the same pass (the same bits)
+    if (senv && (strtoul(senv, nullptr, 0) & 1u)) {
+      st = launch_solve_kernel(b.get(), 0, none, 0, 1, s);
+      if (st == A3D_OK) st = launch_head_kernel<true>(b.get(), 0, 0, none, 0, 1, s);
+    } else {
+      st = launch_head_kernel<false>(b.get(), 0, 0, none, 0, 1, s);
+    }
   }
 #ifdef A3D_DIAGNOSTICS
   if (st == A3D_OK && which == 1) {

@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(BLOCK)
   const uint32_t n_split = (1u << max_depth) - 1u;
   kd_stage_splits(split, n_split, lds_levels, kd_lds);
   const KdSplits sp{split, kd_lds, lds_levels};
-  head_advance(state_in, blockIdx.x == 0 ? state_out : nullptr, partials_in, head, 0, s_state, blockIdx.x == 0);
+  head_advance<BLOCK>(state_in, blockIdx.x == 0 ? state_out : nullptr, partials_in, head, 0, s_state, blockIdx.x == 0);
   float acc[GN_ACC];
 #pragma unroll
   for (int k = 0; k < GN_ACC; ++k) acc[k] = 0.0f;

@@ -38,7 +38,6 @@ __global__ void __launch_bounds__(BLOCK)
                               const float* __restrict__ partials_in, float* __restrict__ partials_out, HeadArgs head) {
   // head_advance picks the solving wave as (blockIdx.x + blockIdx.y) & 3 (A3D_HEAD_ROTATE) and sums the partials with
   // the block's first 256 threads
-  static_assert(BLOCK >= 256 && BLOCK % 64 == 0, "head_advance needs four waves");
   extern __shared__ __attribute__((aligned(16))) float kd_lds[];
   __shared__ uint32_t s_state[JOB_WORDS];
   const uint32_t job = blockIdx.y;
@@ -48,7 +47,7 @@ __global__ void __launch_bounds__(BLOCK)
   kd_stage_splits(d.split, n_split, lds_levels, kd_lds);
   const KdSplits sp{d.split, kd_lds, lds_levels};
   const size_t job_stride = (size_t)gridDim.x * GN_PARTIAL;
-  head_advance(state_in + job, blockIdx.x == 0 ? state_out + job : nullptr, partials_in + job * job_stride, head,
+  head_advance<BLOCK>(state_in + job, blockIdx.x == 0 ? state_out + job : nullptr, partials_in + job * job_stride, head,
                (int)job, s_state, blockIdx.x == 0);
   float acc[GN_ACC];
 #pragma unroll

@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(BLOCK)
                          const JobState* __restrict__ state_in, JobState* __restrict__ state_out, PclGates gates,
                          const float* __restrict__ partials_in, float* __restrict__ partials_out, HeadArgs head) {
   __shared__ uint32_t s_state[JOB_WORDS];
-  head_advance(state_in, blockIdx.x == 0 ? state_out : nullptr, partials_in, head, 0, s_state, blockIdx.x == 0);
+  head_advance<BLOCK>(state_in, blockIdx.x == 0 ? state_out : nullptr, partials_in, head, 0, s_state, blockIdx.x == 0);
   float acc[GN_ACC];
 #pragma unroll
   for (int k = 0; k < GN_ACC; ++k) acc[k] = 0.0f;
