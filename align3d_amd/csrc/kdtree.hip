@@ -8,6 +8,7 @@
 #include "icp_engine.hpp"
 #include "kdtree.hpp"
 #include "pcl_icp.hpp"
+#include "solo_icp.hpp"
 
 using namespace a3d;
 
@@ -246,16 +247,7 @@ struct a3d_pcl_icp {
   bool target_has_normals = false;
   uint32_t blocks = 0;  // block partials (= grid size of the iteration kernel)
   KdLaunch launch{};
-  void* d_block = nullptr;         // one device block (ctx_block_alloc) behind the five pointers below
-  size_t block_bytes = 0;
-  JobState* d_state = nullptr;     // two buffers: the head-solve form alternates between them
-  float* d_partials = nullptr;    // [2][blocks][GN_PARTIAL]
-  Pose* d_out_pose = nullptr;     // what job_finish_head leaves for the host (one allocation with d_out_status)
-  int32_t* d_out_status = nullptr;
-  unsigned* d_counter = nullptr;
-  double* d_readback = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket the iteration launches of the last align
-  float last_device_ms = 0.f;
+  SoloIcp solo;  // the working state of an align or accumulate (solo_icp.hpp), reserved with the object
 };
 
 extern "C" {
@@ -458,21 +450,10 @@ static a3d_status pcl_icp_new_impl(a3d_context* ctx, const a3d_icp_params* param
   // is fixed per Icp object (sized for a source cloud as large as the target) so the partials buffer is too
   icp->launch = kd_launch_config(t, 1ull << 31, "A3D_PCL", 1024, 15, 1);
   icp->blocks = icp->launch.blocks;
-  if (st == A3D_OK) {  // the object's device state: one block of the context's (no hipMalloc once a previous Icp was freed)
-    const size_t state_b = pad256(2 * sizeof(JobState)), part_b = pad256(2 * (size_t)icp->blocks * GN_PARTIAL * sizeof(float)),
-                 pose_b = 256, read_b = pad256(GN_PARTIAL * sizeof(double)), count_b = 256;
-    char* blk = nullptr;
-    st = ctx_block_alloc(ctx, state_b + part_b + pose_b + read_b + count_b, (void**)&blk, &icp->block_bytes);
-    if (st == A3D_OK) {
-      icp->d_block = blk;
-      icp->d_state = (JobState*)blk;
-      icp->d_partials = (float*)(blk + state_b);
-      icp->d_out_pose = (Pose*)(blk + state_b + part_b);
-      icp->d_readback = (double*)(blk + state_b + part_b + pose_b);
-      icp->d_counter = (unsigned*)(blk + state_b + part_b + pose_b + read_b);
-      if (hipMemsetAsync(icp->d_counter, 0, sizeof(unsigned), ctx->stream) != hipSuccess) st = A3D_HIP_ERROR;
-    }
-  }
+  // the object's device state: one block of the context's (no hipMalloc once a previous Icp was freed)
+  if (st == A3D_OK) st = solo_icp_reserve(ctx, &icp->solo, icp->blocks);
+  // (the ticket of the diagnostics form; it leaves the counter at zero behind every launch)
+  if (st == A3D_OK && hipMemsetAsync(icp->solo.counter, 0, sizeof(unsigned), ctx->stream) != hipSuccess) st = A3D_HIP_ERROR;
   if (st != A3D_OK) {
     set_error("a3d_pcl_icp_new: HIP failure: %s", hipGetErrorString(hipGetLastError()));
     a3d_pcl_icp_free(icp.release());
@@ -517,12 +498,17 @@ static a3d_status pcl_upload_source(a3d_pcl_icp* icp, const a3d_point_cloud_view
   return A3D_OK;
 }
 
+// A source that could not be staged: what the call put on the stream is waited for, as behind every other outcome.
+static a3d_status pcl_upload_failed(a3d_pcl_icp* icp, a3d_status st, const char* entry_name) {
+  hipStreamSynchronize(icp->ctx->stream);
+  if (st == A3D_HIP_ERROR) set_error("%s: HIP failure: %s", entry_name, hipGetErrorString(hipGetLastError()));
+  return st;
+}
+
 #ifdef A3D_DIAGNOSTICS  // the last-block (ticket) form: cross-check of the head-solve form
 static a3d_status pcl_launch_pass(a3d_pcl_icp* icp, const float* d_pts, const float* d_nrm, uint32_t m,
                                   const SolveArgs& solve) {
-  PclGates g;
-  g.max_distance_sqr = icp->params.max_distance * icp->params.max_distance;
-  g.dot_reject_max = acos_gate_threshold(icp->params.max_normal_angle, /*strict=*/true);
+  const PclGates g = pcl_gates(icp->params);
   a3d_kdtree* t = icp->tree;
   const KdLaunch& L = icp->launch;
 #define A3D_PCL_LAUNCH(B)                                                                                      \
@@ -530,7 +516,7 @@ static a3d_status pcl_launch_pass(a3d_pcl_icp* icp, const float* d_pts, const fl
     A3D_TRY(kd_allow_big_lds(pcl_icp_kernel<B>, L.lds_bytes));                                                 \
     hipLaunchKernelGGL(pcl_icp_kernel<B>, dim3(L.blocks), dim3(B), L.lds_bytes, icp->ctx->stream, t->d_split,  \
                        t->d_leaves, t->d_leaf_normals, t->n, t->max_depth, L.lds_levels, d_pts, d_nrm, m,      \
-                       icp->d_state, g, icp->d_partials, icp->d_counter, solve);                               \
+                       icp->solo.state, g, icp->solo.partials, icp->solo.counter, solve);                      \
   }
   if (L.block == 256) A3D_PCL_LAUNCH(256) else if (L.block == 512) A3D_PCL_LAUNCH(512) else A3D_PCL_LAUNCH(1024)
 #undef A3D_PCL_LAUNCH
@@ -538,92 +524,69 @@ static a3d_status pcl_launch_pass(a3d_pcl_icp* icp, const float* d_pts, const fl
   return A3D_OK;
 }
 
+// A3D_ICP_HANDOFF=ticket: Icp::align's loop with the iteration finished by the last block of its own launch, in place.
+static a3d_status pcl_icp_align_ticket(a3d_pcl_icp* icp, const float* d_pts, const float* d_nrm, uint32_t m, a3d_pose* out_pose) {
+  SoloIcp& b = icp->solo;
+  hipStream_t s = icp->ctx->stream;
+  if (!b.ev1) {
+    if (!b.ev0) A3D_HIP_TRY(hipEventCreate(&b.ev0));
+    A3D_HIP_TRY(hipEventCreate(&b.ev1));
+  }
+  hipEventRecord(b.ev0, s);
+  a3d_status st = launch_job_init(s, b.state, nullptr, 1);
+  for (uint64_t it = 0; st == A3D_OK && it < icp->params.max_iterations; ++it) {
+    SolveArgs sa{};
+    sa.weight = icp->params.weight, sa.color_weight = 0.0f;
+    sa.mode = SOLVE_PCL_ICP;
+    sa.first_in_level = it == 0, sa.last_in_level = it + 1 == icp->params.max_iterations;
+    st = pcl_launch_pass(icp, d_pts, d_nrm, m, sa);
+  }
+  if (st == A3D_OK) hipEventRecord(b.ev1, s);
+  JobState h;
+  if (st == A3D_OK && hipMemcpyAsync(&h, b.state, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) st = A3D_HIP_ERROR;
+  if (hipStreamSynchronize(s) != hipSuccess && st == A3D_OK) st = A3D_HIP_ERROR;
+  if (st == A3D_OK) hipEventElapsedTime(&b.last_device_ms, b.ev0, b.ev1);
+  if (st == A3D_HIP_ERROR) set_error("a3d_pcl_icp_align: HIP failure: %s", hipGetErrorString(hipGetLastError()));
+  if (st != A3D_OK) return st;
+  pose_to_c(h.pose, out_pose);
+  if (h.status == A3D_SOLVE_FAILED) set_error("GaussNewton::solve() returned None (count == 0 or Cholesky failed)");
+  return (a3d_status)h.status;
+}
 #endif  // A3D_DIAGNOSTICS
 
-static a3d_status pcl_launch_head_pass(a3d_pcl_icp* icp, const float* d_pts, const float* d_nrm, uint32_t m, uint32_t seq,
-                                       const HeadArgs& head) {
-  PclGates g;
-  g.max_distance_sqr = icp->params.max_distance * icp->params.max_distance;
-  g.dot_reject_max = acos_gate_threshold(icp->params.max_normal_angle, /*strict=*/true);
-  a3d_kdtree* t = icp->tree;
-  const KdLaunch& L = icp->launch;
-  const size_t half = (size_t)icp->blocks * GN_PARTIAL;
-  const JobState* st_in = icp->d_state + (seq & 1u);
-  JobState* st_out = icp->d_state + ((seq + 1u) & 1u);
-  const float* part_in = icp->d_partials + (size_t)((seq + 1u) & 1u) * half;  // written by launch seq - 1
-  float* part_out = icp->d_partials + (size_t)(seq & 1u) * half;
+// One pass of the head-solve iteration kernel over the staged source.
+static SoloLaunch pcl_pass_launcher(a3d_pcl_icp* icp, const float* d_pts, const float* d_nrm, uint32_t m) {
+  const PclGates g = pcl_gates(icp->params);
+  return [icp, d_pts, d_nrm, m, g](const SoloPass& p) -> a3d_status {
+    a3d_kdtree* t = icp->tree;
+    const KdLaunch& L = icp->launch;
 #define A3D_PCL_LAUNCH(B)                                                                                          \
   {                                                                                                                \
     A3D_TRY(kd_allow_big_lds(pcl_icp_head_kernel<B>, L.lds_bytes));                                                \
     hipLaunchKernelGGL(pcl_icp_head_kernel<B>, dim3(L.blocks), dim3(B), L.lds_bytes, icp->ctx->stream, t->d_split, \
-                       t->d_leaves, t->d_leaf_normals, t->n, t->max_depth, L.lds_levels, d_pts, d_nrm, m, st_in,   \
-                       st_out, g, part_in, part_out, head);                                                        \
+                       t->d_leaves, t->d_leaf_normals, t->n, t->max_depth, L.lds_levels, d_pts, d_nrm, m,          \
+                       p.state_in, p.state_out, g, p.partials_in, p.partials_out, p.head);                         \
   }
-  if (L.block == 256) A3D_PCL_LAUNCH(256) else if (L.block == 512) A3D_PCL_LAUNCH(512) else A3D_PCL_LAUNCH(1024)
+    if (L.block == 256) A3D_PCL_LAUNCH(256) else if (L.block == 512) A3D_PCL_LAUNCH(512) else A3D_PCL_LAUNCH(1024)
 #undef A3D_PCL_LAUNCH
-  A3D_HIP_TRY(hipGetLastError());
-  return A3D_OK;
+    A3D_HIP_TRY(hipGetLastError());
+    return A3D_OK;
+  };
 }
 
 static a3d_status pcl_icp_align_impl(a3d_pcl_icp* icp, const a3d_point_cloud_view* source, bool on_device, a3d_pose* out_pose) {
   A3D_REQUIRE(icp && source && out_pose, A3D_INVALID_PARAMETER, "null argument");
   float *d_pts = nullptr, *d_nrm = nullptr;
-  a3d_status st = pcl_upload_source(icp, source, on_device, &d_pts, &d_nrm);
-  hipStream_t s = icp->ctx->stream;
+  const a3d_status st = pcl_upload_source(icp, source, on_device, &d_pts, &d_nrm);
+  if (st != A3D_OK) return pcl_upload_failed(icp, st, "a3d_pcl_icp_align");
   const uint32_t m = (uint32_t)source->len;
-  // Icp::align starts from Transform::eye(): initial_transform is ignored (pcl_icp.rs:59)
-  if (!icp->ev0) {
-    hipEventCreate(&icp->ev0);
-    hipEventCreate(&icp->ev1);
-  }
-  if (st == A3D_OK) hipEventRecord(icp->ev0, s);
-  if (st == A3D_OK) st = launch_job_init(s, icp->d_state, nullptr, 1);
-  const char* handoff = A3D_DIAG_ENV("A3D_ICP_HANDOFF");
-  const bool head_form = !(handoff && !strcmp(handoff, "ticket"));  // diagnostics build: the last-block form
-  icp->d_out_status = (int32_t*)((char*)icp->d_out_pose + 128);
-  JobState h;
-  Pose h_pose{};
-  int32_t h_status = A3D_OK;
-  if (head_form) {
-    HeadArgs prev{};
-    prev.mode = SOLVE_NONE;
-    uint32_t seq = 0;
-    for (uint64_t it = 0; st == A3D_OK && it < icp->params.max_iterations; ++it, ++seq) {
-      st = pcl_launch_head_pass(icp, d_pts, d_nrm, m, seq, prev);
-      prev.weight = icp->params.weight, prev.color_weight = 0.0f, prev.mode = SOLVE_PCL_ICP;
-      prev.tiles = icp->blocks;
-      prev.first_in_level = it == 0, prev.last_in_level = it + 1 == icp->params.max_iterations;
-    }
-    if (st == A3D_OK)  // the last iteration is still pending: the finish kernel applies it
-      st = launch_job_finish_head(s, icp->d_state + (seq & 1u),
-                                  icp->d_partials + (size_t)((seq + 1u) & 1u) * icp->blocks * GN_PARTIAL, 0, prev,
-                                  icp->d_out_pose, icp->d_out_status, nullptr, 1);
-    if (st == A3D_OK) hipEventRecord(icp->ev1, s);
-    if (st == A3D_OK && (hipMemcpyAsync(&h_pose, icp->d_out_pose, sizeof(Pose), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                         hipMemcpyAsync(&h_status, icp->d_out_status, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess))
-      st = A3D_HIP_ERROR;
-  } else {
 #ifdef A3D_DIAGNOSTICS
-    for (uint64_t it = 0; st == A3D_OK && it < icp->params.max_iterations; ++it) {
-      SolveArgs sa{};
-      sa.weight = icp->params.weight, sa.color_weight = 0.0f;
-      sa.mode = SOLVE_PCL_ICP;
-      sa.first_in_level = it == 0, sa.last_in_level = it + 1 == icp->params.max_iterations;
-      st = pcl_launch_pass(icp, d_pts, d_nrm, m, sa);
-    }
-    if (st == A3D_OK) hipEventRecord(icp->ev1, s);
-    if (st == A3D_OK && hipMemcpyAsync(&h, icp->d_state, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess)
-      st = A3D_HIP_ERROR;
+  const char* handoff = A3D_DIAG_ENV("A3D_ICP_HANDOFF");
+  if (handoff && !strcmp(handoff, "ticket")) return pcl_icp_align_ticket(icp, d_pts, d_nrm, m, out_pose);
 #endif
-  }
-  if (hipStreamSynchronize(s) != hipSuccess && st == A3D_OK) st = A3D_HIP_ERROR;
-  if (!head_form) h_pose = h.pose, h_status = h.status;
-  if (st == A3D_OK) hipEventElapsedTime(&icp->last_device_ms, icp->ev0, icp->ev1);
-  if (st == A3D_HIP_ERROR) set_error("a3d_pcl_icp_align: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-  if (st != A3D_OK) return st;
-  pose_to_c(h_pose, out_pose);
-  if (h_status == A3D_SOLVE_FAILED) set_error("GaussNewton::solve() returned None (count == 0 or Cholesky failed)");
-  return (a3d_status)h_status;
+  // Icp::align starts from Transform::eye(): initial_transform is ignored (pcl_icp.rs:59)
+  return solo_icp_align(icp->ctx, &icp->solo, icp->params, nullptr, icp->blocks, "a3d_pcl_icp_align",
+                        pcl_pass_launcher(icp, d_pts, d_nrm, m), out_pose);
 }
 
 a3d_status a3d_pcl_icp_align(a3d_pcl_icp* icp, const a3d_point_cloud_view* source, a3d_pose* out_pose) {
@@ -638,34 +601,17 @@ a3d_status a3d_pcl_icp_accumulate(a3d_pcl_icp* icp, const a3d_point_cloud_view* 
                                   a3d_gn_state* out_state) {
   A3D_REQUIRE(icp && source && out_state, A3D_INVALID_PARAMETER, "null argument");
   float *d_pts = nullptr, *d_nrm = nullptr;
-  a3d_status st = pcl_upload_source(icp, source, /*on_device=*/false, &d_pts, &d_nrm);
-  hipStream_t s = icp->ctx->stream;
-  Pose h_pose = pose ? pose_from_c(pose) : pose_eye();
-  Pose* d_pose = nullptr;
-  double sums[GN_PARTIAL];
-  if (st == A3D_OK && (hipMalloc((void**)&d_pose, sizeof(Pose)) != hipSuccess ||
-                       hipMemcpyAsync(d_pose, &h_pose, sizeof(Pose), hipMemcpyHostToDevice, s) != hipSuccess))
-    st = A3D_HIP_ERROR;
-  if (st == A3D_OK) st = launch_job_init(s, icp->d_state, d_pose, 1);
-  HeadArgs none{};  // the per-iteration launch with nothing to finish at its head: partials in buffer 0
-  none.mode = SOLVE_NONE;
-  if (st == A3D_OK) st = pcl_launch_head_pass(icp, d_pts, d_nrm, (uint32_t)source->len, 0, none);
-  if (st == A3D_OK) st = launch_gn_readback(s, icp->d_partials, (int)icp->blocks, icp->d_readback);
-  if (st == A3D_OK && hipMemcpyAsync(sums, icp->d_readback, sizeof(sums), hipMemcpyDeviceToHost, s) != hipSuccess)
-    st = A3D_HIP_ERROR;
-  if (hipStreamSynchronize(s) != hipSuccess && st == A3D_OK) st = A3D_HIP_ERROR;
-  hipFree(d_pose);
-  if (st == A3D_HIP_ERROR) set_error("a3d_pcl_icp_accumulate: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-  if (st != A3D_OK) return st;
-  gn_states_from_sums(sums, out_state, nullptr);
-  return A3D_OK;
+  const a3d_status st = pcl_upload_source(icp, source, /*on_device=*/false, &d_pts, &d_nrm);
+  if (st != A3D_OK) return pcl_upload_failed(icp, st, "a3d_pcl_icp_accumulate");
+  return solo_icp_accumulate(icp->ctx, &icp->solo, pose ? pose_from_c(pose) : pose_eye(), icp->blocks,
+                             "a3d_pcl_icp_accumulate", pcl_pass_launcher(icp, d_pts, d_nrm, (uint32_t)source->len), out_state);
 }
 
 // Instrumentation: device time of the iteration launches of the most recent a3d_pcl_icp_align
 // (source already uploaded), between hipEvents on the context stream.
 a3d_status a3d_pcl_icp_last_device_ms(a3d_pcl_icp* icp, float* out_ms) {
   A3D_REQUIRE(icp && out_ms, A3D_INVALID_PARAMETER, "null argument");
-  *out_ms = icp->last_device_ms;
+  *out_ms = icp->solo.last_device_ms;
   return A3D_OK;
 }
 
@@ -673,9 +619,7 @@ a3d_status a3d_pcl_icp_free(a3d_pcl_icp* icp) {
   if (!icp) return A3D_OK;
   hipStreamSynchronize(icp->ctx->stream);
   a3d_kdtree_free(icp->tree);
-  ctx_block_release(icp->ctx, icp->d_block, icp->block_bytes);
-  if (icp->ev0) hipEventDestroy(icp->ev0);
-  if (icp->ev1) hipEventDestroy(icp->ev1);
+  solo_icp_release(icp->ctx, &icp->solo);
   delete icp;
   return A3D_OK;
 }

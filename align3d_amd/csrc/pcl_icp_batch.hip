@@ -305,9 +305,7 @@ a3d_status a3d_pcl_icp_batch_align_device(a3d_pcl_icp_batch* b, const a3d_point_
   }
   const uint32_t bpp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b->bpp_cap, (max_m + b->block - 1) / b->block));
   const size_t lds_bytes = (size_t)std::min<uint64_t>((1ull << b->lds_levels) - 1, (1ull << b->max_tree_depth) - 1) * sizeof(float);
-  PclGates g;
-  g.max_distance_sqr = b->params.max_distance * b->params.max_distance;
-  g.dot_reject_max = acos_gate_threshold(b->params.max_normal_angle, /*strict=*/true);
+  const PclGates g = pcl_gates(b->params);
   if (b->block == 256) A3D_TRY(allow_lds<256>(lds_bytes));
   else if (b->block == 512) A3D_TRY(allow_lds<512>(lds_bytes));
   else A3D_TRY(allow_lds<1024>(lds_bytes));

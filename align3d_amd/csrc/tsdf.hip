@@ -204,7 +204,7 @@ a3d_status a3d_tsdf_volume_new(a3d_context* ctx, uint64_t nx, uint64_t ny, uint6
 
 void a3d_tsdf_volume_free(a3d_tsdf_volume* volume) {
   if (!volume) return;
-  tsdf_icp_release(volume);
+  solo_icp_release(volume->ctx, &volume->icp);
   if (volume->block) ctx_block_release(volume->ctx, volume->block, volume->block_bytes);
   delete volume;
 }

@@ -4,6 +4,7 @@
 // and the field query for its distance and direction.
 #pragma once
 #include "cloud_batch.hpp"
+#include "solo_icp.hpp"
 
 struct a3d_tsdf_volume {
   a3d_context* ctx = nullptr;
@@ -14,19 +15,12 @@ struct a3d_tsdf_volume {
   size_t block_bytes = 0, used_bytes = 0;
   float2* records = nullptr;   // [nz][ny][nx] {D, W}
   uint32_t* colors = nullptr;  // [nz][ny][nx] r | g << 8 | b << 16, or null
-  // the working buffers of the point-to-SDF ICP (tsdf_icp.hip): one block of the context's, taken by the first align or
-  // accumulate and released with the volume
-  void* icp_block = nullptr;
-  size_t icp_block_bytes = 0;
-  uint32_t icp_blocks = 0;  // block partials it has room for
-  hipEvent_t icp_ev0 = nullptr, icp_ev1 = nullptr;  // bracket the iteration launches of the last align
-  float icp_last_device_ms = 0.f;
+  // the working state of the point-to-SDF ICP (tsdf_icp.hip): taken by the first align or accumulate and released with
+  // the volume (solo_icp_release)
+  a3d::SoloIcp icp;
 };
 
 namespace a3d {
-
-// Releases the ICP working buffers of a volume that is being freed (tsdf_icp.hip).
-void tsdf_icp_release(a3d_tsdf_volume* volume);
 
 constexpr uint64_t TS_MAX_WEIGHT = 1ull << 24;  // integers up to here are exact in f32
 

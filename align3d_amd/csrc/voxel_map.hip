@@ -1193,7 +1193,7 @@ a3d_status a3d_voxel_map_clear(a3d_voxel_map* map) {
 void a3d_voxel_map_free(a3d_voxel_map* map) {
   if (!map) return;
   if (map->block) ctx_block_release(map->ctx, map->block, map->block_bytes);
-  voxel_map_icp_release(map);
+  solo_icp_release(map->ctx, &map->icp);
   delete map;
 }
 

@@ -1,6 +1,7 @@
 // The persistent voxel map as its two translation units see it: voxel_map.hip (insert, extract, retain: everything
 // that changes the table) and voxel_map_icp.hip (nearest and frame-to-map ICP: the table is only read).
 #pragma once
+#include "solo_icp.hpp"
 #include "voxel_grid.hpp"
 
 struct a3d_voxel_map {
@@ -28,16 +29,7 @@ struct a3d_voxel_map {
   uint32_t* epoch = nullptr;            // [slots]
   uint32_t epoch_no = 0;                // of the last insert call that launched
   uint64_t cells = 0, total = 0, dropped_total = 0, growths = 0;
-  // the working buffers of the frame-to-map ICP (voxel_map_icp.hip): one block of the context's, taken by the first
-  // align or accumulate and released with the map
-  void* icp_block = nullptr;
-  size_t icp_block_bytes = 0;
-  uint32_t icp_blocks = 0;  // block partials it has room for
-  hipEvent_t icp_ev0 = nullptr, icp_ev1 = nullptr;  // bracket the iteration launches of the last align
-  float icp_last_device_ms = 0.f;
+  // the working state of the frame-to-map ICP (voxel_map_icp.hip): taken by the first align or accumulate and released
+  // with the map (solo_icp_release)
+  a3d::SoloIcp icp;
 };
-
-namespace a3d {
-// Releases the ICP working buffers of a map that is being freed (voxel_map_icp.hip).
-void voxel_map_icp_release(a3d_voxel_map* map);
-}  // namespace a3d

@@ -16,11 +16,10 @@
 // in 32 bits and the winner's row is fetched again behind the walk: the ICP kernel then fits the 128 registers of a
 // 1024-thread block but for a dozen spilled words.
 //
-// voxel_map_icp_head_kernel is pcl_icp_head_kernel (kdtree.hip) with that walk in place of the kd-tree descent and no
-// split table to stage: head_advance finishes the previous iteration, the point loop runs under the pose it leaves, and
-// the block stores one partial.  The tail of the point loop behind the association is pcl_point_tail (pcl_icp.hpp), the
-// very function the kd-tree loops call.  Launch geometry follows the source length and the device alone, so an
-// iteration's sums depend on the map's contents and never on its slot count.
+// The ICP's iteration kernel is solo_icp_head_kernel (pcl_icp.hpp) over MapTarget, whose match() is that walk and the
+// gather of the winner's row; the working buffers and the launch sequence of a call are SoloIcp's (solo_icp.hpp).  What
+// is left here: the refusals, the empty map, and the launch of one pass.  Launch geometry follows the source length and
+// the device alone, so an iteration's sums depend on the map's contents and never on its slot count.
 #include <cmath>
 #include <vector>
 
@@ -131,38 +130,18 @@ __global__ void __launch_bounds__(VQ_THREADS)
   }
 }
 
-// One iteration of the frame-to-map ICP: pcl_icp_head_kernel's shape (kdtree.hip), the map in place of the tree.
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
-    voxel_map_icp_head_kernel(MapView map, VoxelGrid grid, const float* __restrict__ src_points,
-                              const float* __restrict__ src_normals, uint32_t m, const JobState* __restrict__ state_in,
-                              JobState* __restrict__ state_out, PclGates gates, const float* __restrict__ partials_in,
-                              float* __restrict__ partials_out, HeadArgs head) {
-  __shared__ uint32_t s_state[JOB_WORDS];
-  head_advance<BLOCK>(state_in, blockIdx.x == 0 ? state_out : nullptr, partials_in, head, 0, s_state, blockIdx.x == 0);
-  float acc[GN_ACC];
-#pragma unroll
-  for (int k = 0; k < GN_ACC; ++k) acc[k] = 0.0f;
-  if ((int)s_state[15] == A3D_OK) {  // a failed job stays frozen
-    const float* f = (const float*)s_state;
-    const Pose T{{f[0], f[1], f[2]}, {f[3], f[4], f[5], f[6]}};
-    const uint32_t stride = gridDim.x * BLOCK;  // (m < 2^31, stride = blocks <= CUs times 1024: the index cannot wrap)
-#pragma unroll 1
-    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < m; i += stride) {
-      const f32x3 pv = *(const f32x3_u*)(src_points + 3 * (size_t)i), nv = *(const f32x3_u*)(src_normals + 3 * (size_t)i);
-      const V3 p = transform_vector(T, V3{pv.x, pv.y, pv.z});
-      const VmMatch win = vm_associate(map, grid, p);
-      // the winner's row and its normal: one 12-byte gather each (slot 0 when nothing was found)
-      const f32x3 tp = *(const f32x3_u*)(map.points + 3 * (size_t)win.slot), tn = *(const f32x3_u*)(map.normals + 3 * (size_t)win.slot);
-      const V3 sn = transform_normal(T, V3{nv.x, nv.y, nv.z});
-      pcl_point_tail(win.word != VM_NONE_WORD, p, sn, V3{tp.x, tp.y, tp.z}, V3{tn.x, tn.y, tn.z},
-                     __uint_as_float((uint32_t)(win.word >> 32)), gates, acc);
-    }
+// The map as solo_icp_head_kernel's target (pcl_icp.hpp): the map in place of the tree.
+struct MapTarget {
+  MapView map;
+  VoxelGrid grid;
+  __device__ __forceinline__ PointMatch match(const V3& p) const {
+    const VmMatch win = vm_associate(map, grid, p);
+    // the winner's row and its normal: one 12-byte gather each (slot 0 when nothing was found)
+    const f32x3 tp = *(const f32x3_u*)(map.points + 3 * (size_t)win.slot), tn = *(const f32x3_u*)(map.normals + 3 * (size_t)win.slot);
+    return PointMatch{win.word != VM_NONE_WORD, V3{tp.x, tp.y, tp.z}, V3{tn.x, tn.y, tn.z},
+                      __uint_as_float((uint32_t)(win.word >> 32))};
   }
-  float* out = partials_out + (size_t)blockIdx.x * GN_PARTIAL;
-  block_reduce_store<GN_ACC, false, BLOCK / 64>(acc, out);
-  if (threadIdx.x >= GN_ACC && threadIdx.x < GN_PARTIAL) out[threadIdx.x] = 0.0f;  // no colour term
-}
+};
 
 // Slot indices are 32-bit in these kernels (registers): a table of more than 2^32 slots, over 120 GiB, is refused.
 a3d_status check_slots(const a3d_voxel_map* m) {
@@ -174,59 +153,28 @@ MapView view_of(const a3d_voxel_map* m) {
   return MapView{m->table, m->points, m->normals, (uint32_t)(m->slots - 1)};
 }
 
-// The map's ICP working buffers inside its one block: two states | two partial sets | out pose (status 128 bytes
-// behind it) | the f64 readback | the pose an align starts from.
-struct IcpBuffers {
-  JobState* state;
-  float* partials;  // [2][blocks][GN_PARTIAL]
-  Pose* out_pose;
-  int32_t* out_status;
-  double* readback;
-  Pose* start_pose;
-};
-
-a3d_status icp_buffers(a3d_voxel_map* map, IcpBuffers* out) {
-  const uint32_t blocks = (uint32_t)std::max(1, map->ctx->num_cus);
-  const size_t state_b = pad256(2 * sizeof(JobState)), part_b = pad256(2 * (size_t)blocks * GN_PARTIAL * sizeof(float)),
-               pose_b = 256, read_b = pad256(GN_PARTIAL * sizeof(double));
-  if (!map->icp_block) {
-    A3D_TRY(ctx_block_alloc(map->ctx, state_b + part_b + pose_b + read_b + pose_b, &map->icp_block, &map->icp_block_bytes));
-    map->icp_blocks = blocks;
-  }
-  char* blk = (char*)map->icp_block;
-  out->state = (JobState*)blk;
-  out->partials = (float*)(blk + state_b);
-  out->out_pose = (Pose*)(blk + state_b + part_b);
-  out->out_status = (int32_t*)(blk + state_b + part_b + 128);
-  out->readback = (double*)(blk + state_b + part_b + pose_b);
-  out->start_pose = (Pose*)(blk + state_b + part_b + pose_b + read_b);
-  return A3D_OK;
-}
-
 // Blocks of an iteration launch: the source length and the device alone decide (never the table).
 uint32_t icp_grid(const a3d_voxel_map* map, uint32_t m) {
-  return std::max(1u, std::min((m + VI_BLOCK - 1) / VI_BLOCK, map->icp_blocks));
+  return std::max(1u, std::min((m + VI_BLOCK - 1) / VI_BLOCK, map->icp.capacity));
 }
 
-PclGates gates_of(const a3d_icp_params* params) {
-  PclGates g;
-  g.max_distance_sqr = params->max_distance * params->max_distance;
-  g.dot_reject_max = acos_gate_threshold(params->max_normal_angle, /*strict=*/true);
-  return g;
+// The map's working buffers, taken by its first align or accumulate: room for a block partial per CU.
+a3d_status icp_reserve(a3d_voxel_map* map) {
+  A3D_HIP_TRY(hipSetDevice(map->ctx->device));
+  return solo_icp_reserve(map->ctx, &map->icp, (uint32_t)std::max(1, map->ctx->num_cus));
 }
 
-a3d_status launch_head_pass(const a3d_voxel_map* map, const IcpBuffers& b, const PclGates& g, const a3d_point_cloud_view* src,
-                            uint32_t seq, const HeadArgs& head) {
-  const uint32_t m = (uint32_t)src->len, blocks = icp_grid(map, m);
-  const size_t half = (size_t)map->icp_blocks * GN_PARTIAL;
-  const JobState* st_in = b.state + (seq & 1u);
-  JobState* st_out = b.state + ((seq + 1u) & 1u);
-  const float* part_in = b.partials + (size_t)((seq + 1u) & 1u) * half;  // written by launch seq - 1
-  float* part_out = b.partials + (size_t)(seq & 1u) * half;
-  hipLaunchKernelGGL(voxel_map_icp_head_kernel<VI_BLOCK>, dim3(blocks), dim3(VI_BLOCK), 0, map->ctx->stream, view_of(map),
-                     map->grid, src->points, src->normals, m, st_in, st_out, g, part_in, part_out, head);
-  A3D_HIP_TRY(hipGetLastError());
-  return A3D_OK;
+// One pass of the iteration kernel over `src`.
+SoloLaunch pass_launcher(const a3d_voxel_map* map, const a3d_icp_params* params, const a3d_point_cloud_view* src) {
+  const PclGates g = pcl_gates(*params);
+  return [map, src, g](const SoloPass& p) -> a3d_status {
+    const uint32_t m = (uint32_t)src->len;
+    hipLaunchKernelGGL((solo_icp_head_kernel<VI_BLOCK, MapTarget>), dim3(icp_grid(map, m)), dim3(VI_BLOCK), 0,
+                       map->ctx->stream, MapTarget{view_of(map), map->grid}, src->points, src->normals, m, p.state_in,
+                       p.state_out, g, p.partials_in, p.partials_out, p.head);
+    A3D_HIP_TRY(hipGetLastError());
+    return A3D_OK;
+  };
 }
 
 // The refusals of align and accumulate, decided before the context is touched.
@@ -241,15 +189,6 @@ a3d_status check_icp_call(const a3d_voxel_map* map, const a3d_icp_params* params
 }
 
 }  // namespace
-
-namespace a3d {
-void voxel_map_icp_release(a3d_voxel_map* map) {
-  if (map->icp_block) ctx_block_release(map->ctx, map->icp_block, map->icp_block_bytes);
-  if (map->icp_ev0) hipEventDestroy(map->icp_ev0);
-  if (map->icp_ev1) hipEventDestroy(map->icp_ev1);
-  map->icp_block = nullptr, map->icp_ev0 = map->icp_ev1 = nullptr;
-}
-}  // namespace a3d
 
 extern "C" {
 
@@ -293,91 +232,34 @@ a3d_status a3d_voxel_map_icp_align_device(a3d_voxel_map* map, const a3d_icp_para
   const Pose start = initial_host ? pose_from_c(initial_host) : pose_eye();
   if (!map->block) {  // no table yet: no point finds a row, as on a cleared map; the pose stays where it started
     pose_to_c(start, out_pose);
-    map->icp_last_device_ms = 0.f;
+    map->icp.last_device_ms = 0.f;
     if (params->max_iterations == 0) return A3D_OK;
     set_error("GaussNewton::solve() returned None (count == 0 or Cholesky failed)");
     return A3D_SOLVE_FAILED;
   }
-  a3d_context* ctx = map->ctx;
-  A3D_HIP_TRY(hipSetDevice(ctx->device));
-  IcpBuffers b;
-  A3D_TRY(icp_buffers(map, &b));
-  if (!map->icp_ev1) {  // (both or neither: ev0 alone is a failed attempt that is taken up again)
-    if (!map->icp_ev0) A3D_HIP_TRY(hipEventCreate(&map->icp_ev0));
-    A3D_HIP_TRY(hipEventCreate(&map->icp_ev1));
-  }
-  hipStream_t s = ctx->stream;
-  const PclGates g = gates_of(params);
-  a3d_status st = A3D_OK;
-  if (hipMemcpyAsync(b.start_pose, &start, sizeof(Pose), hipMemcpyHostToDevice, s) != hipSuccess) st = A3D_HIP_ERROR;
-  if (st == A3D_OK) hipEventRecord(map->icp_ev0, s);
-  if (st == A3D_OK) st = launch_job_init(s, b.state, b.start_pose, 1);
-  // Icp::align's loop (pcl_icp.rs:59-106) in the head-solve form: launch k finishes iteration k - 1
-  HeadArgs prev{};
-  prev.mode = SOLVE_NONE;
-  uint32_t seq = 0;
-  const uint32_t blocks = icp_grid(map, (uint32_t)d_source->len);
-  for (uint64_t it = 0; st == A3D_OK && it < params->max_iterations; ++it, ++seq) {
-    st = launch_head_pass(map, b, g, d_source, seq, prev);
-    prev.weight = params->weight, prev.color_weight = 0.0f, prev.mode = SOLVE_PCL_ICP;
-    prev.tiles = blocks;
-    prev.first_in_level = it == 0, prev.last_in_level = it + 1 == params->max_iterations;
-  }
-  if (st == A3D_OK)  // the last iteration is still pending: the finish kernel applies it
-    st = launch_job_finish_head(s, b.state + (seq & 1u),
-                                b.partials + (size_t)((seq + 1u) & 1u) * map->icp_blocks * GN_PARTIAL, 0, prev, b.out_pose,
-                                b.out_status, nullptr, 1);
-  if (st == A3D_OK) hipEventRecord(map->icp_ev1, s);
-  Pose h_pose{};
-  int32_t h_status = A3D_OK;
-  if (st == A3D_OK && (hipMemcpyAsync(&h_pose, b.out_pose, sizeof(Pose), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                       hipMemcpyAsync(&h_status, b.out_status, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess))
-    st = A3D_HIP_ERROR;
-  // host-synchronous, the one wait of the call
-  if (hipStreamSynchronize(s) != hipSuccess && st == A3D_OK) st = A3D_HIP_ERROR;
-  if (st == A3D_OK) hipEventElapsedTime(&map->icp_last_device_ms, map->icp_ev0, map->icp_ev1);
-  if (st == A3D_HIP_ERROR) set_error("a3d_voxel_map_icp_align_device: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-  if (st != A3D_OK) return st;
-  pose_to_c(h_pose, out_pose);
-  if (h_status == A3D_SOLVE_FAILED) set_error("GaussNewton::solve() returned None (count == 0 or Cholesky failed)");
-  return (a3d_status)h_status;
+  A3D_TRY(icp_reserve(map));
+  return solo_icp_align(map->ctx, &map->icp, *params, &start, icp_grid(map, (uint32_t)d_source->len),
+                        "a3d_voxel_map_icp_align_device", pass_launcher(map, params, d_source), out_pose);
 }
 
 a3d_status a3d_voxel_map_icp_accumulate_device(a3d_voxel_map* map, const a3d_icp_params* params,
                                                const a3d_point_cloud_view* d_source, const a3d_pose* pose,
                                                a3d_gn_state* out_state) {
   A3D_TRY(check_icp_call(map, params, d_source, out_state));
-  double sums[GN_PARTIAL] = {};
   if (!map->block) {  // no table yet: nothing is accumulated
+    const double sums[GN_PARTIAL] = {};
     gn_states_from_sums(sums, out_state, nullptr);
     return A3D_OK;
   }
-  a3d_context* ctx = map->ctx;
-  A3D_HIP_TRY(hipSetDevice(ctx->device));
-  IcpBuffers b;
-  A3D_TRY(icp_buffers(map, &b));
-  hipStream_t s = ctx->stream;
-  const Pose h_pose = pose ? pose_from_c(pose) : pose_eye();
-  a3d_status st = A3D_OK;
-  if (hipMemcpyAsync(b.start_pose, &h_pose, sizeof(Pose), hipMemcpyHostToDevice, s) != hipSuccess) st = A3D_HIP_ERROR;
-  if (st == A3D_OK) st = launch_job_init(s, b.state, b.start_pose, 1);
-  HeadArgs none{};  // the per-iteration launch with nothing to finish at its head: partials in buffer 0
-  none.mode = SOLVE_NONE;
-  if (st == A3D_OK) st = launch_head_pass(map, b, gates_of(params), d_source, 0, none);
-  if (st == A3D_OK) st = launch_gn_readback(s, b.partials, (int)icp_grid(map, (uint32_t)d_source->len), b.readback);
-  if (st == A3D_OK && hipMemcpyAsync(sums, b.readback, sizeof(sums), hipMemcpyDeviceToHost, s) != hipSuccess)
-    st = A3D_HIP_ERROR;
-  if (hipStreamSynchronize(s) != hipSuccess && st == A3D_OK) st = A3D_HIP_ERROR;
-  if (st == A3D_HIP_ERROR)
-    set_error("a3d_voxel_map_icp_accumulate_device: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-  if (st != A3D_OK) return st;
-  gn_states_from_sums(sums, out_state, nullptr);
-  return A3D_OK;
+  A3D_TRY(icp_reserve(map));
+  return solo_icp_accumulate(map->ctx, &map->icp, pose ? pose_from_c(pose) : pose_eye(),
+                             icp_grid(map, (uint32_t)d_source->len), "a3d_voxel_map_icp_accumulate_device",
+                             pass_launcher(map, params, d_source), out_state);
 }
 
 a3d_status a3d_voxel_map_icp_last_device_ms(a3d_voxel_map* map, float* out_ms) {
   A3D_REQUIRE(map && out_ms, A3D_INVALID_PARAMETER, "null argument");
-  *out_ms = map->icp_last_device_ms;
+  *out_ms = map->icp.last_device_ms;
   return A3D_OK;
 }
 

@@ -1272,6 +1272,29 @@ class DevicePointCloud:
         self.d_points = self.d_normals = self.d_colors = None
 
 
+def _resident_cloud(owner, cloud, what):
+    """`cloud` if it is a DevicePointCloud of `owner`'s context; `what` names the method that was given it."""
+    name = type(owner).__name__
+    if not isinstance(cloud, DevicePointCloud):
+        raise TypeError(f"{name}.{what} takes a DevicePointCloud (got {type(cloud).__name__}); there is no host fallback")
+    if cloud.ctx is not owner.ctx:
+        kind = "map" if isinstance(owner, DeviceVoxelMap) else "volume"
+        raise _abi.InvalidParameter(f"{name}.{what}: the cloud must live on the {kind}'s context")
+    return cloud
+
+
+def _device_queries(owner, queries, what):
+    """(device pointer, m, buffer to free or None) of `queries`: a resident cloud of `owner`'s context, or an [m, 3] array
+    uploaded for the call."""
+    if isinstance(queries, DevicePointCloud):
+        return _resident_cloud(owner, queries, what).d_points, queries.n, None
+    q = np.ascontiguousarray(queries, np.float32)
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise _abi.InvalidParameter(f"{type(owner).__name__}.{what}: queries is a DevicePointCloud or an [m, 3] array")
+    own = owner.ctx.to_device(q) if len(q) else None
+    return own, len(q), own
+
+
 class DeviceVoxelMap:
     """A persistent voxel map in HBM (a3d_voxel_map_*): resident clouds go in frame by frame, and after any sequence of
     inserts extract() is DevicePointCloud.merge(all inserted clouds, their transforms).voxel_downsample(voxel_size,
@@ -1443,13 +1466,6 @@ class DeviceVoxelMap:
         """retain() with nothing to remove: renumbers the cells 0 ... cells-1 and shrinks the table to fit."""
         return self.retain()
 
-    def _resident_source(self, cloud, what):
-        if not isinstance(cloud, DevicePointCloud):
-            raise TypeError(f"DeviceVoxelMap.{what} takes a DevicePointCloud (got {type(cloud).__name__}); there is no host fallback")
-        if cloud.ctx is not self.ctx:
-            raise _abi.InvalidParameter(f"DeviceVoxelMap.{what}: the cloud must live on the map's context")
-        return cloud
-
     def nearest(self, queries, transform=None):
         """The map's association (a3d_voxel_map_nearest_device) for every point of `queries`, a DevicePointCloud of the
         map's context or an [m, 3] float32 array (uploaded for the call), moved by `transform` first (None: as they
@@ -1457,15 +1473,7 @@ class DeviceVoxelMap:
         27 cells around the query and the squared distance to it; 0xFFFFFFFF and +inf where there is none.  It is the
         exact nearest row wherever that row lies within about one cell of the query, and not R3dTree.nearest."""
         ctx = self.ctx
-        own = None
-        if isinstance(queries, DevicePointCloud):
-            d_q, m = self._resident_source(queries, "nearest").d_points, queries.n
-        else:
-            q = np.ascontiguousarray(queries, np.float32)
-            if q.ndim != 2 or q.shape[1] != 3:
-                raise _abi.InvalidParameter("DeviceVoxelMap.nearest: queries is a DevicePointCloud or an [m, 3] array")
-            m = len(q)
-            d_q = own = ctx.to_device(q) if m else None
+        d_q, m, own = _device_queries(self, queries, "nearest")
         seq, dist2 = np.empty(m, np.uint32), np.empty(m, np.float32)
         if m == 0:
             return seq, dist2
@@ -1487,7 +1495,7 @@ class DeviceVoxelMap:
         in place of the kd-tree, started from `initial` (None: Transform.eye()).  Returns the Transform that maps
         `source` as given into the map's frame; no extract, no tree build, and the map is not changed.  Map and source
         need normals."""
-        v = self._resident_source(source, "align").view()
+        v = _resident_cloud(self, source, "align").view()
         p = params.to_c()
         init = None if initial is None else C.byref(initial.to_c())
         out = _abi.PoseC()
@@ -1497,7 +1505,7 @@ class DeviceVoxelMap:
 
     def accumulate(self, source, params, transform):
         """One pass of align's per-point loop under `transform` (test hook, as Icp.accumulate): {H, g, ssq, count}."""
-        v = self._resident_source(source, "accumulate").view()
+        v = _resident_cloud(self, source, "accumulate").view()
         p = params.to_c()
         t = transform.to_c()
         g = _abi.GnStateC()
@@ -1716,13 +1724,6 @@ class DeviceTsdfVolume:
         cloud, d_faces, faces = self._extract(min_weight, True, True, self.colors)
         return DeviceTriangleMesh(cloud, d_faces, faces)
 
-    def _resident_source(self, cloud, what):
-        if not isinstance(cloud, DevicePointCloud):
-            raise TypeError(f"DeviceTsdfVolume.{what} takes a DevicePointCloud (got {type(cloud).__name__}); there is no host fallback")
-        if cloud.ctx is not self.ctx:
-            raise _abi.InvalidParameter(f"DeviceTsdfVolume.{what}: the cloud must live on the volume's context")
-        return cloud
-
     def sample(self, queries, pose=None):
         """The field at every point of `queries` (a3d_tsdf_volume_sample_device), a DevicePointCloud of the volume's
         context or an [m, 3] float32 array (uploaded for the call), moved by `pose` first (None: as they are).  Returns
@@ -1731,15 +1732,7 @@ class DeviceTsdfVolume:
         where the field has no value (outside the volume, or beside a voxel never observed); the distance with a zero
         normal where it has no direction (at the truncation, or beside a hole).  The volume is not changed."""
         ctx = self.ctx
-        own = None
-        if isinstance(queries, DevicePointCloud):
-            d_q, m = self._resident_source(queries, "sample").d_points, queries.n
-        else:
-            q = np.ascontiguousarray(queries, np.float32)
-            if q.ndim != 2 or q.shape[1] != 3:
-                raise _abi.InvalidParameter("DeviceTsdfVolume.sample: queries is a DevicePointCloud or an [m, 3] array")
-            m = len(q)
-            d_q = own = ctx.to_device(q) if m else None
+        d_q, m, own = _device_queries(self, queries, "sample")
         distance, normals = np.empty(m, np.float32), np.empty((m, 3), np.float32)
         if m == 0:
             return distance, normals
@@ -1761,7 +1754,7 @@ class DeviceTsdfVolume:
         with the field's distance and gradient in place of the kd-tree, started from `initial` (None: Transform.eye()).
         Returns the Transform that maps `cloud` as given into the volume's world frame; no raycast, no pyramid, no
         tree, and the volume is not changed.  The cloud needs normals."""
-        v = self._resident_source(cloud, "align").view()
+        v = _resident_cloud(self, cloud, "align").view()
         p = params.to_c()
         init = None if initial is None else C.byref(initial.to_c())
         out = _abi.PoseC()
@@ -1772,7 +1765,7 @@ class DeviceTsdfVolume:
     def accumulate(self, cloud, params, pose=None):
         """One pass of align's per-point loop under `pose` (None: the identity); test hook, as Icp.accumulate:
         {H, g, ssq, count}."""
-        v = self._resident_source(cloud, "accumulate").view()
+        v = _resident_cloud(self, cloud, "accumulate").view()
         p = params.to_c()
         t = None if pose is None else C.byref(pose.to_c())
         g = _abi.GnStateC()

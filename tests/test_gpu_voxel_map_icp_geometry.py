@@ -1,8 +1,8 @@
 """The launch geometry of voxel_map_icp.hip at the sizes the product runs: sources longer than one trip of the
 grid-stride loops, num_cus partials per iteration, both halves of the partial double buffer at their real offsets.
 
-B = ctx.num_cus().  voxel_map_icp_head_kernel launches min(ceil(m / 1024), B) blocks of 1024 threads, so one trip serves
-S_icp = 1024 B points; voxel_map_nearest_kernel launches min(ceil(m / 256), 8 B) blocks of 256, S_near = 2048 B.  Both
+B = ctx.num_cus().  The ICP's kernel, solo_icp_head_kernel over MapTarget (csrc/pcl_icp.hpp, voxel_map_icp.hip),
+launches min(ceil(m / 1024), B) blocks of 1024 threads, so one trip serves S_icp = 1024 B points; voxel_map_nearest_kernel launches min(ceil(m / 256), 8 B) blocks of 256, S_near = 2048 B.  Both
 are derived from the device here, and every test that means to take a second trip asserts m > S.  The map is the scene
 of test_gpu_voxel_map_icp.py; the source is its 5 000-point source repeated with period P, S % P != 0, so that an index
 wrong by one stride lands on another query and changes the answer.  Expected values: the association and the per-point
