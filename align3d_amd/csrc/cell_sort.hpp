@@ -189,35 +189,29 @@ __device__ __forceinline__ void consume_run(const CellRecord* __restrict__ sorte
 }
 #endif  // __HIPCC__
 
-// A batch's sort as the host plans it: the tiles so far, and the bytes so far of the two parts of the scratch tail that
-// hold every job's hash table and every job's records.
+// A batch's sort as the host plans it: the tiles so far, and the two parts of the scratch tail that hold every job's hash
+// table and every job's records.
 struct CellSortPlan {
   uint64_t tiles = 0;
-  size_t table_bytes = 0, sorted_bytes = 0;
+  TailPart tables, sorted;
 };
 
-// Adds a cloud of `len` points (0 < len < 2^32) to the plan and fills the job's len, tiles, slot mask and, as offsets
-// inside their parts for now, table and sorted.  `too_long`: the caller's message for a cloud within one tile of 2^32.
+// Adds a cloud of `len` points (0 < len < 2^32) of the entry point `name` to the plan and fills the job's len, tiles,
+// slot mask and, as offsets inside their parts for now, table and sorted.
 template <class Job>
-inline a3d_status cell_sort_plan(CellSortPlan* plan, uint64_t len, const char* too_long, Job* j) {
-  j->len = (uint32_t)len;
-  A3D_TRY(plan_tiles(len, CELL_CHUNK, CELL_MAX_TILES, &plan->tiles, &j->first_tile, &j->chunks_per_tile));
+inline a3d_status cell_sort_plan(CellSortPlan* plan, const char* name, uint64_t len, Job* j) {
+  A3D_TRY(plan_job_tiles(name, len, CELL_CHUNK, CELL_MAX_TILES, &plan->tiles, j));
   j->n_tiles = (uint32_t)plan->tiles - j->first_tile;
-  // the kernels' 32-bit point positions run up to one tile span past len
-  A3D_REQUIRE(len + (uint64_t)j->chunks_per_tile * CELL_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER, too_long);
-  uint64_t slots = 2;
-  while (slots < 2 * len) slots <<= 1;
+  const uint64_t slots = table_slots(len);
   j->slot_mask = slots - 1;
-  j->table = (VoxelSlot*)plan->table_bytes, j->sorted = (CellRecord*)plan->sorted_bytes;
-  plan->table_bytes += slots * sizeof(VoxelSlot), plan->sorted_bytes += pad256(len * sizeof(CellRecord));
+  plan->tables.take(&j->table, slots * sizeof(VoxelSlot)), plan->sorted.take(&j->sorted, pad256(len * sizeof(CellRecord)));
   return A3D_OK;
 }
 
-// The job's two offsets onto the parts of the scratch tail.
+// The job's two offsets onto the parts of the scratch tail (after place_parts).
 template <class Job>
-inline void cell_sort_rebase(Job* j, char* d_tables, char* d_sorted) {
-  j->table = (VoxelSlot*)(d_tables + (size_t)j->table);
-  j->sorted = (CellRecord*)(d_sorted + (size_t)j->sorted);
+inline void cell_sort_rebase(const CellSortPlan& plan, Job* j) {
+  plan.tables.rebase(&j->table), plan.sorted.rebase(&j->sorted);
 }
 
 #ifdef __HIPCC__

@@ -1,4 +1,7 @@
-// What the batched operations over resident clouds share (pointcloud.hip, cloud_transform.hip, voxel_downsample.hip).
+// What the batched operations over resident clouds share: the conversion from range images (pointcloud.hip), transform
+// and merge (cloud_transform.hip), the voxel downsamples (voxel_downsample.hip, voxel_mean.hip), select, knn distances
+// and clustering (cloud_outliers.hip), normals (cloud_normals.hip), plane segmentation (cloud_plane.hip), the voxel map's
+// insert and extract (voxel_map.hip) and the renders (cloud_render.hip).
 // A call turns its clouds into a table of jobs in the context's scratch region 3 and launches over every tile of every
 // job at once: a block finds its job with a block-uniform search over first_tile, and no block waits on another block.
 // An operation that compacts runs a count pass (per tile and per job) and a write pass whose blocks sum their job's
@@ -6,8 +9,15 @@
 // the count pass and the start of the write pass stay in the kernels (cloud_count_kernel / voxel_flag_kernel,
 // cloud_write_kernel / voxel_compact_kernel; keep each pair alike): as functions of this header they were inlined
 // into slightly different code.
+// The host front of those calls is here once, in plain C++17 (tests/cpp/cloud_batch_host_test.cpp runs it on made-up
+// addresses): refuse() for a refusal in an entry point's name, RangeRecorder for "no output overlaps anything",
+// plan_tiles / plan_job_tiles, compact_front / compact_finish for the calls that compact (select, voxel downsample,
+// voxel mean), TailPart for the per-job arrays in the scratch tail (an offset until the region is allocated, an address
+// afterwards), and download_words / zero_results / scatter_words for the end of a call.  A job struct is filled by field
+// name, so every job keeps its own layout.
 #pragma once
 #include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 #include "common.hpp"
@@ -55,22 +65,41 @@ __device__ __forceinline__ void store_color(uint8_t* colors, size_t index, uint3
 }
 #endif  // __HIPCC__
 
-struct ByteRange {
-  uintptr_t begin, end;
-  bool output;
-};
-
-// Whether any output range overlaps any other range (inputs may overlap inputs).
-inline bool outputs_overlap(std::vector<ByteRange>& ranges) {
-  std::sort(ranges.begin(), ranges.end(), [](const ByteRange& a, const ByteRange& b) { return a.begin < b.begin; });
-  uintptr_t end_any = 0, end_out = 0;  // furthest end among the ranges / the output ranges seen so far
-  for (const ByteRange& r : ranges) {
-    if (r.begin < (r.output ? end_any : end_out)) return true;
-    end_any = std::max(end_any, r.end);
-    if (r.output) end_out = std::max(end_out, r.end);
-  }
-  return false;
+// The refusal `what` of the entry point `name`, as the thread's error text.
+inline a3d_status refuse(a3d_status status, const char* name, const char* what) {
+  set_error("%s: %s", name, what);
+  return status;
 }
+
+// The byte ranges a call reads (in) and writes (out).  A null pointer or zero bytes record nothing.
+class RangeRecorder {
+ public:
+  void reserve(size_t n) { ranges_.reserve(n); }
+  void in(const void* p, uint64_t bytes) { add(p, bytes, false); }
+  void out(const void* p, uint64_t bytes) { add(p, bytes, true); }
+  // Whether any output range overlaps any other range (inputs may overlap inputs; ranges that touch do not overlap).
+  bool overlap() {
+    std::sort(ranges_.begin(), ranges_.end(), [](const Range& a, const Range& b) { return a.begin < b.begin; });
+    uintptr_t end_any = 0, end_out = 0;  // furthest end among the ranges / the output ranges seen so far
+    for (const Range& r : ranges_) {
+      if (r.begin < (r.output ? end_any : end_out)) return true;
+      end_any = std::max(end_any, r.end);
+      if (r.output) end_out = std::max(end_out, r.end);
+    }
+    return false;
+  }
+  size_t size() const { return ranges_.size(); }
+
+ private:
+  struct Range {
+    uintptr_t begin, end;
+    bool output;
+  };
+  void add(const void* p, uint64_t bytes, bool output) {
+    if (p && bytes) ranges_.push_back({(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes, output});
+  }
+  std::vector<Range> ranges_;
+};
 
 // A job's `len` elements as tiles of one or more chunks of `chunk` elements: at most `max_tiles` tiles, so the offset sum
 // of a write-pass block stays short whatever the length.  *tiles: the batch's running total, advanced past this job
@@ -82,6 +111,104 @@ inline a3d_status plan_tiles(uint64_t len, uint32_t chunk, uint32_t max_tiles, u
   *first_tile = (uint32_t)*tiles;
   *tiles += (chunks + *chunks_per_tile - 1) / *chunks_per_tile;
   A3D_REQUIRE(*tiles < (1ull << 31), A3D_INVALID_PARAMETER, "batch too large");
+  return A3D_OK;
+}
+
+// plan_tiles into the job's own fields, with its len; refuses a cloud so long that the kernels' 32-bit point positions,
+// which run up to one tile span past len, would wrap.
+template <class Job>
+inline a3d_status plan_job_tiles(const char* name, uint64_t len, uint32_t chunk, uint32_t max_tiles, uint64_t* tiles, Job* j) {
+  j->len = (uint32_t)len;
+  A3D_TRY(plan_tiles(len, chunk, max_tiles, tiles, &j->first_tile, &j->chunks_per_tile));
+  if (len + (uint64_t)j->chunks_per_tile * chunk >= (1ull << 32))
+    return refuse(A3D_INVALID_PARAMETER, name, "a cloud within one tile of 2^32 points");
+  return A3D_OK;
+}
+
+// The per-cloud arrays of a call that compacts (select, voxel downsample, voxel mean), as its entry point received them.
+// colors, out_normals, out_colors and out_index may be null, and so may their entries.
+struct CompactArgs {
+  const a3d_point_cloud_view* clouds;
+  const uint8_t* const* colors;
+  float* const* out_points;
+  float* const* out_normals;
+  uint8_t* const* out_colors;
+  uint32_t* const* out_index;
+  const uint64_t* capacities;
+};
+
+// The front of such a call for its non-empty cloud i: what it requires of the cloud (`others_given`: the entry point's
+// further arrays of this cloud are there; `nulls`: its text for a null one), the job's points ... out_colors, out_index,
+// capacity, len and tiles, and the ranges: every input whole, of each output the first min(len, capacity) elements,
+// which is all the call may write.
+template <class Job>
+inline a3d_status compact_front(const char* name, const CompactArgs& a, uint64_t i, bool others_given, const char* nulls,
+                                uint32_t chunk, uint32_t max_tiles, uint64_t* tiles, RangeRecorder* ranges, Job* j) {
+  const a3d_point_cloud_view& c = a.clouds[i];
+  if (!(c.points && a.out_points[i] && others_given)) return refuse(A3D_INVALID_PARAMETER, name, nulls);
+  float* out_normals = a.out_normals ? a.out_normals[i] : nullptr;
+  if (out_normals && !c.normals) return refuse(A3D_MISSING_FIELD, name, "cloud has no normals");
+  uint8_t* out_colors = a.out_colors ? a.out_colors[i] : nullptr;
+  const uint8_t* colors = out_colors && a.colors ? a.colors[i] : nullptr;
+  if (out_colors && !colors) return refuse(A3D_MISSING_FIELD, name, "cloud has no colours");
+  j->points = c.points, j->normals = out_normals ? c.normals : nullptr, j->colors = colors;
+  j->out_points = a.out_points[i], j->out_normals = out_normals, j->out_colors = out_colors;
+  j->out_index = a.out_index ? a.out_index[i] : nullptr;
+  j->capacity = a.capacities[i];
+  A3D_TRY(plan_job_tiles(name, c.len, chunk, max_tiles, tiles, j));
+  const uint64_t kept = std::min<uint64_t>(c.len, j->capacity);
+  ranges->in(j->points, c.len * 12), ranges->in(j->normals, c.len * 12), ranges->in(j->colors, c.len * 3);
+  ranges->out(j->out_points, kept * 12), ranges->out(out_normals, kept * 12), ranges->out(j->out_index, kept * 4);
+  ranges->out(out_colors, kept * 3);
+  return A3D_OK;
+}
+
+// A part of the scratch tail that holds one array per job.  While the clouds are walked a job's field holds the offset
+// of its array inside the part; once the region is there, place_parts says where each part starts and rebase turns the
+// offset into the address.
+struct TailPart {
+  size_t bytes = 0;      // of the arrays taken so far
+  char* base = nullptr;  // set by place_parts
+  template <class T>
+  void take(T** field, size_t array_bytes) {
+    *field = (T*)bytes;
+    bytes += array_bytes;
+  }
+  template <class T>
+  void rebase(T** field) const {
+    *field = (T*)(base + (size_t)*field);
+  }
+};
+// The parts back to back from `at` (BatchScratch::tail), in the order given.
+inline void place_parts(char* at, std::initializer_list<TailPart*> parts) {
+  for (TailPart* p : parts) p->base = at, at += p->bytes;
+}
+
+// A per-cloud result array zeroed, if the caller gave one (`per` words per cloud).
+inline void zero_results(uint64_t* out, uint64_t n, size_t per = 1) {
+  if (out) std::fill_n(out, per * n, (uint64_t)0);
+}
+// A run of `per` words per job to the per-cloud array `out`, if the caller gave one.
+inline void scatter_words(const unsigned long long* words, const std::vector<uint64_t>& cloud_of_job, uint64_t* out,
+                          size_t per = 1) {
+  if (!out) return;
+  for (size_t q = 0; q < cloud_of_job.size(); ++q)
+    for (size_t w = 0; w < per; ++w) out[per * cloud_of_job[q] + w] = words[per * q + w];
+}
+
+// The end of a call that compacts: words = lens per job, then dropped per job (read only if out_dropped is given).  A
+// capacity below its cloud's count (`rows`: what the entry point calls them) is refused after the counts are out.
+template <class Job>
+inline a3d_status compact_finish(const char* name, const char* rows, const std::vector<Job>& jobs,
+                                 const std::vector<uint64_t>& cloud_of_job, const unsigned long long* words,
+                                 uint64_t* out_lens, uint64_t* out_dropped) {
+  scatter_words(words, cloud_of_job, out_lens);
+  scatter_words(words + jobs.size(), cloud_of_job, out_dropped);
+  for (size_t k = 0; k < jobs.size(); ++k)
+    if (words[k] > jobs[k].capacity) {
+      set_error("%s: a capacity is smaller than its cloud's %s (nothing was written)", name, rows);
+      return A3D_INVALID_PARAMETER;
+    }
   return A3D_OK;
 }
 
@@ -114,6 +241,16 @@ inline a3d_status batch_scratch(a3d_context* ctx, size_t table_bytes, size_t n_w
 inline a3d_status batch_upload(BatchScratch& b, const void* jobs, hipStream_t s) {
   memcpy(b.staging.data(), jobs, b.table_bytes);
   A3D_HIP_TRY(hipMemcpyAsync(b.jobs, b.staging.data(), b.staging.size(), hipMemcpyHostToDevice, s));
+  return A3D_OK;
+}
+
+// The end of a call: its n words to the host and the call's one wait.  Host-synchronous: the caller may free inputs and
+// outputs right after.
+inline a3d_status download_words(const unsigned long long* d_words, size_t n, hipStream_t s,
+                                 std::vector<unsigned long long>* words) {
+  words->resize(n);
+  A3D_HIP_TRY(hipMemcpyAsync(words->data(), d_words, n * 8, hipMemcpyDeviceToHost, s));
+  A3D_HIP_TRY(hipStreamSynchronize(s));
   return A3D_OK;
 }
 

@@ -248,21 +248,19 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
                                                     uint64_t* out_valid, uint64_t* out_dropped) {
   if (n == 0) return A3D_OK;
   A3D_REQUIRE(ctx && d_clouds && d_out_normals && out_valid, A3D_INVALID_PARAMETER, "null argument");
-  A3D_REQUIRE(std::isfinite(radius) && radius > 0.f, A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_estimate_normals_device: the radius must be finite and positive");
-  CnParams prm{radius, radius * radius, 32768.0f / radius, min_neighbors};
-  A3D_REQUIRE(prm.r2 > 0.f && std::isfinite(prm.s), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_estimate_normals_device: a radius whose square is 0 in f32 (below about 1e-19)");
+  static const char NAME[] = "a3d_point_clouds_estimate_normals_device";
+  VoxelGrid grid;
+  CnParams prm{radius, 0.f, 0.f, min_neighbors};
+  A3D_TRY(radius_grid_from(NAME, radius, &grid, &prm.r2, &prm.s));
   A3D_REQUIRE(min_neighbors >= 3, A3D_INVALID_PARAMETER,
               "a3d_point_clouds_estimate_normals_device: min_neighbors must be at least 3 (a plane needs three points)");
   if (viewpoints_host)
     for (uint64_t i = 0; i < 3 * n; ++i)
       A3D_REQUIRE(std::isfinite(viewpoints_host[i]), A3D_INVALID_PARAMETER,
                   "a3d_point_clouds_estimate_normals_device: the viewpoints must be finite");
-  const VoxelGrid grid{radius, 0.f, 0.f, 0.f};
   std::vector<NormalsJob> jobs;
   std::vector<uint64_t> cloud_of_job;
-  std::vector<ByteRange> ranges;
+  RangeRecorder ranges;
   jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(5 * n);
   CellSortPlan plan;
   for (uint64_t i = 0; i < n; ++i) {
@@ -278,30 +276,24 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
     j.out_curvature = d_out_curvature ? d_out_curvature[i] : nullptr;
     j.out_counts = d_out_counts ? d_out_counts[i] : nullptr;
     if (viewpoints_host) j.ex = viewpoints_host[3 * i], j.ey = viewpoints_host[3 * i + 1], j.ez = viewpoints_host[3 * i + 2];
-    A3D_TRY(cell_sort_plan(&plan, c.len, "a3d_point_clouds_estimate_normals_device: a cloud within one tile of 2^32 points", &j));
+    A3D_TRY(cell_sort_plan(&plan, NAME, c.len, &j));
     jobs.push_back(j), cloud_of_job.push_back(i);
-    const uintptr_t bytes = (uintptr_t)c.len * 12;
-    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + bytes, false});
+    ranges.in(j.points, c.len * 12);
     // in place is the one allowed overlap: a thread reads its own row's old normal before it writes the new one
-    if (j.old_normals && j.old_normals != j.out_normals)
-      ranges.push_back({(uintptr_t)j.old_normals, (uintptr_t)j.old_normals + bytes, false});
-    ranges.push_back({(uintptr_t)j.out_normals, (uintptr_t)j.out_normals + bytes, true});
-    if (j.out_curvature) ranges.push_back({(uintptr_t)j.out_curvature, (uintptr_t)j.out_curvature + (uintptr_t)c.len * 4, true});
-    if (j.out_counts) ranges.push_back({(uintptr_t)j.out_counts, (uintptr_t)j.out_counts + (uintptr_t)c.len * 4, true});
+    if (j.old_normals != j.out_normals) ranges.in(j.old_normals, c.len * 12);
+    ranges.out(j.out_normals, c.len * 12), ranges.out(j.out_curvature, c.len * 4), ranges.out(j.out_counts, c.len * 4);
   }
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_estimate_normals_device: an output overlaps an input or another output (only the normals "
-              "may be estimated in place)");
-  for (uint64_t i = 0; i < n; ++i) out_valid[i] = 0;
-  if (out_dropped)
-    for (uint64_t i = 0; i < n; ++i) out_dropped[i] = 0;
+  if (ranges.overlap())
+    return refuse(A3D_INVALID_PARAMETER, NAME,
+                  "an output overlaps an input or another output (only the normals may be estimated in place)");
+  zero_results(out_valid, n), zero_results(out_dropped, n);
   if (jobs.empty()) return A3D_OK;
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   BatchScratch scratch;  // the words: cursors (kept counts), dropped, valid, fault; the tail: hash tables | records
-  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(NormalsJob), 3 * n_jobs + 1, 0, plan.table_bytes + plan.sorted_bytes, &scratch));
-  char* d_tables = scratch.tail;
-  for (NormalsJob& j : jobs) cell_sort_rebase(&j, d_tables, d_tables + plan.table_bytes);
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(NormalsJob), 3 * n_jobs + 1, 0, plan.tables.bytes + plan.sorted.bytes, &scratch));
+  place_parts(scratch.tail, {&plan.tables, &plan.sorted});
+  for (NormalsJob& j : jobs) cell_sort_rebase(plan, &j);
   const NormalsJob* d_jobs = (const NormalsJob*)scratch.jobs;
   unsigned long long* d_cursor = scratch.words;
   unsigned long long* d_dropped = d_cursor + n_jobs;
@@ -309,7 +301,7 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
   unsigned long long* d_fault = d_cursor + 3 * n_jobs;
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, jobs.data(), s));
-  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, plan.table_bytes, s));  // every key word empty, every count 0
+  A3D_HIP_TRY(hipMemsetAsync(plan.tables.base, 0, plan.tables.bytes, s));  // every key word empty, every count 0
   const dim3 grid_dim((uint32_t)plan.tiles), block(CELL_THREADS);
   const uint32_t nj = (uint32_t)n_jobs;
   A3D_TRY(cell_sort_launch(d_jobs, nj, plan.tiles, grid, d_cursor, d_dropped, d_fault, s));
@@ -328,15 +320,10 @@ a3d_status a3d_point_clouds_estimate_normals_device(a3d_context* ctx, const a3d_
 #endif
     hipLaunchKernelGGL((normals_estimate_kernel<true, CELL_AHEAD, false>), grid_dim, block, 0, s, d_jobs, nj, grid, prm, d_kept, d_valid);
   A3D_HIP_TRY(hipGetLastError());
-  std::vector<unsigned long long> words(3 * n_jobs + 1);
-  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_cursor, words.size() * 8, hipMemcpyDeviceToHost, s));
-  // host-synchronous: the caller may free inputs and outputs right after
-  A3D_HIP_TRY(hipStreamSynchronize(s));
+  std::vector<unsigned long long> words;
+  A3D_TRY(download_words(d_cursor, 3 * n_jobs + 1, s, &words));
   A3D_REQUIRE(words[3 * n_jobs] == 0, A3D_HIP_ERROR, "a3d_point_clouds_estimate_normals_device: a hash table filled up");
-  for (size_t k = 0; k < n_jobs; ++k) {
-    out_valid[cloud_of_job[k]] = words[2 * n_jobs + k];
-    if (out_dropped) out_dropped[cloud_of_job[k]] = words[n_jobs + k];
-  }
+  scatter_words(&words[2 * n_jobs], cloud_of_job, out_valid), scatter_words(&words[n_jobs], cloud_of_job, out_dropped);
   return A3D_OK;
 }
 

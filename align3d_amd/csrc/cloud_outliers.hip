@@ -668,61 +668,40 @@ a3d_status a3d_point_clouds_select_device(a3d_context* ctx, const a3d_point_clou
                                           float* const* d_out_normals, uint8_t* const* d_out_colors,
                                           uint32_t* const* d_out_index, const uint64_t* capacities, uint64_t* out_lens) {
   if (n == 0) return A3D_OK;
-  A3D_REQUIRE(ctx && d_clouds && d_values && lo && hi && d_out_points && capacities && out_lens, A3D_INVALID_PARAMETER,
-              "null argument");
+  static const char NAME[] = "a3d_point_clouds_select_device";
+  if (!(ctx && d_clouds && d_values && lo && hi && d_out_points && capacities && out_lens))
+    return refuse(A3D_INVALID_PARAMETER, NAME, "null argument");
+  const CompactArgs args{d_clouds, d_colors, d_out_points, d_out_normals, d_out_colors, d_out_index, capacities};
   std::vector<SelectJob> jobs;
   std::vector<uint64_t> cloud_of_job;
-  std::vector<ByteRange> ranges;
+  RangeRecorder ranges;
   jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(8 * n);
   uint64_t tiles = 0;
-  size_t flag_bytes = 0;  // offsets of a job's ballot words inside the scratch region, for now
+  TailPart flags;
   for (uint64_t i = 0; i < n; ++i) {
-    const a3d_point_cloud_view& c = d_clouds[i];
-    A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
-    if (c.len == 0) continue;  // yields no rows; its pointers may be null
-    A3D_REQUIRE(c.points && d_out_points[i] && d_values[i], A3D_INVALID_PARAMETER, "null points, values or output pointer");
-    float* out_normals = d_out_normals ? d_out_normals[i] : nullptr;
-    A3D_REQUIRE(!out_normals || c.normals, A3D_MISSING_FIELD, "cloud has no normals");
-    uint8_t* out_colors = d_out_colors ? d_out_colors[i] : nullptr;
-    const uint8_t* colors = out_colors && d_colors ? d_colors[i] : nullptr;
-    A3D_REQUIRE(!out_colors || colors, A3D_MISSING_FIELD, "cloud has no colours");
+    const uint64_t len = d_clouds[i].len;
+    if (len >= (1ull << 32)) return refuse(A3D_INVALID_PARAMETER, NAME, "a cloud of 2^32 points or more");
+    if (len == 0) continue;  // yields no rows; its pointers may be null
     SelectJob j{};
-    j.points = c.points, j.normals = out_normals ? c.normals : nullptr;
-    j.out_points = d_out_points[i], j.out_normals = out_normals;
-    j.out_index = d_out_index ? d_out_index[i] : nullptr;
+    // (the values are this call's own array: their null test rides in the shared one, which is why compact_front takes a
+    // flag and the text: one refusal, at the place in the order where it has always stood)
+    A3D_TRY(compact_front(NAME, args, i, d_values[i] != nullptr, "null points, values or output pointer", CELL_CHUNK,
+                          CELL_MAX_TILES, &tiles, &ranges, &j));
     j.values = d_values[i], j.lo = lo[i], j.hi = hi[i];
-    j.colors = colors, j.out_colors = out_colors;
-    j.capacity = capacities[i];
-    j.len = (uint32_t)c.len;
-    A3D_TRY(plan_tiles(c.len, CELL_CHUNK, CELL_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
-    // the kernels' 32-bit row positions run up to one tile span past len
-    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * CELL_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
-                "a3d_point_clouds_select_device: a cloud within one tile of 2^32 points");
-    j.flags = (unsigned long long*)flag_bytes;
-    flag_bytes += pad256((c.len + 63) / 64 * 8);
+    ranges.in(j.values, len * 4);
+    flags.take(&j.flags, pad256((len + 63) / 64 * 8));
     jobs.push_back(j), cloud_of_job.push_back(i);
-    // what the call may write is the first min(len, capacity) elements of each output
-    const uintptr_t in_bytes = (uintptr_t)c.len * 12, kept = (uintptr_t)std::min<uint64_t>(c.len, j.capacity);
-    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + in_bytes, false});
-    ranges.push_back({(uintptr_t)j.values, (uintptr_t)j.values + (uintptr_t)c.len * 4, false});
-    if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + in_bytes, false});
-    if (j.colors) ranges.push_back({(uintptr_t)j.colors, (uintptr_t)j.colors + (uintptr_t)c.len * 3, false});
-    if (kept) {
-      ranges.push_back({(uintptr_t)j.out_points, (uintptr_t)j.out_points + kept * 12, true});
-      if (out_normals) ranges.push_back({(uintptr_t)out_normals, (uintptr_t)out_normals + kept * 12, true});
-      if (j.out_index) ranges.push_back({(uintptr_t)j.out_index, (uintptr_t)j.out_index + kept * 4, true});
-      if (out_colors) ranges.push_back({(uintptr_t)out_colors, (uintptr_t)out_colors + kept * 3, true});
-    }
   }
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_select_device: an output overlaps an input or another output (there is no in-place form)");
-  for (uint64_t i = 0; i < n; ++i) out_lens[i] = 0;
+  if (ranges.overlap())
+    return refuse(A3D_INVALID_PARAMETER, NAME, "an output overlaps an input or another output (there is no in-place form)");
+  zero_results(out_lens, n);
   if (jobs.empty()) return A3D_OK;
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   BatchScratch scratch;  // the words: lens; the tail: ballot words
-  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(SelectJob), n_jobs, tiles, flag_bytes, &scratch));
-  for (SelectJob& j : jobs) j.flags = (unsigned long long*)(scratch.tail + (size_t)j.flags);
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(SelectJob), n_jobs, tiles, flags.bytes, &scratch));
+  place_parts(scratch.tail, {&flags});
+  for (SelectJob& j : jobs) flags.rebase(&j.flags);
   const SelectJob* d_jobs = (const SelectJob*)scratch.jobs;
   unsigned long long* d_lens = scratch.words;
   uint32_t* d_tile_counts = scratch.tile_counts;
@@ -734,18 +713,9 @@ a3d_status a3d_point_clouds_select_device(a3d_context* ctx, const a3d_point_clou
   hipLaunchKernelGGL(select_compact_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, (const uint32_t*)d_tile_counts,
                      (const unsigned long long*)d_lens);
   A3D_HIP_TRY(hipGetLastError());
-  std::vector<unsigned long long> words(n_jobs);
-  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_lens, words.size() * 8, hipMemcpyDeviceToHost, s));
-  // host-synchronous: the caller may free inputs and outputs right after
-  A3D_HIP_TRY(hipStreamSynchronize(s));
-  bool over = false;
-  for (size_t k = 0; k < n_jobs; ++k) {
-    out_lens[cloud_of_job[k]] = words[k];
-    over |= words[k] > jobs[k].capacity;
-  }
-  A3D_REQUIRE(!over, A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_select_device: a capacity is smaller than its cloud's kept rows (nothing was written)");
-  return A3D_OK;
+  std::vector<unsigned long long> words;
+  A3D_TRY(download_words(d_lens, n_jobs, s, &words));
+  return compact_finish(NAME, "kept rows", jobs, cloud_of_job, words.data(), out_lens, nullptr);
 }
 
 a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_point_cloud_view* d_clouds, uint64_t n,
@@ -753,17 +723,15 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
                                                 uint32_t* const* d_out_qsum, uint64_t* out_stats, uint64_t* out_dropped) {
   if (n == 0) return A3D_OK;
   A3D_REQUIRE(ctx && d_clouds, A3D_INVALID_PARAMETER, "null argument");
-  A3D_REQUIRE(std::isfinite(radius) && radius > 0.f, A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_knn_distance_device: the radius must be finite and positive");
-  KnnParams prm{radius, radius * radius, 32768.0f / radius, k};
-  A3D_REQUIRE(prm.r2 > 0.f && std::isfinite(prm.s), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_knn_distance_device: a radius whose square is 0 in f32 (below about 1e-19)");
+  static const char NAME[] = "a3d_point_clouds_knn_distance_device";
+  VoxelGrid grid;
+  KnnParams prm{radius, 0.f, 0.f, k};
+  A3D_TRY(radius_grid_from(NAME, radius, &grid, &prm.r2, &prm.s));
   A3D_REQUIRE(k <= CO_MAX_K, A3D_INVALID_PARAMETER, "a3d_point_clouds_knn_distance_device: k must be at most 32");
   A3D_REQUIRE(k == 0 || d_out_qsum, A3D_INVALID_PARAMETER, "null argument");
-  const VoxelGrid grid{radius, 0.f, 0.f, 0.f};
   std::vector<KnnJob> jobs;
   std::vector<uint64_t> cloud_of_job;
-  std::vector<ByteRange> ranges;
+  RangeRecorder ranges;
   jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(3 * n);
   CellSortPlan plan;
   for (uint64_t i = 0; i < n; ++i) {
@@ -775,25 +743,19 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
     j.points = c.points;
     j.out_counts = d_out_counts ? d_out_counts[i] : nullptr;
     j.out_qsum = k ? d_out_qsum[i] : nullptr;
-    A3D_TRY(cell_sort_plan(&plan, c.len, "a3d_point_clouds_knn_distance_device: a cloud within one tile of 2^32 points", &j));
+    A3D_TRY(cell_sort_plan(&plan, NAME, c.len, &j));
     jobs.push_back(j), cloud_of_job.push_back(i);
-    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + (uintptr_t)c.len * 12, false});
-    if (j.out_counts) ranges.push_back({(uintptr_t)j.out_counts, (uintptr_t)j.out_counts + (uintptr_t)c.len * 4, true});
-    if (j.out_qsum) ranges.push_back({(uintptr_t)j.out_qsum, (uintptr_t)j.out_qsum + (uintptr_t)c.len * 4, true});
+    ranges.in(j.points, c.len * 12), ranges.out(j.out_counts, c.len * 4), ranges.out(j.out_qsum, c.len * 4);
   }
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_knn_distance_device: an output overlaps an input or another output");
-  if (out_stats)
-    for (uint64_t i = 0; i < 4 * n; ++i) out_stats[i] = 0;
-  if (out_dropped)
-    for (uint64_t i = 0; i < n; ++i) out_dropped[i] = 0;
+  if (ranges.overlap()) return refuse(A3D_INVALID_PARAMETER, NAME, "an output overlaps an input or another output");
+  zero_results(out_stats, n, 4), zero_results(out_dropped, n);
   if (jobs.empty()) return A3D_OK;
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   BatchScratch scratch;  // the words: cursors (kept counts), dropped, 4 sums per job, fault; the tail: hash tables | records
-  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(KnnJob), 6 * n_jobs + 1, 0, plan.table_bytes + plan.sorted_bytes, &scratch));
-  char* d_tables = scratch.tail;
-  for (KnnJob& j : jobs) cell_sort_rebase(&j, d_tables, d_tables + plan.table_bytes);
+  A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(KnnJob), 6 * n_jobs + 1, 0, plan.tables.bytes + plan.sorted.bytes, &scratch));
+  place_parts(scratch.tail, {&plan.tables, &plan.sorted});
+  for (KnnJob& j : jobs) cell_sort_rebase(plan, &j);
   const KnnJob* d_jobs = (const KnnJob*)scratch.jobs;
   unsigned long long* d_cursor = scratch.words;
   unsigned long long* d_dropped = d_cursor + n_jobs;
@@ -801,7 +763,7 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
   unsigned long long* d_fault = d_cursor + 6 * n_jobs;
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, jobs.data(), s));
-  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, plan.table_bytes, s));  // every key word empty, every count 0
+  A3D_HIP_TRY(hipMemsetAsync(plan.tables.base, 0, plan.tables.bytes, s));  // every key word empty, every count 0
   const dim3 grid_dim((uint32_t)plan.tiles), block(CELL_THREADS);
   const uint32_t nj = (uint32_t)n_jobs;
   A3D_TRY(cell_sort_launch(d_jobs, nj, plan.tiles, grid, d_cursor, d_dropped, d_fault, s));
@@ -829,16 +791,10 @@ a3d_status a3d_point_clouds_knn_distance_device(a3d_context* ctx, const a3d_poin
   }
 #undef CO_LAUNCH
   A3D_HIP_TRY(hipGetLastError());
-  std::vector<unsigned long long> words(6 * n_jobs + 1);
-  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_cursor, words.size() * 8, hipMemcpyDeviceToHost, s));
-  // host-synchronous: the caller may free inputs and outputs right after
-  A3D_HIP_TRY(hipStreamSynchronize(s));
+  std::vector<unsigned long long> words;
+  A3D_TRY(download_words(d_cursor, 6 * n_jobs + 1, s, &words));
   A3D_REQUIRE(words[6 * n_jobs] == 0, A3D_HIP_ERROR, "a3d_point_clouds_knn_distance_device: a hash table filled up");
-  for (size_t q = 0; q < n_jobs; ++q) {
-    if (out_stats)
-      for (int w = 0; w < 4; ++w) out_stats[4 * cloud_of_job[q] + w] = words[2 * n_jobs + 4 * q + w];
-    if (out_dropped) out_dropped[cloud_of_job[q]] = words[n_jobs + q];
-  }
+  scatter_words(&words[2 * n_jobs], cloud_of_job, out_stats, 4), scatter_words(&words[n_jobs], cloud_of_job, out_dropped);
   return A3D_OK;
 }
 
@@ -849,20 +805,18 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
                                            uint64_t* out_dropped) {
   if (n == 0) return A3D_OK;
   A3D_REQUIRE(ctx && d_clouds && d_out_labels, A3D_INVALID_PARAMETER, "null argument");
-  A3D_REQUIRE(std::isfinite(radius) && radius > 0.f, A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_cluster_device: the radius must be finite and positive");
-  const float r2 = radius * radius;
-  A3D_REQUIRE(r2 > 0.f && std::isfinite(32768.0f / radius), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_cluster_device: a radius whose square is 0 in f32 (below about 1e-19)");
+  static const char NAME[] = "a3d_point_clouds_cluster_device";
+  VoxelGrid grid;
+  float r2;
+  A3D_TRY(radius_grid_from(NAME, radius, &grid, &r2, nullptr));
   A3D_REQUIRE(min_points >= 1, A3D_INVALID_PARAMETER, "a3d_point_clouds_cluster_device: min_points must be at least 1");
-  const VoxelGrid grid{radius, 0.f, 0.f, 0.f};
   std::vector<KnnJob> sort_jobs;
   std::vector<ClusterJob> jobs;
   std::vector<uint64_t> cloud_of_job;
-  std::vector<ByteRange> ranges;
+  RangeRecorder ranges;
   sort_jobs.reserve(n), jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(6 * n);
   CellSortPlan plan;
-  size_t row_bytes = 0, flag_bytes = 0;  // offsets of a job's arrays inside their parts of the scratch region, for now
+  TailPart sizes, owners, parents, flags;  // (a job's size, owner and parent lie at one offset of their three parts)
   for (uint64_t i = 0; i < n; ++i) {
     const a3d_point_cloud_view& c = d_clouds[i];
     A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
@@ -871,52 +825,38 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
     KnnJob k{};
     ClusterJob j{};
     k.points = c.points;
-    A3D_TRY(cell_sort_plan(&plan, c.len, "a3d_point_clouds_cluster_device: a cloud within one tile of 2^32 points", &k));
+    A3D_TRY(cell_sort_plan(&plan, NAME, c.len, &k));
     j.len = k.len, j.first_tile = k.first_tile, j.chunks_per_tile = k.chunks_per_tile, j.slot_mask = k.slot_mask;
-    j.parent = (uint32_t*)row_bytes, j.flags = (unsigned long long*)flag_bytes;
-    row_bytes += pad256(c.len * 4), flag_bytes += pad256((c.len + 63) / 64 * 8);
+    const size_t row_bytes = pad256(c.len * 4);
+    sizes.take(&j.size, row_bytes), owners.take(&j.owner, row_bytes), parents.take(&j.parent, row_bytes);
+    flags.take(&j.flags, pad256((c.len + 63) / 64 * 8));
     j.labels = d_out_labels[i];
     j.row_sizes = d_out_row_sizes ? d_out_row_sizes[i] : nullptr;
     j.sizes = d_out_sizes ? d_out_sizes[i] : nullptr;
     j.roots = d_out_roots ? d_out_roots[i] : nullptr;
     sort_jobs.push_back(k), jobs.push_back(j), cloud_of_job.push_back(i);
-    ranges.push_back({(uintptr_t)c.points, (uintptr_t)c.points + (uintptr_t)c.len * 12, false});
-    if (c.normals) ranges.push_back({(uintptr_t)c.normals, (uintptr_t)c.normals + (uintptr_t)c.len * 12, false});
-    for (uint32_t* out : {j.labels, j.row_sizes, j.sizes, j.roots})
-      if (out) ranges.push_back({(uintptr_t)out, (uintptr_t)out + (uintptr_t)c.len * 4, true});
+    ranges.in(c.points, c.len * 12), ranges.in(c.normals, c.len * 12);
+    for (uint32_t* out : {j.labels, j.row_sizes, j.sizes, j.roots}) ranges.out(out, c.len * 4);
   }
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_cluster_device: an output overlaps an input or another output");
-  for (uint64_t i = 0; i < n; ++i) {
-    if (out_clusters) out_clusters[i] = 0;
-    if (out_noise) out_noise[i] = 0;
-    if (out_dropped) out_dropped[i] = 0;
-  }
+  if (ranges.overlap()) return refuse(A3D_INVALID_PARAMETER, NAME, "an output overlaps an input or another output");
+  zero_results(out_clusters, n), zero_results(out_noise, n), zero_results(out_dropped, n);
   if (jobs.empty()) return A3D_OK;
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   // the table: the sort's jobs, then the cluster jobs; the words: cursors (kept counts), dropped, clusters, noise per job,
   // fault; the tail: hash tables | size | owner (these three zeroed by the one fill) | parent | records | ballot words
-  const size_t sort_table = n_jobs * sizeof(KnnJob), zeroed = plan.table_bytes + 2 * row_bytes;
+  const size_t sort_table = n_jobs * sizeof(KnnJob), zeroed = plan.tables.bytes + sizes.bytes + owners.bytes;
   std::vector<char> both(sort_table + n_jobs * sizeof(ClusterJob));
   BatchScratch scratch;
-  A3D_TRY(batch_scratch(ctx, both.size(), 4 * n_jobs + 1, plan.tiles, zeroed + row_bytes + plan.sorted_bytes + flag_bytes,
+  A3D_TRY(batch_scratch(ctx, both.size(), 4 * n_jobs + 1, plan.tiles, zeroed + parents.bytes + plan.sorted.bytes + flags.bytes,
                         &scratch));
-  char* d_tables = scratch.tail;
-  char* d_size = d_tables + plan.table_bytes;
-  char* d_owner = d_size + row_bytes;
-  char* d_parent = d_owner + row_bytes;
-  char* d_sorted = d_parent + row_bytes;
-  char* d_flags = d_sorted + plan.sorted_bytes;
+  place_parts(scratch.tail, {&plan.tables, &sizes, &owners, &parents, &plan.sorted, &flags});
   for (size_t q = 0; q < n_jobs; ++q) {
     KnnJob& k = sort_jobs[q];
     ClusterJob& j = jobs[q];
-    const size_t rows_at = (size_t)j.parent;
-    cell_sort_rebase(&k, d_tables, d_sorted);
+    cell_sort_rebase(plan, &k);
     j.table = k.table, j.sorted = k.sorted;
-    j.size = (uint32_t*)(d_size + rows_at), j.owner = (uint32_t*)(d_owner + rows_at);
-    j.parent = (uint32_t*)(d_parent + rows_at);
-    j.flags = (unsigned long long*)(d_flags + (size_t)j.flags);
+    sizes.rebase(&j.size), owners.rebase(&j.owner), parents.rebase(&j.parent), flags.rebase(&j.flags);
     k.out_counts = nullptr, k.out_qsum = j.parent;  // the scatter's CO_NONE of a dropped row: not a core row
   }
   memcpy(both.data(), sort_jobs.data(), sort_table);
@@ -931,7 +871,7 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
   uint32_t* d_tile_counts = scratch.tile_counts;
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, both.data(), s));
-  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, zeroed, s));  // every key word empty, every count, size and owner 0
+  A3D_HIP_TRY(hipMemsetAsync(plan.tables.base, 0, zeroed, s));  // every key word empty, every count, size and owner 0
   const dim3 grid_dim((uint32_t)plan.tiles), block(CELL_THREADS);
   const uint32_t nj = (uint32_t)n_jobs;
   A3D_TRY(cell_sort_launch(d_sort_jobs, nj, plan.tiles, grid, d_cursor, d_dropped, d_fault, s));
@@ -959,17 +899,12 @@ a3d_status a3d_point_clouds_cluster_device(a3d_context* ctx, const a3d_point_clo
   A3D_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(cluster_label_kernel, grid_dim, block, 0, s, d_jobs, nj);
   A3D_HIP_TRY(hipGetLastError());
-  std::vector<unsigned long long> words(4 * n_jobs + 1);
-  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_cursor, words.size() * 8, hipMemcpyDeviceToHost, s));
-  // host-synchronous: the caller may free inputs and outputs right after
-  A3D_HIP_TRY(hipStreamSynchronize(s));
+  std::vector<unsigned long long> words;
+  A3D_TRY(download_words(d_cursor, 4 * n_jobs + 1, s, &words));
   A3D_REQUIRE(words[4 * n_jobs] == 0, A3D_HIP_ERROR,
               "a3d_point_clouds_cluster_device: a hash table filled up or a union-find loop ran past its bound");
-  for (size_t q = 0; q < n_jobs; ++q) {
-    if (out_dropped) out_dropped[cloud_of_job[q]] = words[n_jobs + q];
-    if (out_clusters) out_clusters[cloud_of_job[q]] = words[2 * n_jobs + q];
-    if (out_noise) out_noise[cloud_of_job[q]] = words[3 * n_jobs + q];
-  }
+  scatter_words(&words[n_jobs], cloud_of_job, out_dropped), scatter_words(&words[2 * n_jobs], cloud_of_job, out_clusters);
+  scatter_words(&words[3 * n_jobs], cloud_of_job, out_noise);
   return A3D_OK;
 }
 

@@ -376,10 +376,11 @@ a3d_status a3d_point_clouds_segment_plane_device(a3d_context* ctx, const a3d_poi
               "a3d_point_clouds_segment_plane_device: at most 8 refinement rounds");
   std::vector<PlaneJob> jobs;
   std::vector<uint64_t> cloud_of_job;
-  std::vector<ByteRange> ranges;
-  jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(4 * n);
+  std::vector<size_t> cand_at;  // per job: the candidates of the jobs before it
+  RangeRecorder ranges;
+  jobs.reserve(n), cloud_of_job.reserve(n), cand_at.reserve(n), ranges.reserve(4 * n);
   uint64_t tiles = 0;
-  size_t cand_total = 0;  // candidates of the jobs before this one
+  size_t cand_total = 0;
   uint32_t cand_max = 0;
   for (uint64_t i = 0; i < n; ++i) {
     const a3d_point_cloud_view& c = d_clouds[i];
@@ -397,16 +398,14 @@ a3d_status a3d_point_clouds_segment_plane_device(a3d_context* ctx, const a3d_poi
     j.points = c.points, j.flags = d_out_flags[i];
     j.out_counts = d_out_counts && H ? d_out_counts[i] : nullptr;
     j.len = (uint32_t)c.len, j.n_cand = H;
-    j.triples = (const uint32_t*)cand_total;  // offsets, for now
+    cand_at.push_back(cand_total);
     cand_total += H, cand_max = std::max(cand_max, H);
     A3D_TRY(plan_tiles(c.len, PL_CHUNK, PL_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
     jobs.push_back(j), cloud_of_job.push_back(i);
-    ranges.push_back({(uintptr_t)c.points, (uintptr_t)c.points + (uintptr_t)c.len * 12, false});
-    if (c.normals) ranges.push_back({(uintptr_t)c.normals, (uintptr_t)c.normals + (uintptr_t)c.len * 12, false});
-    ranges.push_back({(uintptr_t)j.flags, (uintptr_t)j.flags + (uintptr_t)c.len * 4, true});
-    if (j.out_counts) ranges.push_back({(uintptr_t)j.out_counts, (uintptr_t)j.out_counts + (uintptr_t)H * 4, true});
+    ranges.in(c.points, c.len * 12), ranges.in(c.normals, c.len * 12);
+    ranges.out(j.flags, c.len * 4), ranges.out(j.out_counts, (uint64_t)H * 4);
   }
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+  A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER,
               "a3d_point_clouds_segment_plane_device: an output overlaps an input or another output");
   for (uint64_t i = 0; i < n; ++i) {
     for (int k = 0; k < 4; ++k) out_planes[4 * i + k] = 0.0;
@@ -430,7 +429,7 @@ a3d_status a3d_point_clouds_segment_plane_device(a3d_context* ctx, const a3d_poi
   const uint32_t* d_triples = (const uint32_t*)((const char*)scratch.jobs + jobs_bytes);
   for (size_t q = 0; q < n_jobs; ++q) {
     PlaneJob& j = jobs[q];
-    const size_t at = (size_t)j.triples;
+    const size_t at = cand_at[q];
     if (j.n_cand) memcpy(table.data() + jobs_bytes + at * 12, triples[cloud_of_job[q]], (size_t)j.n_cand * 12);
     j.triples = d_triples + 3 * at, j.counts = d_counts + at, j.cand = d_cand + PL_PLANE * at;
   }

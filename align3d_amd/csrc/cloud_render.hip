@@ -231,15 +231,10 @@ a3d_status a3d_point_cloud_render_device(a3d_context* ctx, const a3d_point_cloud
   const a3d_point_cloud_view cloud = *d_cloud;  // (len == 0: nothing is read, the fields only say what the image has)
   const uint64_t npx = width * height;
   if (d_out_index) {  // the index plane is the one output the caller owns: it may not lie over the cloud it is made from
-    std::vector<ByteRange> ranges;
-    ranges.push_back({(uintptr_t)d_out_index, (uintptr_t)d_out_index + (uintptr_t)npx * 4, true});
-    const uintptr_t len = (uintptr_t)cloud.len;
-    if (len) {
-      ranges.push_back({(uintptr_t)cloud.points, (uintptr_t)cloud.points + len * 12, false});
-      if (cloud.normals) ranges.push_back({(uintptr_t)cloud.normals, (uintptr_t)cloud.normals + len * 12, false});
-      if (d_colors) ranges.push_back({(uintptr_t)d_colors, (uintptr_t)d_colors + len * 3, false});
-    }
-    A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+    RangeRecorder ranges;
+    ranges.out(d_out_index, npx * 4);
+    ranges.in(cloud.points, cloud.len * 12), ranges.in(cloud.normals, cloud.len * 12), ranges.in(d_colors, cloud.len * 3);
+    A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER,
                 "a3d_point_cloud_render_device: the index plane overlaps the cloud");
   }
   A3D_HIP_TRY(hipSetDevice(ctx->device));

@@ -149,7 +149,7 @@ a3d_status a3d_point_clouds_transform_device(a3d_context* ctx, const a3d_point_c
   if (n == 0) return A3D_OK;
   A3D_REQUIRE(ctx && d_clouds && d_out_points, A3D_INVALID_PARAMETER, "null argument");
   std::vector<XformJob> jobs;
-  std::vector<ByteRange> ranges;
+  RangeRecorder ranges;
   jobs.reserve(n), ranges.reserve(4 * n);
   for (uint64_t i = 0; i < n; ++i) {
     const a3d_point_cloud_view& c = d_clouds[i];
@@ -165,17 +165,11 @@ a3d_status a3d_point_clouds_transform_device(a3d_context* ctx, const a3d_point_c
     if (poses_host) j.has_pose = 1, j.pose = pose_from_c(&poses_host[i]);
     jobs.push_back(j);
     // an output that is exactly its own input (in place) stands for both; everything else must be disjoint
-    const uintptr_t bytes = (uintptr_t)c.len * 12;
-    const uintptr_t ip = (uintptr_t)j.points, op = (uintptr_t)j.out_points;
-    if (ip != op) ranges.push_back({ip, ip + bytes, false});
-    ranges.push_back({op, op + bytes, true});
-    if (out_normals) {
-      const uintptr_t in = (uintptr_t)j.normals, on = (uintptr_t)j.out_normals;
-      if (in != on) ranges.push_back({in, in + bytes, false});
-      ranges.push_back({on, on + bytes, true});
-    }
+    if (j.points != j.out_points) ranges.in(j.points, c.len * 12);
+    if (j.normals != j.out_normals) ranges.in(j.normals, c.len * 12);
+    ranges.out(j.out_points, c.len * 12), ranges.out(j.out_normals, c.len * 12);
   }
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+  A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER,
               "a3d_point_clouds_transform_device: an output overlaps an input or another output (only output i == input i "
               "is allowed)");
   return run_jobs(ctx, jobs, points_per_thread_setting());
@@ -191,7 +185,7 @@ a3d_status a3d_point_clouds_merge_rgb_device(a3d_context* ctx, const a3d_point_c
   }
   A3D_REQUIRE(ctx && d_clouds && d_out_points && out_len, A3D_INVALID_PARAMETER, "null argument");
   std::vector<XformJob> jobs;
-  std::vector<ByteRange> ranges;
+  RangeRecorder ranges;
   jobs.reserve(n), ranges.reserve(3 * n + 3);
   uint64_t total = 0;
   for (uint64_t i = 0; i < n; ++i) {
@@ -209,10 +203,7 @@ a3d_status a3d_point_clouds_merge_rgb_device(a3d_context* ctx, const a3d_point_c
     j.len = (uint32_t)c.len;
     if (poses_host) j.has_pose = 1, j.pose = pose_from_c(&poses_host[i]);
     jobs.push_back(j);
-    const uintptr_t bytes = (uintptr_t)c.len * 12;
-    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + bytes, false});
-    if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + bytes, false});
-    if (j.colors) ranges.push_back({(uintptr_t)j.colors, (uintptr_t)j.colors + (uintptr_t)c.len * 3, false});
+    ranges.in(j.points, c.len * 12), ranges.in(j.normals, c.len * 12), ranges.in(j.colors, c.len * 3);
     total += c.len;
   }
   if (capacity < total) {
@@ -221,10 +212,8 @@ a3d_status a3d_point_clouds_merge_rgb_device(a3d_context* ctx, const a3d_point_c
               (unsigned long long)capacity, (unsigned long long)total);
     return A3D_INVALID_PARAMETER;
   }
-  ranges.push_back({(uintptr_t)d_out_points, (uintptr_t)d_out_points + total * 12, true});
-  if (d_out_normals) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + total * 12, true});
-  if (d_out_colors) ranges.push_back({(uintptr_t)d_out_colors, (uintptr_t)d_out_colors + total * 3, true});
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+  ranges.out(d_out_points, total * 12), ranges.out(d_out_normals, total * 12), ranges.out(d_out_colors, total * 3);
+  A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER,
               "a3d_point_clouds_merge_device: the output overlaps an input (or its own normals or colours)");
   A3D_TRY(run_jobs(ctx, jobs, points_per_thread_setting()));
   *out_len = total;

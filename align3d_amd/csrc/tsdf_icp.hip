@@ -134,10 +134,9 @@ a3d_status a3d_tsdf_volume_sample_device(a3d_tsdf_volume* volume, const float* d
   A3D_REQUIRE(d_queries && d_out_distance && d_out_normals, A3D_INVALID_PARAMETER, "null argument");
   A3D_REQUIRE(m < (1ull << 31), A3D_INVALID_PARAMETER, "a3d_tsdf_volume_sample_device: 2^31 queries or more");
   {
-    std::vector<ByteRange> ranges{{(uintptr_t)d_queries, (uintptr_t)d_queries + (uintptr_t)m * 12, false},
-                                  {(uintptr_t)d_out_distance, (uintptr_t)d_out_distance + (uintptr_t)m * 4, true},
-                                  {(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + (uintptr_t)m * 12, true}};
-    A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+    RangeRecorder ranges;
+    ranges.in(d_queries, m * 12), ranges.out(d_out_distance, m * 4), ranges.out(d_out_normals, m * 12);
+    A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER,
                 "a3d_tsdf_volume_sample_device: the outputs overlap each other or the queries");
   }
   a3d_context* ctx = volume->ctx;

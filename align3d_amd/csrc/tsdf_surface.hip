@@ -266,15 +266,13 @@ a3d_status a3d_tsdf_volume_extract_surface(a3d_tsdf_volume* volume, uint64_t min
   const bool count_only = !d_out_points && !d_out_faces;
   {
     // what the call may write: the first min(capacity, 2^32 - 2) elements of each output
-    const uintptr_t vcap = (uintptr_t)std::min<uint64_t>(vertex_capacity, SF_MAX_COUNT - 1);
-    const uintptr_t fcap = (uintptr_t)std::min<uint64_t>(face_capacity, SF_MAX_COUNT - 1);
-    std::vector<ByteRange> ranges;
-    ranges.push_back({(uintptr_t)volume->block, (uintptr_t)volume->block + volume->used_bytes, false});
-    if (d_out_points && vcap) ranges.push_back({(uintptr_t)d_out_points, (uintptr_t)d_out_points + vcap * 12, true});
-    if (d_out_normals && vcap) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + vcap * 12, true});
-    if (d_out_colors && vcap) ranges.push_back({(uintptr_t)d_out_colors, (uintptr_t)d_out_colors + vcap * 3, true});
-    if (d_out_faces && fcap) ranges.push_back({(uintptr_t)d_out_faces, (uintptr_t)d_out_faces + fcap * 12, true});
-    A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+    const uint64_t vcap = std::min<uint64_t>(vertex_capacity, SF_MAX_COUNT - 1);
+    const uint64_t fcap = std::min<uint64_t>(face_capacity, SF_MAX_COUNT - 1);
+    RangeRecorder ranges;
+    ranges.in(volume->block, volume->used_bytes);
+    ranges.out(d_out_points, vcap * 12), ranges.out(d_out_normals, vcap * 12), ranges.out(d_out_colors, vcap * 3);
+    ranges.out(d_out_faces, fcap * 12);
+    A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER,
                 "a3d_tsdf_volume_extract_surface: an output overlaps the volume or another output");
   }
   a3d_context* ctx = volume->ctx;

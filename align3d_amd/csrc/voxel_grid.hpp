@@ -4,7 +4,10 @@
 //   c_k   = floorf((p_k - o_k) / v)            dropped unless every c_k is finite and in [-2^20, 2^20)
 //   key   = (c_x + 2^20) << 42 | (c_y + 2^20) << 21 | (c_z + 2^20)
 //   ctr_k = (c_k + 0.5f) * v + o_k,  d_k = p_k - ctr_k,  dist = (d_x * d_x + d_y * d_y) + d_z * d_z   (never NaN, may be +inf)
+// The host's checks of a grid's parameters and the size of a table are here too, once for every entry point.
 #pragma once
+#include <cmath>
+
 #include "cloud_batch.hpp"
 
 namespace a3d {
@@ -21,6 +24,40 @@ static_assert(sizeof(VoxelSlot) == 16, "VoxelSlot layout");
 struct VoxelGrid {
   float v, ox, oy, oz;
 };
+
+// The grid of pitch `voxel_size` anchored at `origin` (null: the zero point), as the entry point `name` accepts it.
+inline a3d_status voxel_grid_from(const char* name, float voxel_size, const float origin[3], VoxelGrid* grid) {
+  if (!(std::isfinite(voxel_size) && voxel_size > 0.f))
+    return refuse(A3D_INVALID_PARAMETER, name, "the voxel size must be finite and positive");
+  *grid = VoxelGrid{voxel_size, 0.f, 0.f, 0.f};
+  if (origin) {
+    if (!(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2])))
+      return refuse(A3D_INVALID_PARAMETER, name, "the origin must be finite");
+    grid->ox = origin[0], grid->oy = origin[1], grid->oz = origin[2];
+  }
+  return A3D_OK;
+}
+
+// The neighbour grid of pitch `radius` at the zero point, with r2 = radius^2 and s = 32768 / radius (the distance
+// lattice; `s` may be null), as the entry point `name` accepts it.
+inline a3d_status radius_grid_from(const char* name, float radius, VoxelGrid* grid, float* r2, float* s) {
+  if (!(std::isfinite(radius) && radius > 0.f))
+    return refuse(A3D_INVALID_PARAMETER, name, "the radius must be finite and positive");
+  const float lattice = 32768.0f / radius;
+  *r2 = radius * radius;
+  if (!(*r2 > 0.f && std::isfinite(lattice)))
+    return refuse(A3D_INVALID_PARAMETER, name, "a radius whose square is 0 in f32 (below about 1e-19)");
+  if (s) *s = lattice;
+  *grid = VoxelGrid{radius, 0.f, 0.f, 0.f};
+  return A3D_OK;
+}
+
+// Slots of a hash table that holds up to `len` keys: the power of two that is at least 2 * len, and at least `least`.
+inline uint64_t table_slots(uint64_t len, uint64_t least = 2) {
+  uint64_t slots = least;
+  while (slots < 2 * len) slots <<= 1;
+  return slots;
+}
 
 #ifdef __HIPCC__
 // The cell key of a point and (with_dist) its squared distance to the cell centre; false = the point is dropped.

@@ -758,10 +758,8 @@ void adopt_table(a3d_voxel_map* m, void* block, size_t block_bytes, uint64_t slo
 
 // Makes sure the table has at least 2 * (cells + incoming) slots; `fault` is the call's guard word in scratch.
 a3d_status ensure_slots(a3d_voxel_map* m, uint64_t incoming, unsigned long long* d_fault) {
-  const uint64_t need = 2 * (m->cells + incoming);
-  if (m->block && m->slots >= need) return A3D_OK;
-  uint64_t slots = 64;
-  while (slots < need || slots < 2 * m->reserve_cells) slots <<= 1;
+  if (m->block && m->slots >= 2 * (m->cells + incoming)) return A3D_OK;
+  const uint64_t slots = table_slots(std::max<uint64_t>(m->cells + incoming, m->reserve_cells), 64);
   a3d_context* ctx = m->ctx;
   const TableLayout lay = table_layout(slots, m->with_normals, m->with_colors, m->mean);
   const size_t bytes = lay.end + 256;
@@ -818,14 +816,8 @@ extern "C" {
 a3d_status a3d_voxel_map_new_rgb(a3d_context* ctx, float voxel_size, const float origin[3], int with_normals,
                                  int with_colors, uint64_t reserve_cells, a3d_voxel_map** out) {
   A3D_REQUIRE(ctx && out, A3D_INVALID_PARAMETER, "null argument");
-  A3D_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.f, A3D_INVALID_PARAMETER,
-              "a3d_voxel_map_new: the voxel size must be finite and positive");
-  VoxelGrid grid{voxel_size, 0.f, 0.f, 0.f};
-  if (origin) {
-    A3D_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), A3D_INVALID_PARAMETER,
-                "a3d_voxel_map_new: the origin must be finite");
-    grid.ox = origin[0], grid.oy = origin[1], grid.oz = origin[2];
-  }
+  VoxelGrid grid;
+  A3D_TRY(voxel_grid_from("a3d_voxel_map_new", voxel_size, origin, &grid));
   A3D_REQUIRE(reserve_cells < (1ull << 32), A3D_INVALID_PARAMETER, "a3d_voxel_map_new: a reservation of 2^32 cells or more");
   a3d_voxel_map* m = new a3d_voxel_map();
   m->ctx = ctx, m->grid = grid, m->with_normals = with_normals != 0, m->with_colors = with_colors != 0;
@@ -877,8 +869,7 @@ a3d_status a3d_voxel_map_insert_rgb(a3d_voxel_map* map, const a3d_point_cloud_vi
     incoming += c.len;
     jobs.push_back(j), cloud_of_job.push_back(i);
   }
-  if (out_dropped)
-    for (uint64_t i = 0; i < n; ++i) out_dropped[i] = 0;
+  zero_results(out_dropped, n);
   if (jobs.empty()) {
     if (out_cells) *out_cells = map->cells;
     return A3D_OK;
@@ -965,16 +956,11 @@ a3d_status a3d_voxel_map_extract_mean(a3d_voxel_map* map, float* d_out_points, f
   A3D_REQUIRE(!d_out_normals || map->with_normals, A3D_MISSING_FIELD, "a3d_voxel_map_extract: the map has no normals");
   A3D_REQUIRE(!d_out_colors || map->with_colors, A3D_MISSING_FIELD, "a3d_voxel_map_extract: the map has no colours");
   {  // the outputs as the caller declared them: `capacity` rows each (no map has 2^32 cells)
-    const uintptr_t rows = (uintptr_t)std::min<uint64_t>(capacity, 1ull << 32);
-    std::vector<ByteRange> ranges;
-    if (rows) {
-      ranges.push_back({(uintptr_t)d_out_points, (uintptr_t)d_out_points + rows * 12, true});
-      if (d_out_normals) ranges.push_back({(uintptr_t)d_out_normals, (uintptr_t)d_out_normals + rows * 12, true});
-      if (d_out_index) ranges.push_back({(uintptr_t)d_out_index, (uintptr_t)d_out_index + rows * 4, true});
-      if (d_out_colors) ranges.push_back({(uintptr_t)d_out_colors, (uintptr_t)d_out_colors + rows * 3, true});
-      if (d_out_counts) ranges.push_back({(uintptr_t)d_out_counts, (uintptr_t)d_out_counts + rows * 4, true});
-    }
-    A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER, "a3d_voxel_map_extract: the outputs overlap one another");
+    const uint64_t rows = std::min<uint64_t>(capacity, 1ull << 32);
+    RangeRecorder ranges;
+    ranges.out(d_out_points, rows * 12), ranges.out(d_out_normals, rows * 12), ranges.out(d_out_index, rows * 4);
+    ranges.out(d_out_colors, rows * 3), ranges.out(d_out_counts, rows * 4);
+    A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER, "a3d_voxel_map_extract: the outputs overlap one another");
   }
   *out_len = map->cells;
   if (capacity < map->cells) {
@@ -1075,8 +1061,7 @@ a3d_status a3d_voxel_map_retain(a3d_voxel_map* map, const float box_min[3], cons
   unsigned long long* d_out = (unsigned long long*)((char*)d_marks + marks_bytes);  // [n_all] translations, then the fault word
   unsigned long long* d_fault = d_out + n_all;
   // the new table: room for every old cell (k is known on the device only until the wait); its cell count at the end
-  uint64_t min_slots = 64;
-  while (min_slots < 2 * map->reserve_cells) min_slots <<= 1;
+  const uint64_t min_slots = table_slots(map->reserve_cells, 64);
   const uint64_t max_slots = retained_slots(map->cells, min_slots);
   const size_t bytes = table_layout(max_slots, map->with_normals, map->with_colors, map->mean).end + 256;
   void* block = nullptr;

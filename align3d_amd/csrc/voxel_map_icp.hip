@@ -199,10 +199,9 @@ a3d_status a3d_voxel_map_nearest_device(a3d_voxel_map* map, const float* d_queri
   A3D_REQUIRE(d_queries && d_out_seq && d_out_dist2, A3D_INVALID_PARAMETER, "null argument");
   A3D_REQUIRE(m < (1ull << 31), A3D_INVALID_PARAMETER, "a3d_voxel_map_nearest_device: 2^31 queries or more");
   {
-    std::vector<ByteRange> ranges{{(uintptr_t)d_queries, (uintptr_t)d_queries + (uintptr_t)m * 12, false},
-                                  {(uintptr_t)d_out_seq, (uintptr_t)d_out_seq + (uintptr_t)m * 4, true},
-                                  {(uintptr_t)d_out_dist2, (uintptr_t)d_out_dist2 + (uintptr_t)m * 4, true}};
-    A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
+    RangeRecorder ranges;
+    ranges.in(d_queries, m * 12), ranges.out(d_out_seq, m * 4), ranges.out(d_out_dist2, m * 4);
+    A3D_REQUIRE(!ranges.overlap(), A3D_INVALID_PARAMETER,
                 "a3d_voxel_map_nearest_device: the outputs overlap each other or the queries");
   }
   A3D_TRY(check_slots(map));

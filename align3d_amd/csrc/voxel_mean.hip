@@ -470,91 +470,49 @@ a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_
                                               uint32_t* const* d_out_index, uint32_t* const* d_out_counts,
                                               const uint64_t* capacities, uint64_t* out_lens, uint64_t* out_dropped) {
   if (n == 0) return A3D_OK;
-  A3D_REQUIRE(ctx && d_clouds && d_out_points && capacities && out_lens, A3D_INVALID_PARAMETER, "null argument");
-  A3D_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.f, A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_voxel_mean_device: the voxel size must be finite and positive");
-  VoxelGrid grid{voxel_size, 0.f, 0.f, 0.f};
-  if (origin) {
-    A3D_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), A3D_INVALID_PARAMETER,
-                "a3d_point_clouds_voxel_mean_device: the origin must be finite");
-    grid.ox = origin[0], grid.oy = origin[1], grid.oz = origin[2];
-  }
+  static const char NAME[] = "a3d_point_clouds_voxel_mean_device";
+  if (!(ctx && d_clouds && d_out_points && capacities && out_lens)) return refuse(A3D_INVALID_PARAMETER, NAME, "null argument");
+  VoxelGrid grid;
+  A3D_TRY(voxel_grid_from(NAME, voxel_size, origin, &grid));
   const MeanParams prm = voxel_mean_params(voxel_size);
+  const CompactArgs args{d_clouds, d_colors, d_out_points, d_out_normals, d_out_colors, d_out_index, capacities};
   std::vector<MeanJob> jobs;
   std::vector<uint64_t> cloud_of_job;
-  std::vector<ByteRange> ranges;
+  RangeRecorder ranges;
   jobs.reserve(n), cloud_of_job.reserve(n), ranges.reserve(8 * n);
   uint64_t tiles = 0;
-  // offsets of a job's arrays inside their parts of the scratch region, for now
-  size_t flag_bytes = 0, row_bytes = 0, sorted_bytes = 0, table_bytes = 0, spill_bytes = 0;
+  TailPart flags, rows, sorted, tables, spill;
   for (uint64_t i = 0; i < n; ++i) {
-    const a3d_point_cloud_view& c = d_clouds[i];
-    A3D_REQUIRE(c.len < (1ull << 32), A3D_INVALID_PARAMETER, "a cloud of 2^32 points or more");
-    if (c.len == 0) continue;  // yields no points; its pointers may be null
-    A3D_REQUIRE(c.points && d_out_points[i], A3D_INVALID_PARAMETER, "null points or output pointer");
-    float* out_normals = d_out_normals ? d_out_normals[i] : nullptr;
-    A3D_REQUIRE(!out_normals || c.normals, A3D_MISSING_FIELD, "cloud has no normals");
-    uint8_t* out_colors = d_out_colors ? d_out_colors[i] : nullptr;
-    const uint8_t* colors = out_colors && d_colors ? d_colors[i] : nullptr;
-    A3D_REQUIRE(!out_colors || colors, A3D_MISSING_FIELD, "cloud has no colours");
+    const uint64_t len = d_clouds[i].len;
+    if (len >= (1ull << 32)) return refuse(A3D_INVALID_PARAMETER, NAME, "a cloud of 2^32 points or more");
+    if (len == 0) continue;  // yields no points; its pointers may be null
     MeanJob j{};
-    j.points = c.points, j.normals = out_normals ? c.normals : nullptr, j.colors = colors;
-    j.out_points = d_out_points[i], j.out_normals = out_normals, j.out_colors = out_colors;
-    j.out_index = d_out_index ? d_out_index[i] : nullptr;
-    j.out_counts = d_out_counts ? d_out_counts[i] : nullptr;
-    j.capacity = capacities[i];
-    j.len = (uint32_t)c.len;
-    A3D_TRY(plan_tiles(c.len, VM_CHUNK, VM_MAX_TILES, &tiles, &j.first_tile, &j.chunks_per_tile));
+    A3D_TRY(compact_front(NAME, args, i, true, "null points or output pointer", VM_CHUNK, VM_MAX_TILES, &tiles, &ranges, &j));
     j.n_tiles = (uint32_t)tiles - j.first_tile;
-    // the kernels' 32-bit point positions run up to one tile span past len
-    A3D_REQUIRE(c.len + (uint64_t)j.chunks_per_tile * VM_CHUNK < (1ull << 32), A3D_INVALID_PARAMETER,
-                "a3d_point_clouds_voxel_mean_device: a cloud within one tile of 2^32 points");
-    uint64_t slots = 2;
-    while (slots < 2 * c.len) slots <<= 1;
+    j.out_counts = d_out_counts ? d_out_counts[i] : nullptr;
+    ranges.out(j.out_counts, std::min<uint64_t>(len, j.capacity) * 4);
+    const uint64_t slots = table_slots(len);
     j.slot_mask = slots - 1;
-    const size_t groups = (c.len + 63) / 64;
-    j.flags = (unsigned long long*)flag_bytes, j.row_at = (uint32_t*)row_bytes, j.sorted = (CellRecord*)sorted_bytes;
-    j.table = (VoxelSlot*)table_bytes, j.spill = (VmSpill*)spill_bytes;
-    flag_bytes += pad256(groups * 8), row_bytes += pad256(c.len * 4), sorted_bytes += pad256(c.len * sizeof(CellRecord));
-    table_bytes += slots * sizeof(VoxelSlot), spill_bytes += pad256(groups * sizeof(VmSpill));
+    const size_t groups = (len + 63) / 64;
+    flags.take(&j.flags, pad256(groups * 8)), rows.take(&j.row_at, pad256(len * 4));
+    sorted.take(&j.sorted, pad256(len * sizeof(CellRecord))), tables.take(&j.table, slots * sizeof(VoxelSlot));
+    spill.take(&j.spill, pad256(groups * sizeof(VmSpill)));
     jobs.push_back(j), cloud_of_job.push_back(i);
-    // what the call may write is the first min(len, capacity) elements of each output
-    const uintptr_t in_bytes = (uintptr_t)c.len * 12, kept = (uintptr_t)std::min<uint64_t>(c.len, j.capacity);
-    ranges.push_back({(uintptr_t)j.points, (uintptr_t)j.points + in_bytes, false});
-    if (j.normals) ranges.push_back({(uintptr_t)j.normals, (uintptr_t)j.normals + in_bytes, false});
-    if (j.colors) ranges.push_back({(uintptr_t)j.colors, (uintptr_t)j.colors + (uintptr_t)c.len * 3, false});
-    if (kept) {
-      ranges.push_back({(uintptr_t)j.out_points, (uintptr_t)j.out_points + kept * 12, true});
-      if (out_normals) ranges.push_back({(uintptr_t)out_normals, (uintptr_t)out_normals + kept * 12, true});
-      if (j.out_index) ranges.push_back({(uintptr_t)j.out_index, (uintptr_t)j.out_index + kept * 4, true});
-      if (j.out_counts) ranges.push_back({(uintptr_t)j.out_counts, (uintptr_t)j.out_counts + kept * 4, true});
-      if (out_colors) ranges.push_back({(uintptr_t)out_colors, (uintptr_t)out_colors + kept * 3, true});
-    }
   }
-  A3D_REQUIRE(!outputs_overlap(ranges), A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_voxel_mean_device: an output overlaps an input or another output (there is no in-place "
-              "form)");
-  for (uint64_t i = 0; i < n; ++i) out_lens[i] = 0;
-  if (out_dropped)
-    for (uint64_t i = 0; i < n; ++i) out_dropped[i] = 0;
+  if (ranges.overlap())
+    return refuse(A3D_INVALID_PARAMETER, NAME, "an output overlaps an input or another output (there is no in-place form)");
+  zero_results(out_lens, n), zero_results(out_dropped, n);
   if (jobs.empty()) return A3D_OK;
   const size_t n_jobs = jobs.size();
   A3D_HIP_TRY(hipSetDevice(ctx->device));
   // the words: lens, dropped, cursor, fault; the tail: ballot words | row numbers | records | hash tables | accumulators
   BatchScratch scratch;
   A3D_TRY(batch_scratch(ctx, n_jobs * sizeof(MeanJob), 3 * n_jobs + 1, tiles,
-                        flag_bytes + row_bytes + sorted_bytes + table_bytes + spill_bytes, &scratch));
-  char* d_flags = scratch.tail;
-  char* d_rows = d_flags + flag_bytes;
-  char* d_sorted = d_rows + row_bytes;
-  char* d_tables = d_sorted + sorted_bytes;
-  char* d_spill = d_tables + table_bytes;
+                        flags.bytes + rows.bytes + sorted.bytes + tables.bytes + spill.bytes, &scratch));
+  place_parts(scratch.tail, {&flags, &rows, &sorted, &tables, &spill});
   for (MeanJob& j : jobs) {
-    j.flags = (unsigned long long*)(d_flags + (size_t)j.flags);
-    j.row_at = (uint32_t*)(d_rows + (size_t)j.row_at);
-    j.sorted = (CellRecord*)(d_sorted + (size_t)j.sorted);
-    j.table = (VoxelSlot*)(d_tables + (size_t)j.table);
-    j.spill = (VmSpill*)(d_spill + (size_t)j.spill);
+    flags.rebase(&j.flags), rows.rebase(&j.row_at), sorted.rebase(&j.sorted);
+    tables.rebase(&j.table), spill.rebase(&j.spill);
   }
   const MeanJob* d_jobs = (const MeanJob*)scratch.jobs;
   unsigned long long* d_lens = scratch.words;
@@ -564,7 +522,7 @@ a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_
   uint32_t* d_tile_counts = scratch.tile_counts;
   hipStream_t s = ctx->stream;
   A3D_TRY(batch_upload(scratch, jobs.data(), s));
-  A3D_HIP_TRY(hipMemsetAsync(d_tables, 0, table_bytes + spill_bytes, s));  // every slot empty, every accumulator zero
+  A3D_HIP_TRY(hipMemsetAsync(tables.base, 0, tables.bytes + spill.bytes, s));  // every slot empty, every accumulator zero
   const dim3 grid_dim((uint32_t)tiles), block(VM_THREADS);
   hipLaunchKernelGGL(vmean_count_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, d_dropped, d_fault);
   A3D_HIP_TRY(hipGetLastError());
@@ -581,20 +539,10 @@ a3d_status a3d_point_clouds_voxel_mean_device(a3d_context* ctx, const a3d_point_
   hipLaunchKernelGGL(vmean_spill_kernel, grid_dim, block, 0, s, d_jobs, (uint32_t)n_jobs, grid, prm,
                      (const unsigned long long*)d_lens);
   A3D_HIP_TRY(hipGetLastError());
-  std::vector<unsigned long long> words(3 * n_jobs + 1);
-  A3D_HIP_TRY(hipMemcpyAsync(words.data(), d_lens, words.size() * 8, hipMemcpyDeviceToHost, s));
-  // host-synchronous: the caller may free inputs and outputs right after
-  A3D_HIP_TRY(hipStreamSynchronize(s));
+  std::vector<unsigned long long> words;
+  A3D_TRY(download_words(d_lens, 3 * n_jobs + 1, s, &words));
   A3D_REQUIRE(words[3 * n_jobs] == 0, A3D_HIP_ERROR, "a3d_point_clouds_voxel_mean_device: a hash table filled up");
-  bool over = false;
-  for (size_t k = 0; k < n_jobs; ++k) {
-    out_lens[cloud_of_job[k]] = words[k];
-    if (out_dropped) out_dropped[cloud_of_job[k]] = words[n_jobs + k];
-    over |= words[k] > jobs[k].capacity;
-  }
-  A3D_REQUIRE(!over, A3D_INVALID_PARAMETER,
-              "a3d_point_clouds_voxel_mean_device: a capacity is smaller than its cloud's rows (nothing was written)");
-  return A3D_OK;
+  return compact_finish(NAME, "rows", jobs, cloud_of_job, words.data(), out_lens, out_dropped);
 }
 
 }  // extern "C"

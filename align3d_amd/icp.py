@@ -1,5 +1,6 @@
 """ImageIcp, MultiscaleAlign, Icp — the reference's alignment API (src/icp/*.rs) over the C ABI."""
 import ctypes as C
+import types
 
 import numpy as np
 
@@ -544,52 +545,18 @@ class DevicePointCloud:
         if not clouds:
             return [], ([] if return_index else None)
         clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "voxel_downsample")
-        o = None
-        if origin is not None:
-            o = np.ascontiguousarray(origin, np.float32).reshape(-1)
-            if o.size != 3:
-                raise _abi.InvalidParameter("voxel_downsample: the origin has three coordinates")
-            o = (C.c_float * 3)(*o.tolist())
-        n, outs, d_index = len(clouds), [], []
-        try:
-            for c in clouds:
-                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
-                if return_index:
-                    d_index.append(ctx.malloc(max(1, c.n) * 4))
-            lens = (C.c_uint64 * n)()
-            if any(c.d_colors is not None for c in clouds):
-                _abi.check(
-                    ctx.lib.a3d_point_clouds_voxel_downsample_rgb_device(
-                        ctx.handle, DevicePointCloud._views(clouds), DevicePointCloud._colors_array(clouds), n,
-                        float(voxel_size), o, (C.c_void_p * n)(*[x.d_points for x in outs]),
-                        (C.c_void_p * n)(*[x.d_normals for x in outs]), DevicePointCloud._colors_array(outs),
-                        (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens,
-                        None),
-                    "a3d_point_clouds_voxel_downsample_rgb_device",
-                )
-            else:
-                _abi.check(
-                    ctx.lib.a3d_point_clouds_voxel_downsample_device(
-                        ctx.handle, DevicePointCloud._views(clouds), n, float(voxel_size), o,
-                        (C.c_void_p * n)(*[x.d_points for x in outs]), (C.c_void_p * n)(*[x.d_normals for x in outs]),
-                        (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens,
-                        None),
-                    "a3d_point_clouds_voxel_downsample_device",
-                )
-            for x, k in zip(outs, lens):
-                x.n = int(k)
-            index = None
-            if return_index:
-                index = [ctx.to_host(d, np.empty(x.n, np.uint32)) if x.n else np.empty(0, np.uint32)
-                         for d, x in zip(d_index, outs)]
-        except BaseException:
-            for x in outs:
-                x.free()
-            raise
-        finally:
-            for d in d_index:
-                ctx.free(d)
-        return outs, index
+        o = DevicePointCloud._origin3(origin)
+
+        def call(a):  # (the plain entry point forwards to this one with NULL colours)
+            _abi.check(
+                ctx.lib.a3d_point_clouds_voxel_downsample_rgb_device(
+                    ctx.handle, a.views, a.colors, a.n, float(voxel_size), o, a.out_points, a.out_normals, a.out_colors,
+                    a.side["index"], a.capacities, a.lens, None),
+                "a3d_point_clouds_voxel_downsample_rgb_device",
+            )
+
+        outs, host = DevicePointCloud._compact(ctx, clouds, index=return_index, call=call)
+        return outs, host["index"]
 
     @staticmethod
     def _origin3(origin):
@@ -601,49 +568,61 @@ class DevicePointCloud:
         return (C.c_float * 3)(*o.tolist())
 
     @staticmethod
+    def _compact(ctx, clouds, call, **side):
+        """What the wrappers of the compacting calls share (voxel_downsample in both modes, select_many): allocates one
+        output per cloud, shaped like its input, and for each name of `side` given as true one u32 device buffer per
+        cloud; runs call(a), where `a` holds the call's ctypes arrays (n, views, colors, out_points, out_normals,
+        out_colors, capacities, lens, and side[name]: the array of that side's buffers, or None); sets each output's
+        length from lens.  Returns (outputs, {name: [uint32 host arrays of the output's length] or None}).  The outputs are
+        freed if anything fails, the side buffers always."""
+        n, outs = len(clouds), []
+        d_side = {name: [] for name, wanted in side.items() if wanted}
+        try:
+            for c in clouds:
+                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
+                for buffers in d_side.values():
+                    buffers.append(ctx.malloc(max(1, c.n) * 4))
+            colours = any(c.d_colors is not None for c in clouds)
+            a = types.SimpleNamespace(
+                n=n, views=DevicePointCloud._views(clouds), colors=DevicePointCloud._colors_array(clouds) if colours else None,
+                out_points=(C.c_void_p * n)(*[x.d_points for x in outs]),
+                out_normals=(C.c_void_p * n)(*[x.d_normals for x in outs]),
+                out_colors=DevicePointCloud._colors_array(outs) if colours else None,
+                side={name: (C.c_void_p * n)(*d_side[name]) if name in d_side else None for name in side},
+                capacities=(C.c_uint64 * n)(*[c.n for c in clouds]), lens=(C.c_uint64 * n)())
+            call(a)
+            for x, k in zip(outs, a.lens):
+                x.n = int(k)
+            host = {name: [ctx.to_host(d, np.empty(x.n, np.uint32)) if x.n else np.empty(0, np.uint32)
+                           for d, x in zip(d_side[name], outs)] if name in d_side else None for name in side}
+        except BaseException:
+            for x in outs:
+                x.free()
+            raise
+        finally:
+            for buffers in d_side.values():
+                for d in buffers:
+                    ctx.free(d)
+        return outs, host
+
+    @staticmethod
     def _voxel_mean(clouds, voxel_size, origin, return_index, return_counts):
         """The mode="mean" half of _voxel_downsample: one a3d_point_clouds_voxel_mean_device call."""
         if not clouds:
             return [], ([] if return_index else None), ([] if return_counts else None)
         clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "voxel_downsample")
         o = DevicePointCloud._origin3(origin)
-        n, outs, d_index, d_counts = len(clouds), [], [], []
-        try:
-            for c in clouds:
-                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
-                if return_index:
-                    d_index.append(ctx.malloc(max(1, c.n) * 4))
-                if return_counts:
-                    d_counts.append(ctx.malloc(max(1, c.n) * 4))
-            lens = (C.c_uint64 * n)()
-            colours = any(c.d_colors is not None for c in clouds)
+
+        def call(a):
             _abi.check(
                 ctx.lib.a3d_point_clouds_voxel_mean_device(
-                    ctx.handle, DevicePointCloud._views(clouds), DevicePointCloud._colors_array(clouds) if colours else None,
-                    n, float(voxel_size), o, (C.c_void_p * n)(*[x.d_points for x in outs]),
-                    (C.c_void_p * n)(*[x.d_normals for x in outs]), DevicePointCloud._colors_array(outs) if colours else None,
-                    (C.c_void_p * n)(*d_index) if return_index else None,
-                    (C.c_void_p * n)(*d_counts) if return_counts else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens,
-                    None),
+                    ctx.handle, a.views, a.colors, a.n, float(voxel_size), o, a.out_points, a.out_normals, a.out_colors,
+                    a.side["index"], a.side["counts"], a.capacities, a.lens, None),
                 "a3d_point_clouds_voxel_mean_device",
             )
-            for x, k in zip(outs, lens):
-                x.n = int(k)
 
-            def download(buffers):
-                return [ctx.to_host(d, np.empty(x.n, np.uint32)) if x.n else np.empty(0, np.uint32)
-                        for d, x in zip(buffers, outs)]
-
-            index = download(d_index) if return_index else None
-            counts = download(d_counts) if return_counts else None
-        except BaseException:
-            for x in outs:
-                x.free()
-            raise
-        finally:
-            for d in d_index + d_counts:
-                ctx.free(d)
-        return outs, index, counts
+        outs, host = DevicePointCloud._compact(ctx, clouds, index=return_index, counts=return_counts, call=call)
+        return outs, host["index"], host["counts"]
 
     @staticmethod
     def voxel_downsample_many(clouds, voxel_size, origin=None, mode="nearest"):
@@ -791,7 +770,16 @@ class DevicePointCloud:
         clouds, ctx, _ = DevicePointCloud._resident_batch(clouds, None, "select")
         n = len(clouds)
         lo, hi = DevicePointCloud._per_cloud_u32(lo, n, "select"), DevicePointCloud._per_cloud_u32(hi, n, "select")
-        outs, d_index, uploaded, d_values = [], [], [], []
+        uploaded, d_values = [], []
+
+        def call(a):
+            _abi.check(
+                ctx.lib.a3d_point_clouds_select_device(
+                    ctx.handle, a.views, a.colors, n, (C.c_void_p * n)(*d_values), lo, hi, a.out_points, a.out_normals,
+                    a.out_colors, a.side["index"], a.capacities, a.lens),
+                "a3d_point_clouds_select_device",
+            )
+
         try:
             for c, v in zip(clouds, values):
                 if isinstance(v, (C.c_void_p, int)):
@@ -804,34 +792,11 @@ class DevicePointCloud:
                     raise _abi.InvalidParameter(f"select: values are booleans or unsigned 32-bit integers (got {v.dtype})")
                 uploaded.append(ctx.to_device(np.ascontiguousarray(v, np.uint32)) if c.n else ctx.malloc(4))
                 d_values.append(uploaded[-1])
-            for c in clouds:
-                outs.append(DevicePointCloud._allocate(ctx, c.n, c.d_normals is not None, c.d_colors is not None))
-                if return_index:
-                    d_index.append(ctx.malloc(max(1, c.n) * 4))
-            lens = (C.c_uint64 * n)()
-            colours = any(c.d_colors is not None for c in clouds)
-            _abi.check(
-                ctx.lib.a3d_point_clouds_select_device(
-                    ctx.handle, DevicePointCloud._views(clouds), DevicePointCloud._colors_array(clouds) if colours else None,
-                    n, (C.c_void_p * n)(*d_values), lo, hi, (C.c_void_p * n)(*[x.d_points for x in outs]),
-                    (C.c_void_p * n)(*[x.d_normals for x in outs]), DevicePointCloud._colors_array(outs) if colours else None,
-                    (C.c_void_p * n)(*d_index) if return_index else None, (C.c_uint64 * n)(*[c.n for c in clouds]), lens),
-                "a3d_point_clouds_select_device",
-            )
-            for x, k in zip(outs, lens):
-                x.n = int(k)
-            index = None
-            if return_index:
-                index = [ctx.to_host(d, np.empty(x.n, np.uint32)) if x.n else np.empty(0, np.uint32)
-                         for d, x in zip(d_index, outs)]
-        except BaseException:
-            for x in outs:
-                x.free()
-            raise
+            outs, host = DevicePointCloud._compact(ctx, clouds, index=return_index, call=call)
         finally:
-            for d in d_index + uploaded:
+            for d in uploaded:
                 ctx.free(d)
-        return (outs, index) if return_index else outs
+        return (outs, host["index"]) if return_index else outs
 
     def select(self, values_or_mask, lo=1, hi=0xFFFFFFFF, return_index=False):
         """The rows p of this cloud with lo <= values[p] <= hi, in input order, as a new resident cloud
